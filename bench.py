@@ -16,11 +16,18 @@ with every input already resident in HBM.  Documents shard across ranks with no 
 collective (weak scaling, 8 docs per GPU); the only collective is the one-shot RCCL broadcast of the
 packed weight blob from rank 0.  Synthetic inputs and weights (no checkpoint / dataset offline).
 
-Rank 0 prints ONE JSON line (contract in the task statement) that also carries
+Rank 0 prints ONE JSON line (metric, value, unit, higher_is_better, dtype, ms_per_step = wall milliseconds of one
+timed step) that also carries
   roofline     : the dominant kernel (head_dim-256 decoder flash attention), timed per launch with HIP
-                 events on the launch stream inside the timed region, against the dense f16 MFMA peak;
-  cpu_baseline : the CPU oracle (a port pinned to the reference by golden vectors) timed on this
-                 host's cores on a bounded sample and scaled to documents/s.
+                 events on the launch stream inside the timed region, against the dense f16 MFMA peak.
+A plain run does nothing else: set-up, warm-up, the timed steps, the optional output dump, the line.
+--full adds what takes work of its own after the timed steps (its fields are null without it):
+  roofline_unwarp : the full-resolution gather, timed in launches of its own;
+  cpu_baseline    : the CPU oracle (a port pinned to the reference by golden vectors) timed on this
+                    host's cores on a bounded sample and scaled to documents/s, with three full-size parity checks;
+  other_configs   : bounded legs for the other BASELINE.json configurations, each with a parity figure.
+--dump-outputs DIR writes what the last timed step returned on rank 0 (see dump_outputs); the inputs and weights
+are seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -29,8 +36,10 @@ import sys
 import time
 
 _T_PROCESS_START = time.perf_counter()
-CFG3_FULL_DEADLINE_S = 900        # other_configs: configs[3] runs its stated 32 documents (5.6 minutes) if the process is younger than
-                                  # this when the leg starts (a 25-step run reaches it at ~600 s and ends at ~17 minutes)
+CFG3_FULL_DEADLINE_S = 480        # other_configs: configs[3] runs its stated 32 documents (5.6 minutes) only if, projected from the
+                                  # north_star_batch32 leg's time, the leg would end this young; else 4 documents: a --full run
+                                  # with a few steps has to end within 10 minutes
+DUMP_ELEMS = 1 << 22              # --dump-outputs: at most this many values per array (16 MiB of f32), a seeded sample above it
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
@@ -202,6 +211,27 @@ def per_rank_seconds(elapsed, world, dev):
     return [float(x.item()) for x in out]
 
 
+def _dump_sample(t, limit=DUMP_ELEMS):
+    """`t` flattened as float32 on the host: whole when it has at most `limit` values, otherwise the values at `limit`
+    positions drawn (with repetition, then sorted) by a fixed seed - the same positions for the same shape in every run."""
+    flat = t.reshape(-1)
+    if flat.numel() > limit:
+        idx = np.sort(np.random.default_rng(0).integers(0, flat.numel(), limit))
+        flat = flat[torch.from_numpy(idx).to(flat.device)]
+    return flat.float().cpu().numpy()
+
+
+def dump_outputs(out_dir, flow, outs):
+    """What the timed path returned in its last step, as float32 .npy files:
+      flow.npy        [B, 2, G, G] coordinate maps after the hypothesis mean + clamp (flattened when sampled);
+      unwarped_u8.npy the batch's full-resolution u8 unwarped images [B, H, W, 3] (a seeded sample of DUMP_ELEMS values
+                      at the default 3508x2480)."""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in (("flow", flow), ("unwarped_u8", outs)):
+        a = _dump_sample(t)
+        np.save(os.path.join(out_dir, f"{name}.npy"), a.reshape(t.shape) if a.size == t.numel() else a)
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -220,6 +250,10 @@ def main(argv=None):
     ap.add_argument("--no-other-configs", action="store_true",
                     help="skip the bounded legs for BASELINE configs[3], configs[4] and the reference's native point")
     ap.add_argument("--backend", default="nccl", help="process-group backend (nccl = RCCL; the CPU test of the rank logic uses gloo)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure roofline_unwarp, cpu_baseline (+ parity) and other_configs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (rank 0) to DIR/<name>.npy as float32")
     args = ap.parse_args(argv)
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -307,6 +341,8 @@ def main(argv=None):
     launches, attn_ms = eng.profile_read()
     eng.profile(False)
     assert bool(torch.isfinite(flow).all()), "non-finite coordinates"
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, flow, outs)
 
     if rank == 0:
         docs_total = B * world * args.steps
@@ -352,7 +388,7 @@ def main(argv=None):
         # timed here, after the timed region, on this run's own documents (all B in one launch); the fused u8 tail the
         # timed region actually uses (6 B/px algorithmic, VALU-bound) is reported beside it.
         roof_unwarp = None
-        if unwarp_events:
+        if args.full and unwarp_events:
             ms_u8 = sum(a.elapsed_time(b) for a, b in unwarp_events) / len(unwarp_events)
             srcf = src_u8.permute(0, 3, 1, 2).float().contiguous()                        # [B,3,H,W] f32 0..255
             # the gather pattern is set by the flow: the sampler's output under RANDOM synthetic weights is white-noise-
@@ -416,7 +452,7 @@ def main(argv=None):
         if not args.no_split_weights:
             pass   # split weights double the GEMM MFMAs; algorithmic FLOPs are unchanged by definition
         cpu = None
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             # engine output for the run's first loop step (all samples; sample 0 is compared with the oracle)
             t_first = tab.model_time(S - 1)
             eng.prepare(y512, mask_cat, mask_y512, line_msk)
@@ -437,7 +473,7 @@ def main(argv=None):
                 if not par["ok"]:
                     raise SystemExit(f"PARITY FAILURE at G={G}: {par}")
         others = None
-        if world == 1 and not args.no_other_configs and (G, S, args.sampler) == (288, 50, "ddim"):
+        if args.full and world == 1 and not args.no_other_configs and (G, S, args.sampler) == (288, 50, "ddim"):
             del y512, mask_cat, mask_y512, line_msk, x_T, src_u8, outs
             eng.workspace = None
             torch.cuda.empty_cache()
@@ -495,8 +531,9 @@ def other_configs(dev, blob288, H, FH, FW, want_cpu=True, legs=("cfg4", "ns32", 
       ns32        north_star's stated target point: 32 documents, 50-step DDIM, G = 288, + unwarp: ONE whole batch (round 6);
       configs[3]  (parity since round 6: the fused step vs the oracle AND document 0 of the batch after all 250 steps == itself alone)
                   250-step DDPM ancestral sampling at G = 288 at its STATED 32 documents (x H hypotheses = 64 samples, one
-                  engine batch, ~5.5 minutes; round 5) - unless the process has already run longer than CFG3_FULL_DEADLINE_S,
-                  in which case 4 documents are run and the leg says so (the loop is strictly per-document work, so
+                  engine batch, ~5.5 minutes; round 5) - unless the process would be older than CFG3_FULL_DEADLINE_S at its
+                  end (projected as 5x the ns32 leg's time; no ns32 leg, no projection), in which case 4 documents are run and
+                  the leg says so (the loop is strictly per-document work, so
                   documents/s at 4 per batch is a lower bound of the rate at 32);
       native      the reference's own operating point (admin/local.py:28-35,82: G = 64, 3 DDIM steps, 2 hypotheses, one
                   document at a time) from a decoded IMAGE: ingest + the three pre-stage nets + sampling + unwarp."""
@@ -504,6 +541,7 @@ def other_configs(dev, blob288, H, FH, FW, want_cpu=True, legs=("cfg4", "ns32", 
     from dvd_amd import ops, prestage, sampler, schedule, synth
     from dvd_amd.engine import Engine
     out = {}
+    ns32_s = None
     G = 288
     gen = torch.Generator(device=dev)
     gen.manual_seed(4321)
@@ -574,6 +612,7 @@ def other_configs(dev, blob288, H, FH, FW, want_cpu=True, legs=("cfg4", "ns32", 
             flow = sampler.sample(eng, tab, x_T)
             return flow, ops.unwarp_u8_batch(flow, src_u8)
         dt, (flow, outs) = timed(ns32)
+        ns32_s = dt
         del eng
         torch.cuda.empty_cache()
         eng1 = Engine(G, 1, H, device=dev)
@@ -592,7 +631,8 @@ def other_configs(dev, blob288, H, FH, FW, want_cpu=True, legs=("cfg4", "ns32", 
 
     if "cfg3" in legs:
         # ---- configs[3]: 250-step DDPM at the stated 32 documents (4 if the run is already long) ------------------------
-        B = 32 if time.perf_counter() - _T_PROCESS_START < CFG3_FULL_DEADLINE_S else 4
+        full_ok = ns32_s is not None and time.perf_counter() - _T_PROCESS_START + 5 * ns32_s < CFG3_FULL_DEADLINE_S
+        B = 32 if full_ok else 4
         eng = Engine(G, B, H, device=dev)
         eng.bind_blob(blob288)
         cond = docs(B, G)
@@ -644,7 +684,7 @@ def other_configs(dev, blob288, H, FH, FW, want_cpu=True, legs=("cfg4", "ns32", 
         del eng1, flow1, x_T1
         out["configs[3]"] = {"workload": (f"BASELINE configs[3]: batch={B} documents x {H} hypotheses" if B == 32 else
                                           f"BASELINE configs[3] at batch={B} instead of 32 documents (x {H} hypotheses; the run "
-                                          f"was past {CFG3_FULL_DEADLINE_S} s when this leg started)") +
+                                          f"would have ended past {CFG3_FULL_DEADLINE_S} s with 32)") +
                                          ": 250-step DDPM ancestral sampling, 288x288 grid (no unwarp in this configuration)",
                              "batches_timed": 1, "ms_per_batch": round(dt * 1e3, 1), "value": round(B / dt, 5),
                              "unit": "documents/s", "finite": bool(torch.isfinite(flow).all()), "parity": par}
@@ -753,7 +793,9 @@ def cpu_baseline(grid, hyp, steps, check=None):
     # torch's intra-op pool stops scaling (and then collapses) long before a 256-thread host is full on these op sizes:
     # the thread count is the MEASURED knee of this host (one G=64 sample-step per candidate, best wins), not a fixed cap.
     # `cores` reports the threads used.
-    ncpu = os.cpu_count() or 1
+    # the CPUs this process may use (its affinity mask), and no more threads than OMP_NUM_THREADS asks for when it is set:
+    # on a shared host the probes above that only oversubscribe the cores the job was given
+    ncpu = min(len(os.sched_getaffinity(0)), int(os.environ.get("OMP_NUM_THREADS") or 1 << 30))
     cores, knee = ncpu, None
 
     def time_one(g):

@@ -64,7 +64,7 @@ cat $O/c4_ab.txt
 ( timeout 300 python benchmarks/gemm_t384_stamps.py 1536 1536; timeout 300 python benchmarks/gemm_t384_stamps.py 3072 1536 ) > $O/c4_stamps.txt 2>&1
 cat $O/c4_stamps.txt
 timeout 900 python -m pytest tests/test_gpu_engine.py -x -q -k "baseline_grid or batched_documents or forward_stages or g96" 2>&1 | tail -5 | tee $O/c4_engine.txt
-timeout 600 python bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-other-configs 2>/dev/null | tail -1 > $O/c4_bench.json
+timeout 600 python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-other-configs 2>/dev/null | tail -1 > $O/c4_bench.json
 python - <<'PY'
 import json
 d=json.loads(open('gpurun_out/r5/c4_bench.json').read())
@@ -526,14 +526,14 @@ cat $O
 ;;
 40)   # was call40_head.sh
 # round 5 call 40: whole GPU suite + the default bench run at HEAD (after the ring kernels)
-cd /root/repo; mkdir -p gpurun_out/r5
-python -c "import __graft_entry__ as g; g.smoke()" > gpurun_out/r5/call40_smoke.log 2>&1; echo "smoke rc=$?"; tail -1 gpurun_out/r5/call40_smoke.log
-( time python -m pytest tests -q -m gpu --durations=6 ) > gpurun_out/r5/call40_gpu_tests.log 2>&1; echo "gpu tests rc=$?"
-grep -E "passed|failed|^real|FAILED" gpurun_out/r5/call40_gpu_tests.log | tail -5
-( time python bench.py ) > gpurun_out/r5/call40_bench_default.json 2> gpurun_out/r5/call40_bench_default.err; echo "bench rc=$?"
-grep real gpurun_out/r5/call40_bench_default.err
+O=${O:-bench_out/r5}; mkdir -p $O
+python -c "import __graft_entry__ as g; g.smoke()" > $O/call40_smoke.log 2>&1; echo "smoke rc=$?"; tail -1 $O/call40_smoke.log
+( time python -m pytest tests -q -m gpu --durations=6 ) > $O/call40_gpu_tests.log 2>&1; echo "gpu tests rc=$?"
+grep -E "passed|failed|^real|FAILED" $O/call40_gpu_tests.log | tail -5
+( time python bench.py --full ) > $O/call40_bench_default.json 2> $O/call40_bench_default.err; echo "bench rc=$?"
+grep real $O/call40_bench_default.err
 python -c "
-import json; d=json.loads(open('gpurun_out/r5/call40_bench_default.json').read().strip().splitlines()[-1]); print('bench', d['value'], d['ms_per_step'], d['roofline']['achieved'], d['roofline']['frac'], d['roofline_unwarp']['frac']); print({k: (v['value'], v['parity']['ok'] if v.get('parity') else None) for k, v in d['other_configs'].items()})"
+import json; d=json.loads(open('$O/call40_bench_default.json').read().strip().splitlines()[-1]); print('bench', d['value'], d['ms_per_step'], d['roofline']['achieved'], d['roofline']['frac'], d['roofline_unwarp']['frac']); print({k: (v['value'], v['parity']['ok'] if v.get('parity') else None) for k, v in d['other_configs'].items()})"
 ;;
 41)   # was call41_spread.sh
 cd /root/repo; mkdir -p gpurun_out/r5
@@ -541,11 +541,11 @@ python benchmarks/lab/big_spread_ab.py 2>&1 | grep -v amdgpu.ids > gpurun_out/r5
 ;;
 42)   # was call42_driverlike.sh
 # round 5 call 42: the driver's bench invocation at the last commit of the round
-cd /root/repo; mkdir -p gpurun_out/r5
-( time python bench.py --gpus 1 --steps 20 --warmup 5 ) > gpurun_out/r5/call42_bench_driverlike.json 2> gpurun_out/r5/call42_bench_driverlike.err; echo "bench rc=$?"
-grep real gpurun_out/r5/call42_bench_driverlike.err
+O=${O:-bench_out/r5}; mkdir -p $O
+( time python bench.py --full --gpus 1 --steps 20 --warmup 5 ) > $O/call42_bench_driverlike.json 2> $O/call42_bench_driverlike.err; echo "bench rc=$?"
+grep real $O/call42_bench_driverlike.err
 python -c "
-import json; d=json.loads(open('gpurun_out/r5/call42_bench_driverlike.json').read().strip().splitlines()[-1]); print('bench', d['value'], d['ms_per_step'], d['roofline']['achieved'], d['roofline']['frac'], d['roofline_unwarp']['achieved'], d['roofline_unwarp']['frac'], d['cpu_baseline']['value'], d['cpu_baseline']['cores']); print({k: (v['value'], v['parity']['ok'] if v.get('parity') else None) for k, v in d['other_configs'].items()})"
+import json; d=json.loads(open('$O/call42_bench_driverlike.json').read().strip().splitlines()[-1]); print('bench', d['value'], d['ms_per_step'], d['roofline']['achieved'], d['roofline']['frac'], d['roofline_unwarp']['achieved'], d['roofline_unwarp']['frac'], d['cpu_baseline']['value'], d['cpu_baseline']['cores']); print({k: (v['value'], v['parity']['ok'] if v.get('parity') else None) for k, v in d['other_configs'].items()})"
 ;;
 *) echo "usage: bash benchmarks/r5_calls.sh <N>"; exit 2 ;;
 esac

@@ -112,7 +112,7 @@ python -c "import __graft_entry__ as g; g.smoke()" > $F/smoke.log 2>&1; echo "sm
 grep -E "passed|failed|^real" $F/gpu_tests.log | tail -3
 bash benchmarks/pmc_round.sh r6 > $F/pmc_round.log 2>&1; echo "pmc rc=$?"
 cp gpurun_out/pmc_r6/r6_pmc_*.json gpurun_out/pmc_r6/r6_pmc_*.txt profiles/ 2>/dev/null
-( time python bench.py --gpus 1 --steps 20 --warmup 5 ) > $F/bench_driverlike.json 2> $F/bench_driverlike.err; echo "bench rc=$?"
+( time python bench.py --full --gpus 1 --steps 20 --warmup 5 ) > $F/bench_driverlike.json 2> $F/bench_driverlike.err; echo "bench rc=$?"
 grep real $F/bench_driverlike.err
 python -c "
 import json; d=json.loads(open('$F/bench_driverlike.json').read().strip().splitlines()[-1]); print('bench', d['value'], d['ms_per_step'], d['roofline']['achieved'], d['roofline']['frac'], d['roofline'].get('traffic'), d['roofline_unwarp']['achieved'], d['roofline_unwarp']['frac'], d['cpu_baseline']['value'], d['cpu_baseline']['cores']); print({k: (v['value'], v['parity']['ok'] if v.get('parity') else None) for k, v in d['other_configs'].items()})"

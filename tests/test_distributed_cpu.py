@@ -401,6 +401,48 @@ def test_bench_launches_its_own_ranks(tmp_path):
     assert line["config"]["parallelism"].startswith("dp2")
 
 
+@pytest.mark.parametrize("full", [False, True])
+def test_bench_single_rank_plain_full_and_dump(tmp_path, full):
+    """`bench.py --gpus 1`: a plain run reports the headline and leaves the extras null; --full measures roofline_unwarp;
+    --dump-outputs writes the last timed step's outputs as float32 .npy in their own shapes (small enough to be whole)."""
+    import json
+    import subprocess
+    import numpy as np
+    (tmp_path / "sitecustomize.py").write_text(_SITECUSTOMIZE)
+    env = dict(os.environ, DVD_TEST_STUB_BENCH="1", DVD_TEST_ROOT=ROOT, RANK="0", LOCAL_RANK="0", WORLD_SIZE="1",
+               PYTHONPATH=os.pathsep.join([str(tmp_path), ROOT, os.environ.get("PYTHONPATH", "")]))
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--grid", "16",
+           "--docs", "3", "--ddim-steps", "3", "--full-res", "32x24", "--no-cpu-baseline", "--dump-outputs", str(tmp_path / "out")]
+    res = subprocess.run(cmd + (["--full"] if full else []), env=env, cwd=str(tmp_path), capture_output=True, text=True,
+                         timeout=600)
+    assert res.returncode == 0, res.stderr[-3000:]
+    lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, res.stdout[-2000:]
+    line = json.loads(lines[0])
+    assert line["steps"] == 2 and line["warmup"] == 1 and line["ms_per_step"] > 0 and line["value"] > 0
+    assert line["unit"] == "documents/s" and line["higher_is_better"] is True and line["dtype"] == "f16"
+    assert line["cpu_baseline"] is None and line["other_configs"] is None
+    assert (line["roofline_unwarp"] is not None) == full
+    shapes = {"flow": (3, 2, 16, 16), "unwarped_u8": (3, 32, 24, 3)}
+    assert sorted(os.listdir(tmp_path / "out")) == sorted(f"{n}.npy" for n in shapes)
+    for name, shape in shapes.items():
+        a = np.load(tmp_path / "out" / f"{name}.npy")
+        assert a.dtype == np.float32 and a.shape == shape, (name, a.dtype, a.shape)
+
+
+def test_bench_dump_sample_is_seeded_and_bounded():
+    """An output larger than the dump limit is written as the same seeded sample of its values in every run."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_dump", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    t = torch.arange(5000, dtype=torch.float32).reshape(50, 100)
+    a, b = bench._dump_sample(t, limit=300), bench._dump_sample(t.clone(), limit=300)
+    assert a.dtype == "float32" and a.shape == (300,) and (a == b).all()
+    assert (a[1:] >= a[:-1]).all() and a.max() < 5000
+    assert bench._dump_sample(t, limit=5000).shape == (5000,)
+
+
 def test_bench_launcher_propagates_a_rank_failure(tmp_path):
     """A rank that dies must end the job with a non-zero exit code instead of leaving the others in a collective."""
     import subprocess

@@ -294,7 +294,7 @@ def test_large_batch_of_small_grids_matches_single(docs):
     """at the reference's own grid (G = 64) an engine batch of >= 8 documents x 2 hypotheses has >= 16 384
     token rows and takes the 256 x 256 GEMM kernel for its N % 256 == 0 shapes (engine.hip: dtype 3), a single document the
     128 x 128 one - a whole 3-step roll-out of documents 0, 1 and the last one must still equal the single-document engine's
-    BIT FOR BIT (bench.py's native_point legs check document 0 only, and only in the driver's run)."""
+    BIT FOR BIT (bench.py's native_point legs check document 0 only, and only in a --full run)."""
     from dvd_amd import sampler, schedule
     from dvd_amd.engine import Engine
     grid = 64
@@ -343,7 +343,7 @@ def test_engine_at_the_baseline_grid_batch_equals_single():
     (t_model > 600: init_feat <- feat) and an evaluation on the warped-feature branch (feat_mode 2, init_flow = the first
     step's x0) of two documents batched give the same bits as each document alone (no cross-document arithmetic at the
     production size).  Parity with the oracle at this grid: test_long_loop_vs_oracle_trace[ddim_g288_s50_tame] (the whole
-    50-step loop), and every bench.py run (two live-oracle evaluations)."""
+    50-step loop), and every bench.py --full run (two live-oracle evaluations)."""
     from dvd_amd import sampler, schedule
     from dvd_amd.engine import Engine
     from oracle import dvd_oracle as O
