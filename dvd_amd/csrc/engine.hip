@@ -325,6 +325,12 @@ static int gemm(int dtype, int M, int N, int K, int batch, const void* A, int ld
                 int bias_row, int act, const float* pos, int pos_rows, const float* gate, int gate_rows,
                 const float* res, int ldres, long sRes, void* stream, const void* Alo = nullptr,
                 const void* Blo = nullptr) {
+  // every pointer an engine GEMM gets is 16-byte aligned (256-byte workspace buffers, 16-byte weights, offsets in whole
+  // rows): an unaligned output or epilogue operand would move a 384 x 256-tile call site to a kernel with other bits
+  // (tests/test_gemm_dispatch.py), so it is an error here rather than a silent change of kernel
+  auto a16 = [](const void* q) { return ((uintptr_t)q % 16) == 0; };
+  DVD_REQUIRE(a16(C32) && a16(C16) && a16(bias) && a16(pos) && a16(gate) && a16(res),
+              "engine gemm: output / epilogue pointers must be 16-byte aligned");
   dvd_gemm_desc d;
   memset(&d, 0, sizeof(d));
   d.A_lo = Alo; d.B_lo = Blo; d.lo_scale = 1.f;

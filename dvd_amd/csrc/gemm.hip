@@ -2113,7 +2113,25 @@ static unsigned long long* g_gemm_stamps = nullptr;
 extern "C" int dvd_gemm_debug_stamps(void* dev_u64) { g_gemm_stamps = (unsigned long long*)dev_u64; return DVD_OK; }
 #endif
 
-extern "C" int dvd_gemm_nt(const dvd_gemm_desc* d, void* stream) {
+namespace {
+// Every kernel dvd_gemm_nt can launch (the lab build's experiments included).
+enum class GemmKernel { split128, split256, t384, big, f32_narrow, ring256, ring128, plain, lab_ring, lab_big16, lab_big2, lab_w8 };
+
+// What dvd_gemm_nt launches for a descriptor: the kernel and the template arguments of its instance.  gemm_select is the ONE
+// place of the selection rules: dvd_gemm_nt launches what it returns, dvd_gemm_kernel_name names it.
+struct GemmChoice {
+  GemmKernel kernel = GemmKernel::plain;
+  int vec_epilogue = 0;    // GemmArgs::vec_epilogue
+  int variant = 0;         // split128: <B_lo>; big: <variant>; f32_narrow: <variant>; plain: <F32, PD = variant>
+  int dbg = 0, fl = 0;     // t384 <DBG, FL, FULL, X16>
+  bool full = false, x16 = false;
+  int debug = 0;           // GemmArgs::debug (lab: DVD_GEMM_DEBUG)
+};
+}  // namespace
+
+// Validation and kernel choice: host-only (no device call), a function of the descriptor alone in the product build (the lab
+// build also reads its A/B switches).  Returns DVD_E_ARG, with the reason in dvd_last_error, for a descriptor it refuses.
+static int gemm_select(const dvd_gemm_desc* d, GemmChoice& c) {
   DVD_REQUIRE(d && d->A && d->B && (d->C32 || d->C16), "gemm: null pointer");
   DVD_REQUIRE(d->dtype == 0 || d->dtype == 1, "gemm: dtype must be 0 (f16) or 1 (f32)");
   const int bk = d->dtype == 1 ? 16 : 64, esz = d->dtype == 1 ? 4 : 2;
@@ -2126,11 +2144,187 @@ extern "C" int dvd_gemm_nt(const dvd_gemm_desc* d, void* stream) {
               "gemm: operands must be 16-byte aligned (lda=%d ldb=%d)", d->lda, d->ldb);
   DVD_REQUIRE(!d->gate || d->gate_rows > 0, "gemm: gate needs gate_rows");
   DVD_REQUIRE(!d->pos || d->pos_rows > 0, "gemm: pos needs pos_rows");
-  GemmArgs p;
   DVD_REQUIRE(!(d->B_lo && d->A_lo), "gemm: only one operand may be split");
   DVD_REQUIRE((!d->B_lo && !d->A_lo) ||
                   (d->dtype == 0 && ((uintptr_t)d->B_lo % 16) == 0 && ((uintptr_t)d->A_lo % 16) == 0),
               "gemm: split operands need dtype f16, 16-byte aligned");
+  c = GemmChoice();
+
+  // The product library has no switches: the kernel is a function of the descriptor alone.  The lab build
+  // (-DDVD_LAB, benchmarks/lab/libdvd_hip_lab.so) keeps the A/B switches of the experiments that were measured.
+#ifdef DVD_LAB
+  { const char* dbg = getenv("DVD_GEMM_DEBUG"); c.debug = dbg ? atoi(dbg) : 0; }
+  const bool lab_scalar_epi = getenv("DVD_GEMM_SCALAR_EPILOGUE"), lab_v1 = getenv("DVD_GEMM_V1"),
+             lab_twopass = getenv("DVD_GEMM_TWOPASS"), lab_spread = getenv("DVD_GEMM_SPREAD"),
+             lab_no_t384 = getenv("DVD_GEMM_NO_T384") || c.debug;
+#else
+  constexpr bool lab_scalar_epi = false, lab_v1 = false, lab_twopass = false, lab_no_t384 = false;
+#endif
+  {
+    auto al = [](const void* q, size_t a) { return ((uintptr_t)q % a) == 0; };
+    bool ok = d->N % 8 == 0 && !lab_scalar_epi;
+    if (d->C32) ok = ok && d->ldc % 4 == 0 && d->strideC32 % 4 == 0 && al(d->C32, 16);
+    if (d->C16) ok = ok && d->ldc16 % 8 == 0 && d->strideC16 % 8 == 0 && al(d->C16, 16);
+    if (d->bias && !d->bias_row) ok = ok && al(d->bias, 16) && d->strideBias % 4 == 0;
+    if (d->pos) ok = ok && d->ldpos % 4 == 0 && al(d->pos, 16);
+    if (d->gate) ok = ok && d->ldgate % 4 == 0 && d->strideGate % 4 == 0 && al(d->gate, 16);
+    if (d->res) ok = ok && d->ldres % 4 == 0 && d->strideRes % 4 == 0 && al(d->res, 16);
+    c.vec_epilogue = ok ? 1 : 0;
+  }
+  // large-tile kernel for the big f16 GEMMs (decoder): N a multiple of 256, at least a few row tiles
+  // A document must get the same bits whether it is sampled alone or in a batch.  Two ways this holds here: (a) within a
+  // problem family the kernel is chosen from the descriptor's shape and flags, never from M; (b) where the choice DOES follow
+  // M, the kernels on both sides accumulate every output in the same sequence and run the same epilogue arithmetic - the same
+  // bits, tested as such.  The places of (b): small_tiles 1 vs 2 below (the engine switches at 16 384 token rows;
+  // tests/test_gpu_gemm.py::test_gemm_small_family_engine_shapes_same_bits); the 128 x 128 family's ring128 / ring256 /
+  // gemm_nt_kernel choice by tile count (tests/test_gpu_gemm.py::test_gemm_ring128_kernel); the FULL (M % 384 == 0) and
+  // ragged instances of gemm_nt_t384_kernel (tests/test_gpu_gemm_callsites.py::test_t384_full_and_ragged_same_bits).
+  // tests/test_gemm_dispatch.py pins the kernel of every engine call site against these classes.
+  // small_tiles 1: the caller's problem family is small: 128x128 tiles everywhere.  small_tiles 2: the same family with MANY
+  // rows (a large batch of small grids): shapes with N % 256 == 0 take the 256x256 kernel in its TWO-SWEEP form - low parts
+  // first, scale, high parts, k ascending in 16-deep MFMA steps: exactly the 128x128 kernel's accumulation sequence, so a
+  // document still gets the same bits alone (small_tiles 1) and in a large batch (tests/test_gpu_gemm.py) - everything else
+  // stays on the 128x128 kernel.
+  const bool small = d->small_tiles == 1, small_many = d->small_tiles == 2;
+  const bool big = d->dtype == 0 && d->N % 256 == 0 && !lab_v1 && !small;
+  if (d->dtype == 0 && d->N % 128 == 0 && d->N % 256 != 0 && !d->A_lo && (!d->B_lo || d->lo_scale == 1.f) &&
+      d->K % 32 == 0 && !lab_twopass && !lab_v1 && !small && !small_many) {
+    // 256 x 128 tiles for the DiT block's 384-wide GEMMs: (hi, lo) in one pass, or ONE (dithered) weight tensor
+    c.kernel = GemmKernel::split128;
+    c.variant = d->B_lo ? 1 : 0;
+    return DVD_OK;
+  }
+  if (big && d->B_lo && !d->A_lo && d->lo_scale == 1.f && d->K % 32 == 0 && !lab_twopass && !small_many) {
+    c.kernel = GemmKernel::split256;
+    return DVD_OK;
+  }
+#ifdef DVD_LAB
+  if (big && !d->B_lo && !d->A_lo && d->K % 32 == 0 && getenv("DVD_GEMM_RING")) {
+    // lab: the split kernel's 3-stage skewed pipeline on one weight tensor, for A/B runs against gemm_nt_big_kernel
+    c.kernel = GemmKernel::lab_ring;
+    return DVD_OK;
+  }
+  if (big && !d->B_lo && !d->A_lo && c.vec_epilogue && !d->pos && !d->gate && getenv("DVD_GEMM_M16")) {
+    // lab: the 16x16x32-MFMA variant of the 256 x 256 kernel (measured 1-7 % slower, see gemm_nt_big16_kernel)
+    c.kernel = GemmKernel::lab_big16;
+    return DVD_OK;
+  }
+  if (big && !d->B_lo && !d->A_lo && d->K % 32 == 0 && c.vec_epilogue && !d->pos && !d->gate && !(d->bias && d->bias_row) &&
+      getenv("DVD_GEMM_BIG2")) {
+    c.kernel = GemmKernel::lab_big2;
+    return DVD_OK;
+  }
+#endif
+  if (big && !d->B_lo && !d->A_lo && !small_many && c.vec_epilogue && !d->pos && !d->gate && !(d->bias && d->bias_row) &&
+      !(d->res && d->act == 1) && d->K % 128 == 0 && d->K >= 256 && !lab_no_t384) {
+    // 384 x 256 tiles, 4-slot half-slab ring, generated K loop.  Since round 6 (16x16x32 MFMAs) its bits differ from
+    // gemm_nt_big_kernel's: a descriptor that loses vec_epilogue (an unaligned C / residual pointer or leading dimension)
+    // falls through to a kernel with DIFFERENT bits - the engine's workspace layout keeps its call sites aligned
+    // (tests/test_gemm_dispatch.py).
+    c.kernel = GemmKernel::t384;
+    // the epilogue flavour is a function of the descriptor (never of the data): see gemm_nt_t384_kernel
+    c.fl = (d->C16 && !d->C32 && !d->res) ? 0 : (d->C32 && !d->C16 && d->act != 1) ? (d->res ? 2 : 1) : (d->res ? 4 : 3);
+    c.full = d->M % 384 == 0;
+#ifdef DVD_LAB
+    int tdbg = 0;
+    if (const char* e = getenv("DVD_GEMM_T384_DBG")) tdbg = atoi(e);
+    c.x16 = getenv("DVD_GEMM_T384_M32") ? false : (getenv("DVD_GEMM_T384_X16") ? true : (T384_X16 != 0));
+    c.dbg = c.x16 ? (tdbg == 5 ? 5 : 0) : (tdbg >= 1 && tdbg <= 6 ? tdbg : 0);
+#else
+    c.x16 = T384_X16 != 0;
+#endif
+    return DVD_OK;
+  }
+  if (big) {
+    c.kernel = GemmKernel::big;
+#ifdef DVD_LAB
+    const int dv = c.debug;
+    c.variant = (dv == 1 || dv == 2 || dv == 3 || dv == 5 || dv == 6 || dv == 7) ? dv : lab_spread ? 4 : 0;
+#endif
+    return DVD_OK;
+  }
+  if (d->dtype == 1 && d->N <= 64 && d->C32 && !d->C16 && !d->pos && !d->gate && !d->res && !d->bias_row &&
+      (d->act == 0 || d->act == 2) && !d->A_lo && !d->B_lo) {
+    c.kernel = GemmKernel::f32_narrow;
+    c.variant = d->N <= 32 ? 1 : 2;
+    return DVD_OK;
+  }
+  {
+    // f16 problems with few 128 x 128 tiles: the LDS-DMA ring kernel (same bits; see gemm_nt_ring128_kernel)
+    const long ntm = cdiv(d->M, 128), ntn = cdiv(d->N, 128);
+    auto al16 = [](const void* q) { return ((uintptr_t)q % 16) == 0; };
+    bool ring = d->dtype != 1 && d->K % 64 == 0 && d->K >= 128 && d->lda % 8 == 0 && d->ldb % 8 == 0 && d->strideA % 8 == 0 &&
+                d->strideB % 8 == 0 && al16(d->A) && al16(d->B) && al16(d->A_lo) && al16(d->B_lo) &&
+                ntm * ntn <= RING128_MAX_TILES && (long)d->M * d->lda < (1l << 30) && (long)d->N * d->ldb < (1l << 30);
+#ifdef DVD_LAB
+    if (const char* e = getenv("DVD_GEMM_RING128")) ring = ring && atoi(e) != 0;
+#endif
+    bool ring256 = d->dtype != 1 && d->N % 256 == 0 && d->K % 32 == 0 && d->K >= 128 && d->lda % 8 == 0 && d->ldb % 8 == 0 &&
+                   d->strideA % 8 == 0 && d->strideB % 8 == 0 && al16(d->A) && al16(d->B) && al16(d->A_lo) && al16(d->B_lo) &&
+                   ntm * (d->N / 256) <= RING256_MAX_TILES && ntm * (d->N / 256) >= RING256_MIN_TILES &&
+                   (long)d->M * d->lda < (1l << 30) &&
+                   (long)d->N * d->ldb < (1l << 30);
+#ifdef DVD_LAB
+    if (const char* e = getenv("DVD_GEMM_RING256")) {       // 0: off; 2: also below RING256_MIN_TILES (tests, A/B runs)
+      if (atoi(e) == 0) ring256 = false;
+      if (atoi(e) == 2) ring256 = d->dtype != 1 && d->N % 256 == 0 && d->K >= 128 && d->lda % 8 == 0 && d->ldb % 8 == 0 && d->strideA % 8 == 0 &&
+                                  d->strideB % 8 == 0 && al16(d->A) && al16(d->B) && al16(d->A_lo) && al16(d->B_lo) &&
+                                  ntm * (d->N / 256) <= RING256_MAX_TILES;
+    }
+#endif
+    if (ring256) { c.kernel = GemmKernel::ring256; return DVD_OK; }
+    if (ring) { c.kernel = GemmKernel::ring128; return DVD_OK; }
+  }
+#ifdef DVD_LAB
+  if (const char* e = getenv("DVD_GEMM_W8"); e && atoi(e) != 0 && d->dtype != 1) {   // lab: two waves per SIMD on each tile
+    c.kernel = GemmKernel::lab_w8;
+    return DVD_OK;
+  }
+  if (getenv("DVD_GEMM_PD4")) {       // lab: register prefetch four tiles deep (measured: no gain, see gemm_nt_kernel)
+    c.kernel = GemmKernel::plain;
+    c.variant = 4;
+    return DVD_OK;
+  }
+#endif
+  c.kernel = GemmKernel::plain;
+  c.variant = 2;
+  return DVD_OK;
+}
+
+// The demangled (rocprofv3) name of the instance dvd_gemm_nt launches for *d, "" for a descriptor it refuses.
+extern "C" const char* dvd_gemm_kernel_name(const dvd_gemm_desc* d) {
+  GemmChoice c;
+  if (gemm_select(d, c) != DVD_OK) return "";
+  static thread_local char name[64];
+  const char* tf[2] = {"false", "true"};
+  switch (c.kernel) {
+    case GemmKernel::split128: snprintf(name, sizeof(name), "gemm_nt_split128_kernel<%s>", tf[c.variant]); break;
+    case GemmKernel::split256: return "gemm_nt_split_kernel<true>";
+    case GemmKernel::t384:
+      snprintf(name, sizeof(name), "gemm_nt_t384_kernel<%d, %d, %s, %s>", c.dbg, c.fl, tf[c.full], tf[c.x16]);
+      break;
+    case GemmKernel::big: snprintf(name, sizeof(name), "gemm_nt_big_kernel<%d>", c.variant); break;
+    case GemmKernel::f32_narrow: snprintf(name, sizeof(name), "gemm_f32_narrow_kernel<%d>", c.variant); break;
+    case GemmKernel::ring256: return "gemm_nt_ring256_kernel";
+    case GemmKernel::ring128: return "gemm_nt_ring128_kernel";
+    case GemmKernel::plain:
+      snprintf(name, sizeof(name), "gemm_nt_kernel<%s, %d, false>", tf[d->dtype == 1], c.variant);
+      break;
+#ifdef DVD_LAB
+    case GemmKernel::lab_ring: return "gemm_nt_split_kernel<false>";
+    case GemmKernel::lab_big16: return "gemm_nt_big16_kernel";
+    case GemmKernel::lab_big2: return "gemm_nt_big2_kernel";
+    case GemmKernel::lab_w8: return "gemm_nt_w8_kernel";
+#endif
+    default: return "";
+  }
+  return name;
+}
+
+extern "C" int dvd_gemm_nt(const dvd_gemm_desc* d, void* stream) {
+  GemmChoice c;
+  if (const int rc = gemm_select(d, c); rc != DVD_OK) return rc;
+  GemmArgs p;
   p.Blo = d->B_lo; p.Alo = d->A_lo; p.lo_scale = d->lo_scale;
   p.A = d->A; p.B = d->B; p.C32 = d->C32; p.C16 = (_Float16*)d->C16;
   p.bias = d->bias; p.res = d->res; p.gate = d->gate; p.pos = d->pos;
@@ -2142,206 +2336,148 @@ extern "C" int dvd_gemm_nt(const dvd_gemm_desc* d, void* stream) {
   p.gate_rows = d->gate_rows; p.pos_rows = d->pos_rows;
   p.act = d->act; p.bias_row = d->bias_row;
   p.cv_b = nullptr; p.cv_ca = p.cv_cb = p.cv_h = p.cv_w = p.cv_ks = p.cv_dil = 0;
-
-  // The product library has no switches: the kernel is a function of the descriptor alone.  The lab build
-  // (-DDVD_LAB, benchmarks/lab/libdvd_hip_lab.so) keeps the A/B switches of the experiments that were measured.
+  p.vec_epilogue = c.vec_epilogue;
+  p.debug = c.debug;
 #ifdef DVD_LAB
-  { const char* dbg = getenv("DVD_GEMM_DEBUG"); p.debug = dbg ? atoi(dbg) : 0; }
   { const char* sg = getenv("DVD_GEMM_STAGGER"); p.stagger = sg ? atoi(sg) : 0; }   // measured: no effect
   p.stamps = g_gemm_stamps;
   p.walk = 0;
-  const bool lab_scalar_epi = getenv("DVD_GEMM_SCALAR_EPILOGUE"), lab_v1 = getenv("DVD_GEMM_V1"),
-             lab_twopass = getenv("DVD_GEMM_TWOPASS"), lab_nonpersistent = getenv("DVD_GEMM_NONPERSISTENT"),
-             lab_spread = getenv("DVD_GEMM_SPREAD"), lab_no_t384 = getenv("DVD_GEMM_NO_T384") || p.debug;
+  const bool lab_nonpersistent = getenv("DVD_GEMM_NONPERSISTENT");
 #else
-  p.debug = 0; p.stagger = 0; p.stamps = nullptr; p.walk = 0;
-  constexpr bool lab_scalar_epi = false, lab_v1 = false, lab_twopass = false, lab_nonpersistent = false, lab_no_t384 = false;
+  p.stagger = 0; p.stamps = nullptr; p.walk = 0;
+  constexpr bool lab_nonpersistent = false;
 #endif
-  {
-    auto al = [](const void* q, size_t a) { return ((uintptr_t)q % a) == 0; };
-    bool ok = d->N % 8 == 0 && !lab_scalar_epi;
-    if (d->C32) ok = ok && d->ldc % 4 == 0 && d->strideC32 % 4 == 0 && al(d->C32, 16);
-    if (d->C16) ok = ok && d->ldc16 % 8 == 0 && d->strideC16 % 8 == 0 && al(d->C16, 16);
-    if (d->bias && !d->bias_row) ok = ok && al(d->bias, 16) && d->strideBias % 4 == 0;
-    if (d->pos) ok = ok && d->ldpos % 4 == 0 && al(d->pos, 16);
-    if (d->gate) ok = ok && d->ldgate % 4 == 0 && d->strideGate % 4 == 0 && al(d->gate, 16);
-    if (d->res) ok = ok && d->ldres % 4 == 0 && d->strideRes % 4 == 0 && al(d->res, 16);
-    p.vec_epilogue = ok ? 1 : 0;
-  }
-  // large-tile kernel for the big f16 GEMMs (decoder): N a multiple of 256, at least a few row tiles
-  // A document must get the same bits whether it is sampled alone or in a batch.  Two ways this holds here: (a) within a
-  // problem family the kernel is chosen from (dtype, N, K, split) only, never from M - same kernel, same fp32 summation order;
-  // (b) where the choice DOES follow the row count (small_tiles 1 vs 2 below: the engine switches at 16 384 token rows; the
-  // 384 x 256 kernel of round 5 vs gemm_nt_big_kernel), the kernels on both sides accumulate every output in the same MFMA
-  // sequence and run the same epilogue arithmetic - bit-identical by construction, and tested as such (tests/test_gpu_gemm.py).
-  // small_tiles 1: the caller's problem family is small: 128x128 tiles everywhere.  small_tiles 2: the same family with MANY
-  // rows (a large batch of small grids): shapes with N % 256 == 0 take the 256x256 kernel in its TWO-SWEEP form - low parts
-  // first, scale, high parts, k ascending in 16-deep MFMA steps: exactly the 128x128 kernel's accumulation sequence, so a
-  // document still gets the same bits alone (small_tiles 1) and in a large batch (tests/test_gpu_gemm.py) - everything else
-  // stays on the 128x128 kernel.
-  const bool small = d->small_tiles == 1, small_many = d->small_tiles == 2;
-  const bool big = d->dtype == 0 && d->N % 256 == 0 && !lab_v1 && !small;
-  if (d->dtype == 0 && d->N % 128 == 0 && d->N % 256 != 0 && !d->A_lo && (!d->B_lo || d->lo_scale == 1.f) &&
-      d->K % 32 == 0 && !lab_twopass && !lab_v1 && !small && !small_many) {
-    // 256 x 128 tiles for the DiT block's 384-wide GEMMs: (hi, lo) in one pass, or ONE (dithered) weight tensor
-    p.ntm = cdiv(d->M, 256); p.ntn = d->N / 128;
-    constexpr int LDS = 8 * 16384;                    // 3 stages x 32 KiB, rounded up to the epilogue's 8 x 16 KiB
-    static DeviceOnce once_s1;
-    if (const auto bit = DeviceOnce::current_bit(); once_s1.need(bit)) {
-      (void)hipFuncSetAttribute((const void*)gemm_nt_split128_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-      (void)hipFuncSetAttribute((const void*)gemm_nt_split128_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-      once_s1.done(bit);
+  const hipStream_t st = (hipStream_t)stream;
+  switch (c.kernel) {
+    case GemmKernel::split128: {
+      p.ntm = cdiv(d->M, 256); p.ntn = d->N / 128;
+      constexpr int LDS = 8 * 16384;                    // 3 stages x 32 KiB, rounded up to the epilogue's 8 x 16 KiB
+      static DeviceOnce once_s1;
+      if (const auto bit = DeviceOnce::current_bit(); once_s1.need(bit)) {
+        (void)hipFuncSetAttribute((const void*)gemm_nt_split128_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
+        (void)hipFuncSetAttribute((const void*)gemm_nt_split128_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
+        once_s1.done(bit);
+      }
+      int nblk = p.ntm * p.ntn;
+      if (nblk > 256) nblk = 256;
+      if (c.variant) gemm_nt_split128_kernel<true><<<dim3(nblk, d->batch), 512, LDS, st>>>(p);
+      else gemm_nt_split128_kernel<false><<<dim3(nblk, d->batch), 512, LDS, st>>>(p);
+      return check_launch("gemm_nt(128-wide)");
     }
-    int nblk = p.ntm * p.ntn;
-    if (nblk > 256) nblk = 256;
-    if (d->B_lo) gemm_nt_split128_kernel<true><<<dim3(nblk, d->batch), 512, LDS, (hipStream_t)stream>>>(p);
-    else gemm_nt_split128_kernel<false><<<dim3(nblk, d->batch), 512, LDS, (hipStream_t)stream>>>(p);
-    return check_launch("gemm_nt(128-wide)");
-  }
-  if (big && d->B_lo && !d->A_lo && d->lo_scale == 1.f && d->K % 32 == 0 && !lab_twopass && !small_many) {
-    p.ntm = cdiv(d->M, 256); p.ntn = d->N / 256;
-    constexpr int LDS = 3 * 3 * 256 * 64;
-    static DeviceOnce once_s;
-    if (const auto bit = DeviceOnce::current_bit(); once_s.need(bit)) {
-      (void)hipFuncSetAttribute((const void*)gemm_nt_split_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-      once_s.done(bit);
+    case GemmKernel::split256: {
+      p.ntm = cdiv(d->M, 256); p.ntn = d->N / 256;
+      constexpr int LDS = 3 * 3 * 256 * 64;
+      static DeviceOnce once_s;
+      if (const auto bit = DeviceOnce::current_bit(); once_s.need(bit)) {
+        (void)hipFuncSetAttribute((const void*)gemm_nt_split_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
+        once_s.done(bit);
+      }
+      int nblk = p.ntm * p.ntn;
+      if (nblk > 256) nblk = 256;
+      gemm_nt_split_kernel<true><<<dim3(nblk, d->batch), 512, LDS, st>>>(p);
+      return check_launch("gemm_nt(split)");
     }
-    int nblk = p.ntm * p.ntn;
-    if (nblk > 256) nblk = 256;
-    gemm_nt_split_kernel<true><<<dim3(nblk, d->batch), 512, LDS, (hipStream_t)stream>>>(p);
-    return check_launch("gemm_nt(split)");
-  }
 #ifdef DVD_LAB
-  if (big && !d->B_lo && !d->A_lo && d->K % 32 == 0 && getenv("DVD_GEMM_RING")) {
-    // lab: the split kernel's 3-stage skewed pipeline on one weight tensor, for A/B runs against gemm_nt_big_kernel
-    p.ntm = cdiv(d->M, 256); p.ntn = d->N / 256;
-    constexpr int LDS = 3 * 3 * 256 * 64;
-    static DeviceOnce once_r;
-    if (const auto bit = DeviceOnce::current_bit(); once_r.need(bit)) {
-      (void)hipFuncSetAttribute((const void*)gemm_nt_split_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-      once_r.done(bit);
+    case GemmKernel::lab_ring: {
+      p.ntm = cdiv(d->M, 256); p.ntn = d->N / 256;
+      constexpr int LDS = 3 * 3 * 256 * 64;
+      static DeviceOnce once_r;
+      if (const auto bit = DeviceOnce::current_bit(); once_r.need(bit)) {
+        (void)hipFuncSetAttribute((const void*)gemm_nt_split_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
+        once_r.done(bit);
+      }
+      int nblk = p.ntm * p.ntn;
+      if (nblk > 256) nblk = 256;
+      gemm_nt_split_kernel<false><<<dim3(nblk, d->batch), 512, LDS, st>>>(p);
+      return check_launch("gemm_nt(ring, lab)");
     }
-    int nblk = p.ntm * p.ntn;
-    if (nblk > 256) nblk = 256;
-    gemm_nt_split_kernel<false><<<dim3(nblk, d->batch), 512, LDS, (hipStream_t)stream>>>(p);
-    return check_launch("gemm_nt(ring, lab)");
-  }
-#endif
-#ifdef DVD_LAB
-  if (big && !d->B_lo && !d->A_lo && p.vec_epilogue && !d->pos && !d->gate && getenv("DVD_GEMM_M16")) {
-    // lab: the 16x16x32-MFMA variant of the 256 x 256 kernel (measured 1-7 % slower, see gemm_nt_big16_kernel)
-    p.ntm = cdiv(d->M, 256); p.ntn = d->N / 256;
-    constexpr int LDS = 2 * 2 * 256 * 128;
-    static DeviceOnce once16;
-    if (const auto bit = DeviceOnce::current_bit(); once16.need(bit)) {
-      (void)hipFuncSetAttribute((const void*)gemm_nt_big16_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-      once16.done(bit);
+    case GemmKernel::lab_big16: {
+      p.ntm = cdiv(d->M, 256); p.ntn = d->N / 256;
+      constexpr int LDS = 2 * 2 * 256 * 128;
+      static DeviceOnce once16;
+      if (const auto bit = DeviceOnce::current_bit(); once16.need(bit)) {
+        (void)hipFuncSetAttribute((const void*)gemm_nt_big16_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
+        once16.done(bit);
+      }
+      int nblk = p.ntm * p.ntn;
+      if (nblk > 256) nblk = 256;
+      gemm_nt_big16_kernel<<<dim3(nblk, d->batch), 512, LDS, st>>>(p);
+      return check_launch("gemm_nt(big16)");
     }
-    int nblk = p.ntm * p.ntn;
-    if (nblk > 256) nblk = 256;
-    gemm_nt_big16_kernel<<<dim3(nblk, d->batch), 512, LDS, (hipStream_t)stream>>>(p);
-    return check_launch("gemm_nt(big16)");
-  }
-#endif
-#ifdef DVD_LAB
-  if (big && !d->B_lo && !d->A_lo && d->K % 32 == 0 && p.vec_epilogue && !d->pos && !d->gate && !(d->bias && d->bias_row) &&
-      getenv("DVD_GEMM_BIG2")) {
-    p.ntm = cdiv(d->M, 256); p.ntn = d->N / 256;
-    constexpr int LDS = big2::NBUF * big2::HALF;
-    static DeviceOnce once2;
-    if (const auto bit = DeviceOnce::current_bit(); once2.need(bit)) {
-      (void)hipFuncSetAttribute((const void*)gemm_nt_big2_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-      once2.done(bit);
+    case GemmKernel::lab_big2: {
+      p.ntm = cdiv(d->M, 256); p.ntn = d->N / 256;
+      constexpr int LDS = big2::NBUF * big2::HALF;
+      static DeviceOnce once2;
+      if (const auto bit = DeviceOnce::current_bit(); once2.need(bit)) {
+        (void)hipFuncSetAttribute((const void*)gemm_nt_big2_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
+        once2.done(bit);
+      }
+      int nblk = p.ntm * p.ntn;
+      if (nblk > 256) nblk = 256;
+      gemm_nt_big2_kernel<<<dim3(nblk, d->batch), 256, LDS, st>>>(p);
+      return check_launch("gemm_nt(big2)");
     }
-    int nblk = p.ntm * p.ntn;
-    if (nblk > 256) nblk = 256;
-    gemm_nt_big2_kernel<<<dim3(nblk, d->batch), 256, LDS, (hipStream_t)stream>>>(p);
-    return check_launch("gemm_nt(big2)");
-  }
 #endif
-  if (big && !d->B_lo && !d->A_lo && !small_many && p.vec_epilogue && !d->pos && !d->gate && !(d->bias && d->bias_row) &&
-      !(d->res && d->act == 1) && d->K % 128 == 0 && d->K >= 256 && !lab_no_t384) {
-    // round 5: 384 x 256 tiles, 4-slot half-slab ring, generated K loop; bit-identical to gemm_nt_big_kernel
-    p.ntm = cdiv(d->M, 384); p.ntn = d->N / 256;
-    int tdbg = 0;
-    p.stagger = T384_STAGGER;
-    p.walk = T384_WALK;
+    case GemmKernel::t384: {
+      p.ntm = cdiv(d->M, 384); p.ntn = d->N / 256;
+      p.stagger = T384_STAGGER;
+      p.walk = T384_WALK;
 #ifdef DVD_LAB
-    if (const char* e = getenv("DVD_GEMM_T384_DBG")) tdbg = atoi(e);
-    if (const char* e = getenv("DVD_GEMM_T384_STAGGER")) p.stagger = atoi(e);
-    if (getenv("DVD_GEMM_T384_PRIO")) p.debug |= 0x100;
-    if (const char* e = getenv("DVD_GEMM_T384_WALK")) p.walk = atoi(e);
-    if (getenv("DVD_GEMM_T384_NT")) p.debug |= 0x200;
-    if (getenv("DVD_GEMM_T384_RES_PHASED")) p.debug |= 0x400;
-    if (getenv("DVD_GEMM_T384_NOSTORE")) p.debug |= 0x800;
+      if (const char* e = getenv("DVD_GEMM_T384_STAGGER")) p.stagger = atoi(e);
+      if (getenv("DVD_GEMM_T384_PRIO")) p.debug |= 0x100;
+      if (const char* e = getenv("DVD_GEMM_T384_WALK")) p.walk = atoi(e);
+      if (getenv("DVD_GEMM_T384_NT")) p.debug |= 0x200;
+      if (getenv("DVD_GEMM_T384_RES_PHASED")) p.debug |= 0x400;
+      if (getenv("DVD_GEMM_T384_NOSTORE")) p.debug |= 0x800;
 #endif
-    return launch_gemm_t384(p, d->batch, tdbg, stream);
-  }
-  if (big) {
-    p.ntm = cdiv(d->M, 256); p.ntn = d->N / 256;
-    constexpr int LDS = 2 * 2 * 256 * 128;
-    static DeviceOnce once;
-    if (const auto bit = DeviceOnce::current_bit(); once.need(bit)) {
-      (void)hipFuncSetAttribute((const void*)gemm_nt_big_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-#ifdef DVD_LAB
-      (void)hipFuncSetAttribute((const void*)gemm_nt_big_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-      (void)hipFuncSetAttribute((const void*)gemm_nt_big_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-      (void)hipFuncSetAttribute((const void*)gemm_nt_big_kernel<3>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-      (void)hipFuncSetAttribute((const void*)gemm_nt_big_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-      (void)hipFuncSetAttribute((const void*)gemm_nt_big_kernel<5>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-      (void)hipFuncSetAttribute((const void*)gemm_nt_big_kernel<6>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-      (void)hipFuncSetAttribute((const void*)gemm_nt_big_kernel<7>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-#endif
-      once.done(bit);
+      return launch_gemm_t384(p, d->batch, c.dbg, c.fl, c.full, c.x16, stream);
     }
-    int nblk = p.ntm * p.ntn;
-    if (nblk > 256 && !lab_nonpersistent) nblk = 256;
-    dim3 gridb(nblk, d->batch);
+    case GemmKernel::big: {
+      p.ntm = cdiv(d->M, 256); p.ntn = d->N / 256;
+      constexpr int LDS = 2 * 2 * 256 * 128;
+      static DeviceOnce once;
+      if (const auto bit = DeviceOnce::current_bit(); once.need(bit)) {
+        (void)hipFuncSetAttribute((const void*)gemm_nt_big_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
 #ifdef DVD_LAB
-    if (p.debug == 1) gemm_nt_big_kernel<1><<<gridb, 512, LDS, (hipStream_t)stream>>>(p);
-    else if (p.debug == 2) gemm_nt_big_kernel<2><<<gridb, 512, LDS, (hipStream_t)stream>>>(p);
-    else if (p.debug == 3) gemm_nt_big_kernel<3><<<gridb, 512, LDS, (hipStream_t)stream>>>(p);
-    else if (p.debug == 5) gemm_nt_big_kernel<5><<<gridb, 512, LDS, (hipStream_t)stream>>>(p);
-    else if (p.debug == 6) gemm_nt_big_kernel<6><<<gridb, 512, LDS, (hipStream_t)stream>>>(p);
-    else if (p.debug == 7) gemm_nt_big_kernel<7><<<gridb, 512, LDS, (hipStream_t)stream>>>(p);
-    else if (lab_spread) gemm_nt_big_kernel<4><<<gridb, 512, LDS, (hipStream_t)stream>>>(p);
-    else
+        (void)hipFuncSetAttribute((const void*)gemm_nt_big_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
+        (void)hipFuncSetAttribute((const void*)gemm_nt_big_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
+        (void)hipFuncSetAttribute((const void*)gemm_nt_big_kernel<3>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
+        (void)hipFuncSetAttribute((const void*)gemm_nt_big_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
+        (void)hipFuncSetAttribute((const void*)gemm_nt_big_kernel<5>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
+        (void)hipFuncSetAttribute((const void*)gemm_nt_big_kernel<6>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
+        (void)hipFuncSetAttribute((const void*)gemm_nt_big_kernel<7>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
 #endif
-    gemm_nt_big_kernel<0><<<gridb, 512, LDS, (hipStream_t)stream>>>(p);
-    return check_launch("gemm_nt(big)");
+        once.done(bit);
+      }
+      int nblk = p.ntm * p.ntn;
+      if (nblk > 256 && !lab_nonpersistent) nblk = 256;
+      dim3 gridb(nblk, d->batch);
+#ifdef DVD_LAB
+      if (c.variant == 1) gemm_nt_big_kernel<1><<<gridb, 512, LDS, st>>>(p);
+      else if (c.variant == 2) gemm_nt_big_kernel<2><<<gridb, 512, LDS, st>>>(p);
+      else if (c.variant == 3) gemm_nt_big_kernel<3><<<gridb, 512, LDS, st>>>(p);
+      else if (c.variant == 5) gemm_nt_big_kernel<5><<<gridb, 512, LDS, st>>>(p);
+      else if (c.variant == 6) gemm_nt_big_kernel<6><<<gridb, 512, LDS, st>>>(p);
+      else if (c.variant == 7) gemm_nt_big_kernel<7><<<gridb, 512, LDS, st>>>(p);
+      else if (c.variant == 4) gemm_nt_big_kernel<4><<<gridb, 512, LDS, st>>>(p);
+      else
+#endif
+      gemm_nt_big_kernel<0><<<gridb, 512, LDS, st>>>(p);
+      return check_launch("gemm_nt(big)");
+    }
+    case GemmKernel::f32_narrow: {
+      const dim3 grd(cdiv(d->M, 128), d->batch);
+      if (c.variant == 1) gemm_f32_narrow_kernel<1><<<grd, 256, 0, st>>>(p);
+      else gemm_f32_narrow_kernel<2><<<grd, 256, 0, st>>>(p);
+      return check_launch("gemm_nt(f32 narrow)");
+    }
+    default: break;
   }
-  if (d->dtype == 1 && d->N <= 64 && d->C32 && !d->C16 && !d->pos && !d->gate && !d->res && !d->bias_row &&
-      (d->act == 0 || d->act == 2) && !d->A_lo && !d->B_lo) {
-    const dim3 grd(cdiv(d->M, 128), d->batch);
-    if (d->N <= 32) gemm_f32_narrow_kernel<1><<<grd, 256, 0, (hipStream_t)stream>>>(p);
-    else gemm_f32_narrow_kernel<2><<<grd, 256, 0, (hipStream_t)stream>>>(p);
-    return check_launch("gemm_nt(f32 narrow)");
-  }
+  // the 128 x 128-tile family
   p.ntm = cdiv(d->M, 128); p.ntn = cdiv(d->N, 128);
   dim3 grid(p.ntm * p.ntn, d->batch);
-  {
-    // f16 problems with few 128 x 128 tiles: the LDS-DMA ring kernel (same bits; see gemm_nt_ring128_kernel)
-    auto al16 = [](const void* q) { return ((uintptr_t)q % 16) == 0; };
-    bool ring = d->dtype != 1 && d->K % 64 == 0 && d->K >= 128 && d->lda % 8 == 0 && d->ldb % 8 == 0 && d->strideA % 8 == 0 &&
-                d->strideB % 8 == 0 && al16(d->A) && al16(d->B) && al16(d->A_lo) && al16(d->B_lo) &&
-                (long)p.ntm * p.ntn <= RING128_MAX_TILES && (long)d->M * d->lda < (1l << 30) && (long)d->N * d->ldb < (1l << 30);
-#ifdef DVD_LAB
-    if (const char* e = getenv("DVD_GEMM_RING128")) ring = ring && atoi(e) != 0;
-#endif
-    bool ring256 = d->dtype != 1 && d->N % 256 == 0 && d->K % 32 == 0 && d->K >= 128 && d->lda % 8 == 0 && d->ldb % 8 == 0 &&
-                   d->strideA % 8 == 0 && d->strideB % 8 == 0 && al16(d->A) && al16(d->B) && al16(d->A_lo) && al16(d->B_lo) &&
-                   (long)p.ntm * (d->N / 256) <= RING256_MAX_TILES && (long)p.ntm * (d->N / 256) >= RING256_MIN_TILES &&
-                   (long)d->M * d->lda < (1l << 30) &&
-                   (long)d->N * d->ldb < (1l << 30);
-#ifdef DVD_LAB
-    if (const char* e = getenv("DVD_GEMM_RING256")) {       // 0: off; 2: also below RING256_MIN_TILES (tests, A/B runs)
-      if (atoi(e) == 0) ring256 = false;
-      if (atoi(e) == 2) ring256 = d->dtype != 1 && d->N % 256 == 0 && d->K >= 128 && d->lda % 8 == 0 && d->ldb % 8 == 0 && d->strideA % 8 == 0 &&
-                                  d->strideB % 8 == 0 && al16(d->A) && al16(d->B) && al16(d->A_lo) && al16(d->B_lo) &&
-                                  (long)p.ntm * (d->N / 256) <= RING256_MAX_TILES;
-    }
-#endif
-    if (ring256) {
+  switch (c.kernel) {
+    case GemmKernel::ring256: {
       constexpr int LDS = 6 * (128 + 256) * 64;
       static DeviceOnce once_r256;
       if (const auto bit = DeviceOnce::current_bit(); once_r256.need(bit)) {
@@ -2349,35 +2485,37 @@ extern "C" int dvd_gemm_nt(const dvd_gemm_desc* d, void* stream) {
         once_r256.done(bit);
       }
       p.ntn = d->N / 256;
-      gemm_nt_ring256_kernel<<<dim3(p.ntm * p.ntn, d->batch), 512, LDS, (hipStream_t)stream>>>(p);
+      gemm_nt_ring256_kernel<<<dim3(p.ntm * p.ntn, d->batch), 512, LDS, st>>>(p);
       return check_launch("gemm_nt(ring256)");
     }
-    if (ring) {
+    case GemmKernel::ring128: {
       constexpr int LDS = 5 * 2 * 128 * 128;
       static DeviceOnce once_r128;
       if (const auto bit = DeviceOnce::current_bit(); once_r128.need(bit)) {
         (void)hipFuncSetAttribute((const void*)gemm_nt_ring128_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
         once_r128.done(bit);
       }
-      gemm_nt_ring128_kernel<<<grid, 256, LDS, (hipStream_t)stream>>>(p);
+      gemm_nt_ring128_kernel<<<grid, 256, LDS, st>>>(p);
       return check_launch("gemm_nt(ring128)");
     }
-  }
 #ifdef DVD_LAB
-  if (const char* e = getenv("DVD_GEMM_W8"); e && atoi(e) != 0 && d->dtype != 1) {   // lab: two waves per SIMD on each tile
-    gemm_nt_w8_kernel<<<grid, 512, 0, (hipStream_t)stream>>>(p);
-    return check_launch("gemm_nt(w8, lab)");
-  }
-  if (getenv("DVD_GEMM_PD4")) {       // lab: register prefetch four tiles deep (measured: no gain, see gemm_nt_kernel)
-    if (d->dtype == 1) gemm_nt_kernel<true, 4><<<grid, 256, 0, (hipStream_t)stream>>>(p);
-    else gemm_nt_kernel<false, 4><<<grid, 256, 0, (hipStream_t)stream>>>(p);
-    return check_launch("gemm_nt(pd4, lab)");
-  }
+    case GemmKernel::lab_w8:
+      gemm_nt_w8_kernel<<<grid, 512, 0, st>>>(p);
+      return check_launch("gemm_nt(w8, lab)");
+    case GemmKernel::plain:
+      if (c.variant == 4) {
+        if (d->dtype == 1) gemm_nt_kernel<true, 4><<<grid, 256, 0, st>>>(p);
+        else gemm_nt_kernel<false, 4><<<grid, 256, 0, st>>>(p);
+        return check_launch("gemm_nt(pd4, lab)");
+      }
+      break;
 #endif
+    default: break;
+  }
   if (d->dtype == 1)
-    gemm_nt_kernel<true, 2><<<grid, 256, 0, (hipStream_t)stream>>>(p);
+    gemm_nt_kernel<true, 2><<<grid, 256, 0, st>>>(p);
   else
-    gemm_nt_kernel<false, 2><<<grid, 256, 0, (hipStream_t)stream>>>(p);
+    gemm_nt_kernel<false, 2><<<grid, 256, 0, st>>>(p);
   return check_launch("gemm_nt");
 }
 

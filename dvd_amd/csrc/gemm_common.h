@@ -4,6 +4,12 @@
 #include "common.h"
 #include "mfma.h"
 
+// T384_X16: the K loop of gemm_nt_t384_kernel.  1 = v_mfma_f32_16x16x32_f16 (round 6), 0 = round 5's 32x32x16 loop (bit-identical
+// to gemm_nt_big_kernel; the lab build selects it with DVD_GEMM_T384_M32=1).
+#ifndef T384_X16
+#define T384_X16 1
+#endif
+
 namespace dvd {
 
 struct GemmArgs {
@@ -108,7 +114,8 @@ __device__ __forceinline__ float gelu_tanh(float x) {
   return x < -10.5f ? -0.f : y;
 }
 
-// gemm_t384.hip: the 384 x 256 kernel (lab builds: dbg selects a timing ablation / the stamp build)
-int launch_gemm_t384(const GemmArgs& p, int batch, int dbg, void* stream);
+// gemm_t384.hip: the 384 x 256 kernel, instance gemm_nt_t384_kernel<dbg, fl, full, x16> (lab builds: dbg selects a timing
+// ablation / the stamp build, x16 the K loop; the product build has dbg 0 and x16 = T384_X16)
+int launch_gemm_t384(const GemmArgs& p, int batch, int dbg, int fl, bool full, bool x16, void* stream);
 
 }  // namespace dvd

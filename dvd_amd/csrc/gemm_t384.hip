@@ -736,12 +736,8 @@ static void allow_lds() {
 #undef T384_AL
 }
 
-// T384_X16: the product's K loop.  1 = v_mfma_f32_16x16x32_f16 (round 6), 0 = round 5's 32x32x16 loop (bit-identical to
-// gemm_nt_big_kernel).  The lab build carries both (DVD_GEMM_T384_M32=1 selects the old one) and the timing ablations of the old one.
-#ifndef T384_X16
-#define T384_X16 1
-#endif
-int launch_gemm_t384(const GemmArgs& p, int batch, int dbg, void* stream) {
+// T384_X16 (gemm_common.h): the product's K loop.  The lab build carries both loops and the timing ablations of the old one.
+int launch_gemm_t384(const GemmArgs& p, int batch, int dbg, int fl, bool full, bool x16, void* stream) {
   static DeviceOnce once_t;
   if (const auto bit = DeviceOnce::current_bit(); once_t.need(bit)) {
     allow_lds<0, T384_X16 != 0>();
@@ -759,12 +755,9 @@ int launch_gemm_t384(const GemmArgs& p, int batch, int dbg, void* stream) {
 #endif
   const dim3 grid(nblk, batch);
   hipStream_t st = (hipStream_t)stream;
-  // the epilogue flavour is a function of the descriptor (never of the data): see gemm_nt_t384_kernel
-  const int fl = (p.C16 && !p.C32 && !p.res) ? 0 : (p.C32 && !p.C16 && p.act != 1) ? (p.res ? 2 : 1) : (p.res ? 4 : 3);
-  const bool full = p.M % 384 == 0;
+  // (dbg, fl, full, x16): the instance gemm_select (gemm.hip) chose
 #ifdef DVD_LAB
-  const bool use_x16 = getenv("DVD_GEMM_T384_M32") ? false : (getenv("DVD_GEMM_T384_X16") ? true : (T384_X16 != 0));
-  if (use_x16) {
+  if (x16) {
     if (dbg == 5) launch_fl<5, true>(p, fl, full, grid, st);
     else launch_fl<0, true>(p, fl, full, grid, st);
     return check_launch("gemm_nt(t384 x16)");
@@ -779,7 +772,7 @@ int launch_gemm_t384(const GemmArgs& p, int batch, int dbg, void* stream) {
     default: launch_fl<0, false>(p, fl, full, grid, st);
   }
 #else
-  (void)dbg;
+  (void)dbg; (void)x16;
   launch_fl<0, T384_X16 != 0>(p, fl, full, grid, st);
 #endif
   return check_launch("gemm_nt(t384)");

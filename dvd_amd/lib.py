@@ -76,7 +76,7 @@ class CnOp(C.Structure):
 
 
 NON_STATUS = {"dvd_last_error", "dvd_version", "dvd_engine_workspace_bytes", "dvd_engine_tensor_count",
-              "dvd_flash_attn_kernel_name", "dvd_convnet_workspace_bytes", "dvd_convnet_weight_floats",
+              "dvd_flash_attn_kernel_name", "dvd_gemm_kernel_name", "dvd_convnet_workspace_bytes", "dvd_convnet_weight_floats",
               "dvd_ingest_scratch_bytes"}
 
 # name -> argtypes; kept in one table so tests can check every symbol of include/dvd_hip.h
@@ -92,6 +92,7 @@ SIGNATURES = {
     "dvd_hyp_mean_clamp": [c_void, c_void, C.c_int, C.c_int, C.c_int, c_void],
     "dvd_selftest_mfma": [c_void, c_void, c_void, c_void, c_void],
     "dvd_gemm_nt": [C.POINTER(GemmDesc), c_void],
+    "dvd_gemm_kernel_name": [C.POINTER(GemmDesc)],
     "dvd_flash_attn": [C.POINTER(AttnDesc), c_void],
     "dvd_embed_obs_ln": [c_void, c_void, c_void, c_void, c_void, c_void, C.c_int, C.c_int, c_void],
     "dvd_layernorm_rows": [c_void, C.c_int, C.c_long, c_void, C.c_int, C.c_long, C.c_int, C.c_long, C.c_int, c_void,
@@ -138,6 +139,9 @@ SIGNATURES = {
 }
 
 
+# entries of SIGNATURES that return something other than a status
+RESTYPES = {"dvd_gemm_kernel_name": C.c_char_p}
+
 # entry points that exist only in the lab build (benchmarks/lab/dvd_hip_lab.h; loaded through use_library)
 LAB_SIGNATURES = {"dvd_gemm_debug_stamps": [c_void], "dvd_attn_debug_stamps": [c_void]}
 
@@ -155,7 +159,7 @@ def bind(cdll):
     cdll.dvd_flash_attn_kernel_name.argtypes = [C.c_int, C.c_int, C.c_int]
     for name, args in SIGNATURES.items():
         fn = getattr(cdll, name)
-        fn.argtypes, fn.restype = args, C.c_int
+        fn.argtypes, fn.restype = args, RESTYPES.get(name, C.c_int)
     for name, args in LAB_SIGNATURES.items():
         if hasattr(cdll, name):
             fn = getattr(cdll, name)
@@ -183,6 +187,11 @@ def call(name: str, *args):
 
 def flash_attn_kernel_name(head_dim: int, tq: int, tk: int) -> str:
     return _lib.dvd_flash_attn_kernel_name(head_dim, tq, tk).decode()
+
+
+def gemm_kernel_name(desc: GemmDesc) -> str:
+    """The kernel instance dvd_gemm_nt launches for `desc` ("" if it refuses it); host-only."""
+    return _lib.dvd_gemm_kernel_name(C.byref(desc)).decode()
 
 
 def version() -> int:

@@ -139,6 +139,11 @@ typedef struct {
 } dvd_gemm_desc;
 
 int dvd_gemm_nt(const dvd_gemm_desc* desc, void* stream);
+/* Name of the kernel instance dvd_gemm_nt launches for a descriptor, demangled as rocprofv3 prints it (e.g.
+ * "gemm_nt_t384_kernel<0, 2, true, true>", "gemm_nt_split128_kernel<true>", "gemm_nt_ring256_kernel"); "" for a descriptor
+ * dvd_gemm_nt refuses.  Host-only: no device call, so pointers may be any values of the alignment the caller means to test.
+ * The returned string stays valid until the calling thread's next call. */
+const char* dvd_gemm_kernel_name(const dvd_gemm_desc* desc);
 
 /* ------------------------------------------------------------------------------------------
  * Flash attention core  O = softmax(scale * Q K^T) V  per (batch, head); f16 in/out, fp32 softmax.
