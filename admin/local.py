@@ -60,6 +60,9 @@ _DEFAULTS = {
     "use_prestage_nets": True,
     # None = only when eval_dataset_name == 'synthetic' (a missing checkpoint on a real dataset raises)
     "synthetic_weights_if_missing": None,
+    # GeoTr checkpoint (DocTr's geometry transformer, keys 'module.<...>') read when use_init_flow is True: the reference's
+    # reload_model(pretrained_dewarp_model.GeoTr, settings.env.dewarping_model_path) (train_TDiff.py:89)
+    "dewarping_model_path": "",
 }
 
 

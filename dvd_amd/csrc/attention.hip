@@ -1879,6 +1879,7 @@ extern "C" int dvd_attn_debug_stamps(void* dev_u64) { g_attn_stamps = (unsigned 
 static constexpr int R64_MIN_TQ = 5376;
 
 extern "C" const char* dvd_flash_attn_kernel_name(int head_dim, int tq, int tk) {
+  if (head_dim == 32) return "flash_attn_f32_hd32_kernel";     // f32 operands: dvd_flash_attn_f32 (geotr.hip)
   if (head_dim != 64 && head_dim != 256) return "";
   if (tk % 64 != 0) return head_dim == 256 ? "flash_attn_kernel<256>" : "flash_attn_kernel<64>";
   if (head_dim == 256) return tq >= R64_MIN_TQ ? "flash_attn_r64x_kernel<0>" : "flash_attn_glds_kernel<256, 0>";

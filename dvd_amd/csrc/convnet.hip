@@ -9,7 +9,9 @@
 //         weights on the host, bias, optional ReLU) = one gather kernel (im2col with the concat and the
 //         dilation folded in) + the library's exact-f32 MFMA GEMM (v_mfma_f32_32x32x2_f32: fp32 products,
 //         fp32 accumulate - the conditioning reused by every denoising step carries no low-precision error);
-//   max-pool 2x2 / stride 2 (ceil_mode), bilinear resize (align_corners on or off), add, sigmoid.
+//   max-pool 2x2 / stride 2 (ceil_mode), bilinear resize (align_corners on or off), add (optionally relu(a + b)),
+//   sigmoid, and for GeoTr's BasicEncoder (extractor.py:4-117) stride-2 convs (7x7 pad 3, 3x3 pad 1, 1x1) on the gather
+//   path and InstanceNorm (+ReLU).
 // Activations are channels-last f32 ([H*W, C] row-major = the GEMM's C matrix, so a conv writes its output
 // with no transpose).  Everything only enqueues on the caller's stream; nothing allocates or synchronises.
 #include <string.h>
@@ -60,20 +62,22 @@ __global__ void __launch_bounds__(256) nchw_to_nhwc_kernel(const float* __restri
   out[i] = in[(b * c + ch) * hw + q];
 }
 
-// col[p, tap * (ca + cb) + ch] = src(ch)[y + (ky - r) * dil, x + (kx - r) * dil] (zero outside); columns >= ks*ks*(ca+cb)
-// are zero.  One thread per (pixel, 4 consecutive K entries): channels-last sources make the reads contiguous.
+// col[p, tap * (ca + cb) + ch] = src(ch)[y * s + (ky - r) * dil, x * s + (kx - r) * dil] (zero outside) for output pixel
+// (y, x) of the [ho, wo] map; columns >= ks*ks*(ca+cb) are zero.  One thread per (pixel, 4 consecutive K entries):
+// channels-last sources make the reads contiguous.  Stride 1: ho, wo = h, w.
 __global__ void __launch_bounds__(256) im2col_cat_kernel(const float* __restrict__ a, int ca, const float* __restrict__ b,
                                                          int cb, float* __restrict__ col, int kp, int ks, int dil,
-                                                         int h, int w, long total4) {
+                                                         int h, int w, int stride, int ho, int wo, long total4) {
   const long i = (long)blockIdx.x * 256 + threadIdx.x;
   if (i >= total4) return;
   const int kq = kp / 4;
   const long p = i / kq;
   const int k0 = (int)(i - p * kq) * 4;
-  const long hw = (long)h * w;
-  const long img0 = (p / hw) * hw;                       // first row of this pixel's image
-  const long pl = p - img0;
-  const int y = (int)(pl / w), x = (int)(pl - (long)y * w);
+  const long hwo = (long)ho * wo;
+  const long img = p / hwo;
+  const long img0 = img * h * w;                         // first row of this pixel's image in the source
+  const long pl = p - img * hwo;
+  const int y = (int)(pl / wo) * stride, x = (int)(pl - (pl / wo) * wo) * stride;
   const int cc = ca + cb, kreal = ks * ks * cc, r = ks / 2;
   float v[4];
 #pragma unroll
@@ -305,9 +309,56 @@ __global__ void __launch_bounds__(256) resize_planar_kernel(const float* __restr
 }
 
 __global__ void __launch_bounds__(256) add_kernel(const float* __restrict__ a, const float* __restrict__ b,
-                                                  float* __restrict__ out, long n) {
+                                                  float* __restrict__ out, long n, int act) {
   const long i = (long)blockIdx.x * 256 + threadIdx.x;
-  if (i < n) out[i] = a[i] + b[i];
+  if (i >= n) return;
+  const float v = a[i] + b[i];
+  out[i] = act == 2 ? fmaxf(v, 0.f) : v;
+}
+
+// nn.InstanceNorm2d (no affine, biased variance) on channels-last [B * hw, c], then ReLU when act == 2.  One workgroup per
+// (image, 64 channels): lane group g of 16 walks pixels g, g + 16, ...; the 16 partial sums are added in group order (the
+// same for every image and batch); mean first, then the centred second moment, then the normalised write.
+__global__ void __launch_bounds__(1024) instnorm_kernel(const float* __restrict__ in, float* __restrict__ out, int c, long hw,
+                                                        int act, float eps) {
+  __shared__ float part[16][64];
+  __shared__ float stat[2][64];
+  const int cl = threadIdx.x & 63, g = threadIdx.x >> 6;
+  const int ch = blockIdx.y * 64 + cl;
+  const bool ok = ch < c;
+  const float* src = in + (long)blockIdx.x * hw * c + (ok ? ch : 0);
+  float* dst = out + (long)blockIdx.x * hw * c + ch;
+  float s = 0.f;
+  for (long p = g; p < hw; p += 16) s += src[p * c];
+  part[g][cl] = s;
+  __syncthreads();
+  if (g == 0) {
+    float t = 0.f;
+    for (int k = 0; k < 16; ++k) t += part[k][cl];
+    stat[0][cl] = t / (float)hw;
+  }
+  __syncthreads();
+  const float mean = stat[0][cl];
+  s = 0.f;
+  for (long p = g; p < hw; p += 16) {
+    const float d = src[p * c] - mean;
+    s += d * d;
+  }
+  __syncthreads();
+  part[g][cl] = s;
+  __syncthreads();
+  if (g == 0) {
+    float t = 0.f;
+    for (int k = 0; k < 16; ++k) t += part[k][cl];
+    stat[1][cl] = 1.f / sqrtf(t / (float)hw + eps);
+  }
+  __syncthreads();
+  const float rstd = stat[1][cl];
+  if (!ok) return;
+  for (long p = g; p < hw; p += 16) {
+    const float v = (src[p * c] - mean) * rstd;
+    dst[p * c] = act == 2 ? fmaxf(v, 0.f) : v;
+  }
 }
 
 __global__ void __launch_bounds__(256) sigmoid_kernel(const float* __restrict__ a, float* __restrict__ out, long n) {
@@ -387,7 +438,9 @@ extern "C" int dvd_convnet_create_batched(const dvd_cn_op* ops, int n_ops, int n
     d.set = true;
     switch (o.op) {
       case DVD_CN_CONV: {
-        if ((o.ks != 1 && o.ks != 3) || o.dil < 1 || o.cout < 1) return fail("bad conv parameters", i);
+        if ((o.ks != 1 && o.ks != 3 && o.ks != 7) || o.dil < 1 || o.cout < 1) return fail("bad conv parameters", i);
+        if (o.flag < 0 || o.flag > 2 || (o.flag == 2 && o.b >= 0)) return fail("bad conv stride (1 or 2, single source)", i);
+        const int stride = o.flag == 2 ? 2 : 1;
         int cin = a.c;
         if (o.b >= 0) {
           const CnSlot& b = n->slots[o.b];
@@ -399,7 +452,13 @@ extern "C" int dvd_convnet_create_batched(const dvd_cn_op* ops, int n_ops, int n
         if (o.w_off != wf) return fail("weights must be packed in op order (w_off mismatch)", i);
         wf += (long)o.cout * kp + (o.cout + 3) / 4 * 4;   // bias padded to 16 bytes: every conv's weights stay 16-byte aligned
         d.h = a.h; d.w = a.w; d.c = o.cout;
-        {
+        if (stride == 2) {
+          // nn.Conv2d(stride=2, padding=dil * (ks / 2)): always the gather + exact-f32 GEMM path, on the output's rows
+          const int pad = o.dil * (o.ks / 2), span = o.dil * (o.ks - 1);
+          d.h = (a.h + 2 * pad - span - 1) / 2 + 1; d.w = (a.w + 2 * pad - span - 1) / 2 + 1;
+          if (d.h < 1 || d.w < 1) return fail("strided conv of a too small map", i);
+          colmax = std::max(colmax, nb * d.h * d.w * kp * 4);
+        } else {
           // Small maps with wide channels (the UNet's deep layers: 324 ... 1296 pixels, K up to 9216) give the 128 x 128
           // tile kernel a handful of workgroups and a K loop of hundreds of barrier-separated steps.  Such a conv is cut
           // into S slices of K, run as ONE batched GEMM launch (batch stride = K / S along both operands) into S partial
@@ -440,6 +499,9 @@ extern "C" int dvd_convnet_create_batched(const dvd_cn_op* ops, int n_ops, int n
         break;
       }
       case DVD_CN_SIGMOID:
+        d.h = a.h; d.w = a.w; d.c = a.c;
+        break;
+      case DVD_CN_INSTNORM:
         d.h = a.h; d.w = a.w; d.c = a.c;
         break;
       default:
@@ -519,6 +581,21 @@ extern "C" int dvd_convnet_run(void* handle, const float* in_nchw, const float* 
       case DVD_CN_CONV: {
         const int kp = n->kpad[i];
         const int cb = o.b >= 0 ? n->slots[o.b].c : 0;
+        if (o.flag == 2) {                  // stride 2: gather the output pixels' windows, then the exact-f32 GEMM
+          const long orows = B * d.h * d.w, total4 = orows * (kp / 4);
+          im2col_cat_kernel<<<cdiv(total4, 256), 256, 0, st>>>(P(o.a), a.c, nullptr, 0, col, kp, o.ks, o.dil, a.h, a.w, 2,
+                                                              d.h, d.w, total4);
+          dvd_gemm_desc g;
+          memset(&g, 0, sizeof(g));
+          DVD_REQUIRE(orows < (1l << 31), "convnet_run: batch too large for one GEMM");
+          g.dtype = 1; g.M = (int)orows; g.N = o.cout; g.K = kp; g.batch = 1;
+          g.A = col; g.lda = kp; g.B = weights + o.w_off; g.ldb = kp;
+          g.C32 = P(o.dst); g.ldc = o.cout;
+          g.bias = weights + o.w_off + (long)o.cout * kp; g.act = o.act;
+          g.lo_scale = 1.f;
+          if (int e = dvd_gemm_nt(&g, stream)) return e;
+          break;
+        }
         if (o.cout <= 64 && a.c % 8 == 0 && cb % 8 == 0 && (a.c + cb) % 16 == 0 && n->ksplit[i] == 1) {
           // narrow output over 16-aligned channels: implicit GEMM, no im2col matrix
           const dim3 grd(cdiv(rows, 128));
@@ -550,7 +627,7 @@ extern "C" int dvd_convnet_run(void* handle, const float* in_nchw, const float* 
         if (!(o.ks == 1 && o.b < 0 && a.c == kp)) {   // a 1x1 conv over a 16-aligned single source reads the slot directly
           const long total4 = rows * (kp / 4);
           im2col_cat_kernel<<<cdiv(total4, 256), 256, 0, st>>>(P(o.a), a.c, o.b >= 0 ? P(o.b) : nullptr, cb, col, kp,
-                                                              o.ks, o.dil, a.h, a.w, total4);
+                                                              o.ks, o.dil, a.h, a.w, 1, a.h, a.w, total4);
           A = col; lda = kp;
         }
         dvd_gemm_desc g;
@@ -582,10 +659,14 @@ extern "C" int dvd_convnet_run(void* handle, const float* in_nchw, const float* 
         resize_nhwc_kernel<<<cdiv(nd, 256), 256, 0, st>>>(P(o.a), P(o.dst), a.c, a.h, a.w, d.h, d.w, o.flag, nd);
         break;
       case DVD_CN_ADD:
-        add_kernel<<<cdiv(nd, 256), 256, 0, st>>>(P(o.a), P(o.b), P(o.dst), nd);
+        add_kernel<<<cdiv(nd, 256), 256, 0, st>>>(P(o.a), P(o.b), P(o.dst), nd, o.act);
         break;
       case DVD_CN_SIGMOID:
         sigmoid_kernel<<<cdiv(nd, 256), 256, 0, st>>>(P(o.a), P(o.dst), nd);
+        break;
+      case DVD_CN_INSTNORM:
+        instnorm_kernel<<<dim3((unsigned)B, cdiv(a.c, 64)), 1024, 0, st>>>(P(o.a), P(o.dst), a.c, (long)a.h * a.w, o.act,
+                                                                            1e-5f);
         break;
     }
   }

@@ -64,11 +64,12 @@ def npz_documents(settings, indices, files):
         yield d
 
 
-def prepare_conditioning(batch, device, grid, prestage_models):
+def prepare_conditioning(batch, device, grid, prestage_models, use_init_flow=False):
     """Documents given as decoded images: ingest (cv2.resize to 512^2, / 255; doc_benchmark.py:84-88) and the pre-stage
     nets (evaluation.py:162-216) fill in y512 / mask_cat / mask_y512 / line_msk / src_u8 as DEVICE tensors.  Documents
     that already carry their conditioning tensors (synthetic ones with env.use_prestage_nets=False, .npz files of
-    env.conditioning_dir) pass through untouched and need no pre-stage nets."""
+    env.conditioning_dir) pass through untouched and need no pre-stage nets.  use_init_flow: every document also gets
+    `init_flow` [2,G,G] from GeoTr (evaluation.py:172-178), in the same pre-stage pass when that runs."""
     from . import prestage
     need_ingest = [d for d in batch if "image_u8" in d and "y512" not in d]
     for d in need_ingest:
@@ -76,6 +77,16 @@ def prepare_conditioning(batch, device, grid, prestage_models):
         img = (img if th.is_tensor(img) else th.from_numpy(img)).to(device).contiguous()
         d["y512"], d["src_u8"] = ops.ingest_u8(img, swap_rb=False, out_size=512, want_rgb=True)
     todo = [d for d in batch if any(k not in d for k in ("mask_cat", "mask_y512", "line_msk"))]
+    if use_init_flow and (prestage_models is None or prestage_models[0] is None):
+        raise RuntimeError("env.use_init_flow needs the GeoTr_Seg_Inf model (pretrained_dewarp_model)")
+    if use_init_flow:
+        pending = {id(d) for d in todo}
+        rest = [d for d in batch if id(d) not in pending and "init_flow" not in d]
+        if rest:
+            src = th.stack([(d["y512"] if th.is_tensor(d["y512"]) else th.from_numpy(d["y512"])).to(device) for d in rest])
+            flow = prestage.init_flow(prestage_models[0], src, grid)
+            for j, d in enumerate(rest):
+                d["init_flow"] = flow[j]
     if not todo:
         return
     if prestage_models is None:
@@ -83,8 +94,10 @@ def prepare_conditioning(batch, device, grid, prestage_models):
                            "loaded (env.use_prestage_nets=False): give ready conditioning tensors or load the nets")
     src = th.stack([(d["y512"] if th.is_tensor(d["y512"]) else th.from_numpy(d["y512"])).to(device) for d in todo])
     cond = prestage.conditioning(*prestage_models, src, grid)
+    if use_init_flow and "init_flow" not in cond:
+        raise RuntimeError("env.use_init_flow needs GeoTr weights: reload_model(model.GeoTr, env.dewarping_model_path)")
     for j, d in enumerate(todo):
-        for k in ("mask_cat", "mask_y512", "line_msk"):
+        for k in ("mask_cat", "mask_y512", "line_msk") + (("init_flow",) if use_init_flow else ()):
             d[k] = cond[k][j]
 
 
@@ -158,11 +171,13 @@ def run_evaluation_docunet(settings, logger, val_loader, diffusion, model, pretr
                         d["image_u8"] = u8
                 elif "y512" not in d:
                     raise ValueError(f"{d['path']}: no 'source_image' and a non-integer 'source_image_ori' to make it from")
-        prepare_conditioning(batch, device, G, prestage_models)
+        use_init_flow = bool(getattr(env, "use_init_flow", False))
+        prepare_conditioning(batch, device, G, prestage_models, use_init_flow)
         t0 = time.time()
         src, msk, seg, line = stack("y512"), stack("mask_cat"), stack("mask_y512"), stack("line_msk")
+        init_flow = stack("init_flow") if use_init_flow else th.zeros(nb, 2, G, G, device=device)       # :176-181
         flow = run_sample_lr_dewarping(settings, logger, diffusion, model, 4, src, G, None,
-                                       th.zeros(nb, 2, G, G, device=device), None, None, None, msk, seg, line,
+                                       init_flow, None, None, None, msk, seg, line,
                                        th.zeros(nb, 256, G, G, device=device))
         th.cuda.synchronize()
         times.append((time.time() - t0) / nb)

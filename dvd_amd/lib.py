@@ -120,6 +120,12 @@ SIGNATURES = {
     "dvd_resize_bilinear_nchw": [c_void, c_void, C.c_long, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_void],
     "dvd_threshold_mask_mul": [c_void, c_void, c_void, c_void, C.c_int, C.c_long, C.c_float, c_void],
     "dvd_threshold_mask_mul_batch": [c_void, c_void, c_void, c_void, C.c_int, C.c_int, C.c_long, C.c_float, c_void],
+    "dvd_flash_attn_f32": [C.POINTER(AttnDesc), c_void],
+    "dvd_layernorm256_f32": [c_void, c_void, C.c_long, c_void, c_void, C.c_float, c_void],
+    "dvd_add_rows_f32": [c_void, c_void, c_void, C.c_long, C.c_int, C.c_int, c_void],
+    "dvd_transpose_f32": [c_void, c_void, C.c_int, C.c_int, C.c_int, c_void],
+    "dvd_soft_mask_mul_batch": [c_void, c_void, c_void, C.c_int, C.c_int, C.c_long, c_void],
+    "dvd_convex_upsample": [c_void, c_void, C.c_int, C.c_int, C.c_int, c_void, c_void, C.c_int, C.c_float, c_void],
     "dvd_ingest_u8": [c_void, C.c_int, C.c_int, C.c_int, c_void, C.c_int, c_void, c_void, c_void],
     "dvd_dither_f16": [c_void, c_void, c_void, C.c_long, C.c_uint, C.c_uint, c_void],
     "dvd_engine_create": [C.c_int, C.c_int, C.c_int, C.POINTER(c_void)],

@@ -4,6 +4,7 @@ Mirror of what the reference runs once per document before the diffusion loop (t
   GeoTr_Seg_Inf  (geotr_core.py:997-1019)  document mask -> mask_x (`mask_cat`)
   Seg            (geotr_core.py:984-995)   masked image + the six U2NETP decoder maps -> `mask_y512`
   UNet           (unet_model.py:4-37)      text-line features -> `line_msk`
+  GeoTr          (geotr_core.py:690-742)   only under env.use_init_flow: GeoTr_Seg_Inf.GeoTr -> `bm` -> `init_flow`
 with the reference's class names, state_dict keys and call signatures (val_TDiff.py:57-75 builds and loads them), so
 `seg.pth`, `seg_model.pth` and `line_model2.pth` load unchanged.  The architecture is written here ONCE as an op-list
 builder; the library executes the list (gather + exact-f32 MFMA GEMM per conv).  No ATen compute, no CPU fallback.
@@ -23,7 +24,7 @@ from .lib import ptr, stream_ptr
 
 _log = logging.getLogger(__name__)
 
-CONV, POOL, RESIZE, ADD, SIGMOID = range(5)
+CONV, POOL, RESIZE, ADD, SIGMOID, INSTNORM = range(6)
 BN_EPS = 1e-5
 
 
@@ -41,11 +42,12 @@ class Program:
         self.ch[s] = c
         return s
 
-    def conv(self, a, cout, src, ks=3, dil=1, act=2, b=-1):
+    def conv(self, a, cout, src, ks=3, dil=1, act=2, b=-1, stride=1):
         cin = self.ch[a] + (self.ch[b] if b >= 0 else 0)
         kp = (ks * ks * cin + 15) // 16 * 16
         dst = self._new(cout)
-        self.ops.append(dict(op=CONV, a=a, b=b, dst=dst, ks=ks, dil=dil, cout=cout, act=act, w_off=self.w_floats))
+        self.ops.append(dict(op=CONV, a=a, b=b, dst=dst, ks=ks, dil=dil, cout=cout, act=act, w_off=self.w_floats,
+                             flag=2 if stride == 2 else 0))
         self.convs.append((src, cin, cout, ks, kp))
         self.w_floats += cout * kp + (cout + 3) // 4 * 4        # bias padded to 16 bytes
         return dst
@@ -60,9 +62,14 @@ class Program:
         self.ops.append(dict(op=RESIZE, a=a, b=like, dst=dst, flag=int(align)))
         return dst
 
-    def add(self, a, b):
+    def add(self, a, b, relu=False):
         dst = self._new(self.ch[a])
-        self.ops.append(dict(op=ADD, a=a, b=b, dst=dst))
+        self.ops.append(dict(op=ADD, a=a, b=b, dst=dst, act=2 if relu else 0))
+        return dst
+
+    def instnorm(self, a, relu):
+        dst = self._new(self.ch[a])
+        self.ops.append(dict(op=INSTNORM, a=a, dst=dst, act=2 if relu else 0))
         return dst
 
     def sigmoid(self, a):
@@ -304,7 +311,7 @@ class _RefNet(nn.Module):
     def __init__(self):
         super().__init__()
         self._names = OrderedDict()
-        spec = synth.u2netp_spec() if self.kind == "u2netp" else synth.unet_spec()
+        spec = {"u2netp": synth.u2netp_spec, "unet": synth.unet_spec, "geotr": synth.geotr_spec}[self.kind]()
         for key, (shape, knd) in spec.items():
             flat = key.replace(".", "__")
             self._names[key] = flat
@@ -314,7 +321,7 @@ class _RefNet(nn.Module):
             else:
                 self.register_parameter(flat, nn.Parameter(torch.zeros(shape), requires_grad=False))
         self._nets, self._version, self._blob, self._blob_version = {}, 0, None, -1
-        self._program, self._outputs = build_u2netp() if self.kind == "u2netp" else build_unet()
+        self._program, self._outputs = {"u2netp": build_u2netp, "unet": build_unet, "geotr": build_geotr_fnet}[self.kind]()
 
     def state_dict(self, *args, prefix="", **kwargs):
         sd = super().state_dict(*args, **kwargs)
@@ -412,6 +419,254 @@ class UNet(_RefNet):
         return h, logits
 
 
+# ---------------------------------------------------------------------------------------------------------
+# GeoTr: the init-flow prior of env.use_init_flow (geotr_core.py:337-480,496-581,690-742; extractor.py:4-117)
+# ---------------------------------------------------------------------------------------------------------
+GEOTR_SIDE, GEOTR_T, GEOTR_D, GEOTR_HEADS, GEOTR_FF = 36, 1296, 256, 8, 2048
+LN_EPS = 1e-5
+
+
+def build_geotr_fnet(prefix: str = "fnet."):
+    """BasicEncoder(256, norm_fn='instance').forward + the ReLU of GeoTr.forward (folded into the last 1x1 conv)."""
+    P = Program(3)
+    plain = lambda n: ("plain", prefix + n + ".weight", prefix + n + ".bias")  # noqa: E731
+    x = P.instnorm(P.conv(0, 64, plain("conv1"), 7, 1, 0, stride=2), True)
+    for layer, dim, stride in ((1, 64, 1), (2, 128, 2), (3, 192, 2)):
+        for blk in (0, 1):
+            s = stride if blk == 0 else 1
+            p = f"layer{layer}.{blk}."
+            y = P.instnorm(P.conv(x, dim, plain(p + "conv1"), 3, 1, 0, stride=s), True)
+            y = P.instnorm(P.conv(y, dim, plain(p + "conv2"), 3, 1, 0), True)
+            if s != 1:
+                x = P.instnorm(P.conv(x, dim, plain(p + "downsample.0"), 1, 1, 0, stride=s), False)
+            x = P.add(x, y, relu=True)                      # ResidualBlock: relu(x + y)
+    return P, [P.conv(x, GEOTR_D, plain("conv2"), 1, 1, 2)]
+
+
+def build_geotr_update(prefix: str = "update_block."):
+    """UpdateBlock.forward on the decoder's map -> (dflow [2], raw mask [576]; the 0.25 is applied by the upsampling)."""
+    P = Program(GEOTR_D)
+    plain = lambda n: ("plain", prefix + n + ".weight", prefix + n + ".bias")  # noqa: E731
+    dflow = P.conv(P.conv(0, 256, plain("flow_head.conv1"), 3, 1, 2), 2, plain("flow_head.conv2"), 3, 1, 0)
+    mask = P.conv(P.conv(0, 256, plain("mask.0"), 3, 1, 2), 576, plain("mask.2"), 1, 1, 0)
+    return P, [dflow, mask]
+
+
+def geotr_pos_table() -> torch.Tensor:
+    """PositionEmbeddingSine(128, normalize=True) on an all-ones 36 x 36 mask (position_encoding.py:57-81) as [T, 256]
+    token rows, computed with the reference's f32 operations once per model."""
+    mask = torch.ones(1, GEOTR_SIDE, GEOTR_SIDE)
+    y_embed, x_embed = mask.cumsum(1, dtype=torch.float32), mask.cumsum(2, dtype=torch.float32)
+    scale = 2 * np.pi
+    y_embed = y_embed / (y_embed[:, -1:, :] + 1e-6) * scale
+    x_embed = x_embed / (x_embed[:, :, -1:] + 1e-6) * scale
+    dim_t = torch.arange(128, dtype=torch.float32)
+    dim_t = 10000 ** (2 * (dim_t // 2) / 128)
+    pos_x, pos_y = x_embed[:, :, :, None] / dim_t, y_embed[:, :, :, None] / dim_t
+    pos_x = torch.stack((pos_x[:, :, :, 0::2].sin(), pos_x[:, :, :, 1::2].cos()), dim=4).flatten(3)
+    pos_y = torch.stack((pos_y[:, :, :, 0::2].sin(), pos_y[:, :, :, 1::2].cos()), dim=4).flatten(3)
+    return torch.cat((pos_y, pos_x), dim=3).reshape(GEOTR_T, GEOTR_D).contiguous()
+
+
+def _geotr_run_tensors(prefix=""):
+    """The transformer tensors GeoTr evaluates, in blob order.  multihead_attn_list.1 / norm2_list.1 are loaded (they are
+    in the state_dict) but never evaluated: memory_list has one entry (geotr_core.py:390-406)."""
+    names = []
+    for part in ("TransEncoder", "TransDecoder"):
+        for i in range(6):
+            p = f"{prefix}{part}.layers.{i}."
+            for m in ("self_attn.", "multihead_attn_list.0."):
+                names += [p + m + "in_proj_weight", p + m + "in_proj_bias", p + m + "out_proj.weight", p + m + "out_proj.bias"]
+            names += [p + "linear1.weight", p + "linear1.bias", p + "linear2.weight", p + "linear2.bias"]
+            for n in ("norm1.", "norm2_list.0.", "norm3."):
+                names += [p + n + "weight", p + n + "bias"]
+    return names + [prefix + "query_embed.weight"]
+
+
+class GeoTr(_RefNet):
+    """geotr_core.py:690-742 on HIP: fnet on the conv-net executor, the 12 post-norm attention layers on the exact-f32 GEMM
+    + dvd_flash_attn_f32 + dvd_layernorm256_f32, the update block on the executor, the convex upsampling in one kernel.
+    forward(image1 [N,3,288,288]) -> bm [N,2,288,288] (pixels, as the reference).  One pass per batch of documents."""
+    kind = "geotr"
+
+    def __init__(self, num_attn_layers=6, num_token=1296):
+        if (num_attn_layers, num_token) != (6, GEOTR_T):
+            raise NotImplementedError("the init-flow prior builds GeoTr(num_attn_layers=6, num_token=1296)")
+        super().__init__()
+        self._upd_program, self._upd_outputs = build_geotr_update()
+        names = _geotr_run_tensors()
+        spec = synth.geotr_spec()
+        self._tensors, off = OrderedDict(), self._program.w_floats + self._upd_program.w_floats
+        for k in names:
+            n = int(np.prod(spec[k][0]))
+            self._tensors[k] = (off, spec[k][0])
+            off += (n + 3) // 4 * 4
+        self._floats = off
+        self._pos = None
+
+    def bound(self) -> bool:
+        """True once weights were loaded (load_state_dict / reload_model) or received in the rank broadcast."""
+        return self._version > 0 or self._blob is not None
+
+    def blob_bytes(self) -> int:
+        return self._floats * 4
+
+    def pack_into(self, view_u8: torch.Tensor):
+        sd = {k: v.detach().cpu() for k, v in self.state_dict().items()}
+        out = torch.zeros(self._floats, dtype=torch.float32)
+        nf, nu = self._program.w_floats, self._upd_program.w_floats
+        out[:nf] = self._program.pack(sd)
+        out[nf:nf + nu] = self._upd_program.pack(sd)
+        for k, (off, shape) in self._tensors.items():
+            out[off:off + int(np.prod(shape))] = sd[k].float().reshape(-1)
+        view_u8.copy_(out.view(torch.uint8))
+
+    def _weights(self, batch):
+        """(fnet executor, update executor, name -> device view) for `batch` documents (executors cached per batch)."""
+        from .cross_model import _require_gpu
+        dev = self.device
+        _require_gpu(dev)
+        if self._blob is None or self._blob_version != self._version:
+            from . import dist_util
+            if dist_util.world_size() > 1:
+                raise RuntimeError("weights changed in a multi-rank run: call dist_util.materialize_blobs([...]) on "
+                                   "every rank first (the executor never communicates)")
+            dist_util.materialize_blobs([self])
+        blob = self._blob
+        key = (batch, dev.index)
+        nets = self._nets.get(key)
+        if nets is None:
+            for old in [k for k in self._nets if k[1:] == key[1:]][:-(self.MAX_EXECUTORS_PER_SHAPE - 1) or None]:
+                del self._nets[old]
+            nets = (ConvNet(self._program, self._outputs, (288, 288), device=dev, batch=batch),
+                    ConvNet(self._upd_program, self._upd_outputs, (GEOTR_SIDE, GEOTR_SIDE), device=dev, batch=batch))
+            for n in nets:
+                n._bound = None
+        else:
+            del self._nets[key]
+        self._nets[key] = nets
+        nf, nu = self._program.w_floats, self._upd_program.w_floats
+        if nets[0]._bound is not blob:
+            nets[0].bind_weights(blob[:nf])
+            nets[1].bind_weights(blob[nf:nf + nu])
+            nets[0]._bound = nets[1]._bound = blob
+        if self._pos is None or self._pos.device != dev:
+            self._pos = geotr_pos_table().to(dev)
+        w = {k: blob[off:off + int(np.prod(shape))].view(*shape) for k, (off, shape) in self._tensors.items()}
+        return nets, w
+
+    # ---- the transformer (token rows [N * T, 256], document-major) ----
+    def _attention(self, q, ldq, k, ldk, vt, n, out):
+        d = lib.AttnDesc()
+        d.head_dim, d.heads, d.batch, d.tq, d.tk, d.kv_batch_div = 32, GEOTR_HEADS, n, GEOTR_T, GEOTR_T, 1
+        d.Q, d.ldq, d.strideQ = q.data_ptr(), ldq, GEOTR_T * ldq
+        d.K, d.ldk, d.strideK = k.data_ptr(), ldk, GEOTR_T * ldk
+        d.Vt, d.ldvt, d.strideVt = vt.data_ptr(), GEOTR_T, GEOTR_D * GEOTR_T
+        d.O, d.ldo, d.strideO = out.data_ptr(), GEOTR_D, GEOTR_T * GEOTR_D
+        d.scale = float(np.float32(1.0 / np.sqrt(32.0)))
+        lib.call("dvd_flash_attn_f32", C.byref(d), stream_ptr())
+
+    def _mha(self, w, p, q_in, k_in, v_in, res, n, out):
+        """res + MultiheadAttention(q_in, k_in, v_in) (in_proj chunks q / k / v, out_proj) -> out [N*T, 256]."""
+        from .ops import gemm_nt
+        W, B = w[p + "in_proj_weight"], w[p + "in_proj_bias"]
+        D, rows = GEOTR_D, n * GEOTR_T
+        dev = q_in.device
+        if q_in is k_in:      # self-attention: q and k from one GEMM over the stacked q / k weights
+            qk = torch.empty(rows, 2 * D, dtype=torch.float32, device=dev)
+            gemm_nt(q_in, W[:2 * D], out32=qk, bias=B[:2 * D])
+            q, ldq, k, ldk = qk, 2 * D, qk[:, D:], 2 * D
+        else:
+            q = torch.empty(rows, D, dtype=torch.float32, device=dev)
+            k = torch.empty(rows, D, dtype=torch.float32, device=dev)
+            gemm_nt(q_in, W[:D], out32=q, bias=B[:D])
+            gemm_nt(k_in, W[D:2 * D], out32=k, bias=B[D:2 * D])
+            ldq = ldk = D
+        vt = torch.empty(n, D, GEOTR_T, dtype=torch.float32, device=dev)     # V^T per document: Wv . x^T + bv (row bias)
+        gemm_nt(W[2 * D:], v_in, out32=vt, bias=B[2 * D:], bias_row=True, batch=n, M=D, N=GEOTR_T, K=D,
+                strides={"A": 0, "B": GEOTR_T * D, "C32": D * GEOTR_T})
+        o = torch.empty(rows, D, dtype=torch.float32, device=dev)
+        self._attention(q, ldq, k, ldk, vt, n, o)
+        gemm_nt(o, w[p + "out_proj.weight"], out32=out, bias=w[p + "out_proj.bias"], res=res)
+
+    def _ln(self, w, p, x, out):
+        lib.call("dvd_layernorm256_f32", ptr(x), ptr(out), x.shape[0], ptr(w[p + "weight"]), ptr(w[p + "bias"]),
+                 C.c_float(LN_EPS), stream_ptr())
+        return out
+
+    def _add_pos(self, x, out):
+        lib.call("dvd_add_rows_f32", ptr(x), ptr(self._pos), ptr(out), x.shape[0], GEOTR_T, GEOTR_D, stream_ptr())
+        return out
+
+    def _layer(self, w, p, tgt, memory, memory_pos, n):
+        """attnLayer.forward_post (geotr_core.py:381-416) with memory_list = [memory]."""
+        from .ops import gemm_nt
+        e = lambda: torch.empty_like(tgt)  # noqa: E731
+        tp = self._add_pos(tgt, e())
+        y = e()
+        self._mha(w, p + "self_attn.", tp, tp, tgt, tgt, n, y)
+        t1 = self._ln(w, p + "norm1.", y, e())
+        if memory_pos is None:
+            memory_pos = self._add_pos(memory, e())
+        self._mha(w, p + "multihead_attn_list.0.", self._add_pos(t1, e()), memory_pos, memory, t1, n, y)
+        t2 = self._ln(w, p + "norm2_list.0.", y, e())
+        h = torch.empty(tgt.shape[0], GEOTR_FF, dtype=torch.float32, device=tgt.device)
+        gemm_nt(t2, w[p + "linear1.weight"], out32=h, bias=w[p + "linear1.bias"], act=2)
+        gemm_nt(h, w[p + "linear2.weight"], out32=y, bias=w[p + "linear2.bias"], res=t2)
+        return self._ln(w, p + "norm3.", y, e())
+
+    def _transpose(self, x, n, rows, cols):
+        out = torch.empty(n, cols, rows, dtype=torch.float32, device=x.device)
+        lib.call("dvd_transpose_f32", ptr(x), ptr(out), n, rows, cols, stream_ptr())
+        return out
+
+    def stages(self, image1: torch.Tensor):
+        """The stage outputs of one pass: dict(fnet [N,256,36,36] (after the ReLU), encoder / decoder [N,256,36,36],
+        dflow [N,2,36,36], mask [N,576,36,36] (the mask head's conv output, before the 0.25))."""
+        x = image1.to(self.device, torch.float32).contiguous()
+        if x.dim() != 4 or tuple(x.shape[1:]) != (3, 288, 288):
+            raise lib.DvdError(f"GeoTr expects [N,3,288,288] images (num_token 1296 = 36^2), got {tuple(x.shape)}")
+        n = x.shape[0]
+        (fnet, upd), w = self._weights(n)
+        fmap = fnet.run(x)[0]                                                   # [N,256,36,36]
+        tok = self._transpose(fmap, n, GEOTR_D, GEOTR_T).reshape(n * GEOTR_T, GEOTR_D)
+        for i in range(6):                                                      # TransEncoder: memory = the layer's input
+            tok = self._layer(w, f"TransEncoder.layers.{i}.", tok, tok, None, n)
+        enc = tok
+        enc_pos = self._add_pos(enc, torch.empty_like(enc))
+        tgt = w["query_embed.weight"].unsqueeze(0).expand(n, -1, -1).reshape(n * GEOTR_T, GEOTR_D).contiguous()
+        for i in range(6):                                                      # TransDecoder: memory = the encoder output
+            tgt = self._layer(w, f"TransDecoder.layers.{i}.", tgt, enc, enc_pos, n)
+        to_map = lambda t: self._transpose(t, n, GEOTR_T, GEOTR_D).reshape(n, GEOTR_D, GEOTR_SIDE, GEOTR_SIDE)  # noqa: E731
+        dec = to_map(tgt)
+        dflow, mask = upd.run(dec)
+        return {"fnet": fmap, "encoder": to_map(enc), "decoder": dec, "dflow": dflow, "mask": mask}
+
+    def upsample(self, dflow, mask, grid=None, want_bm=True):
+        """convex upsampling -> (bm [N,2,288,288] or None, init_flow [N,2,grid,grid] = resize(bm / 287) or None)."""
+        n = dflow.shape[0]
+        bm = torch.empty(n, 2, 288, 288, dtype=torch.float32, device=dflow.device) if want_bm else None
+        init = torch.empty(n, 2, grid, grid, dtype=torch.float32, device=dflow.device) if grid else None
+        lib.call("dvd_convex_upsample", ptr(mask), ptr(dflow), n, GEOTR_SIDE, GEOTR_SIDE, ptr(bm), ptr(init),
+                 int(grid or 0), C.c_float(287.0), stream_ptr())
+        return bm, init
+
+    def run(self, image1, grid=None, want_bm=True):
+        st = self.stages(image1)
+        return self.upsample(st["dflow"], st["mask"], grid, want_bm)
+
+    def forward(self, image1):
+        return self.run(image1)[0]
+
+
+def soft_mask_mul(msk: torch.Tensor, x: torch.Tensor) -> torch.Tensor:
+    """msk * x with msk [N,1,H,W], x [N,C,H,W] (GeoTr_Seg_Inf.forward, geotr_core.py:1007)."""
+    n, c, h, w = x.shape
+    out = torch.empty_like(x)
+    lib.call("dvd_soft_mask_mul_batch", ptr(msk), ptr(x), ptr(out), n, c, h * w, stream_ptr())
+    return out
+
+
 class _MskHolder(nn.Module):
     """A module whose only trained child is `self.msk = U2NETP(3, 1)` (state_dict keys 'msk.<...>')."""
 
@@ -454,13 +709,53 @@ class Seg(_MskHolder):
 
 
 class GeoTr_Seg_Inf(_MskHolder):
-    """geotr_core.py:997-1019: forward(x) -> (bm, msk resized to 512).  The GeoTr branch that produces `bm` is DEAD on
-    the live configuration - val_TDiff.py:57-58 only loads weights into `.msk`, and evaluation.py:176-181 reads `bm`
-    only under env.use_init_flow - so it is not evaluated and `bm` is None."""
+    """geotr_core.py:997-1019: forward(x) -> (bm, msk resized to 512).  `.GeoTr` is the reference's child
+    GeoTr(num_attn_layers=6, num_token=1296), built on first access (reload_model(model.GeoTr, path) as train_TDiff.py:89
+    calls it): the live configuration without env.use_init_flow never touches it, so it is never constructed, loaded,
+    broadcast or run, and `bm` is None - exactly as before.  Once GeoTr holds weights, bm = GeoTr(msk * x) [N,2,288,288]."""
+
+    def __getattr__(self, name):
+        if name == "GeoTr":
+            mods = self.__dict__.get("_modules")
+            if mods is not None and "GeoTr" not in mods:
+                g = GeoTr(num_attn_layers=6, num_token=GEOTR_T)
+                g.to(self.msk.device)
+                g.train(self.training)
+                mods["GeoTr"] = g
+        return super().__getattr__(name)
+
+    def live_geotr(self):
+        """The GeoTr child when it exists and holds weights, else None (no construction)."""
+        g = self._modules.get("GeoTr")
+        return g if g is not None and g.bound() else None
+
+    def state_dict(self, *args, **kwargs):
+        sd = self.msk.state_dict(prefix="msk.")
+        if "GeoTr" in self._modules:
+            sd.update(self._modules["GeoTr"].state_dict(prefix="GeoTr."))
+        return sd
+
+    def load_state_dict(self, state_dict, strict=True, **kw):
+        geo = {k[6:]: v for k, v in state_dict.items() if k.startswith("GeoTr.")}
+        if geo:
+            self.GeoTr.load_state_dict(geo, strict=strict, **kw)
+        return super().load_state_dict({k: v for k, v in state_dict.items() if not k.startswith("GeoTr.")}, strict=strict,
+                                       **kw)
+
+    def mask_and_init_flow(self, x, grid=None, want_bm=False):
+        """-> (bm or None, msk resized to 512, init_flow [N,2,grid,grid] or None): the U2NETP pass once, then - when GeoTr
+        holds weights - GeoTr(msk * x) with the sampler hand-off of evaluation.py:172-178 fused into its last kernel."""
+        msk = self.msk(x)[0]
+        mask512 = resize_bilinear(msk, 512, True)
+        g = self.live_geotr()
+        if g is None:
+            return None, mask512, None
+        bm, init = g.run(soft_mask_mul(msk, x.to(msk.device, torch.float32).contiguous()), grid, want_bm)
+        return bm, mask512, init
 
     def forward(self, x):
-        msk = self.msk(x)[0]
-        return None, resize_bilinear(msk, 512, True)
+        bm, mask512, _ = self.mask_and_init_flow(x, None, True)
+        return bm, mask512
 
 
 def _strip_and_load(model, sd, n):
@@ -519,14 +814,29 @@ def conditioning(dewarp_model, seg_model, line_model, source512: torch.Tensor, g
     seg_map_all = torch.cat([resize_bilinear(t, grid, False) for t in (hx6, hx5d, hx4d, hx3d, hx2d, hx1d)], dim=1)
     textline_map, _ = line_model(mskx)                                                                   # :209
     line_msk = resize_bilinear(textline_map, grid, False)
+    # with GeoTr weights bound (env.use_init_flow) the same pass also yields init_flow = resize(GeoTr(msk * x) / 287, G)
+    # (:172-178); otherwise it is the U2NETP pass alone, as before
     if side is not None:
         with torch.cuda.stream(side):
             side.wait_event(ready)
-            _, mask_x = dewarp_model(source_288)                                                         # :176
+            _, mask_x, init_flow = dewarp_model.mask_and_init_flow(source_288, grid)                     # :176
         cur.wait_stream(side)
         mask_x.record_stream(cur)
+        if init_flow is not None:
+            init_flow.record_stream(cur)
         source_288.record_stream(side)
     else:
-        _, mask_x = dewarp_model(source_288)
-    return {"mask_cat": mask_x, "mask_y512": seg_map_all, "line_msk": line_msk,
-            "mskx": mskx, "d0": d0}
+        _, mask_x, init_flow = dewarp_model.mask_and_init_flow(source_288, grid)
+    out = {"mask_cat": mask_x, "mask_y512": seg_map_all, "line_msk": line_msk, "mskx": mskx, "d0": d0}
+    if init_flow is not None:
+        out["init_flow"] = init_flow
+    return out
+
+
+def init_flow(dewarp_model, source512: torch.Tensor, grid: int) -> torch.Tensor:
+    """init_flow [N,2,G,G] of documents whose other conditioning tensors are given (evaluation.py:162,172-178)."""
+    source_288 = resize_bilinear(source512.to(torch.float32).contiguous(), 288, True)
+    _, _, flow = dewarp_model.mask_and_init_flow(source_288, grid)
+    if flow is None:
+        raise RuntimeError("env.use_init_flow needs GeoTr weights: reload_model(model.GeoTr, env.dewarping_model_path)")
+    return flow

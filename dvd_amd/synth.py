@@ -353,6 +353,76 @@ def unet_spec():
     return s
 
 
+def _attn_layer(s, p):
+    """attnLayer(256) (geotr_core.py:337-379): registration order of the reference's __init__."""
+    for m in ("self_attn.", "multihead_attn_list.0.", "multihead_attn_list.1."):
+        s[p + m + "in_proj_weight"] = ((768, 256), "w")
+        s[p + m + "in_proj_bias"] = ((768,), "b")
+        s[p + m + "out_proj.weight"] = ((256, 256), "w")
+        s[p + m + "out_proj.bias"] = ((256,), "b")
+    s[p + "linear1.weight"] = ((2048, 256), "w")
+    s[p + "linear1.bias"] = ((2048,), "b")
+    s[p + "linear2.weight"] = ((256, 2048), "w")
+    s[p + "linear2.bias"] = ((256,), "b")
+    for n in ("norm1.", "norm2_list.0.", "norm2_list.1.", "norm3."):
+        s[p + n + "weight"] = ((256,), "ln_w")
+        s[p + n + "bias"] = ((256,), "ln_b")
+
+
+def geotr_spec(prefix: str = ""):
+    """GeoTr(num_attn_layers=6, num_token=1296) (geotr_core.py:690-742; extractor.py:4-117): fnet = BasicEncoder(256,
+    'instance') - InstanceNorm2d without affine parameters holds no tensors - TransEncoder / TransDecoder of 6 attnLayers,
+    query_embed, update_block."""
+    s = OrderedDict()
+    q = prefix + "fnet."
+    s[q + "conv1.weight"] = ((64, 3, 7, 7), "w")
+    s[q + "conv1.bias"] = ((64,), "b")
+    cin = 64
+    for layer, dim, stride in ((1, 64, 1), (2, 128, 2), (3, 192, 2)):
+        for blk in (0, 1):
+            p = f"{q}layer{layer}.{blk}."
+            s[p + "conv1.weight"] = ((dim, cin, 3, 3), "w")
+            s[p + "conv1.bias"] = ((dim,), "b")
+            s[p + "conv2.weight"] = ((dim, dim, 3, 3), "w")
+            s[p + "conv2.bias"] = ((dim,), "b")
+            if blk == 0 and stride != 1:
+                s[p + "downsample.0.weight"] = ((dim, cin, 1, 1), "w")
+                s[p + "downsample.0.bias"] = ((dim,), "b")
+            cin = dim
+    s[q + "conv2.weight"] = ((256, 192, 1, 1), "w")
+    s[q + "conv2.bias"] = ((256,), "b")
+    for part in ("TransEncoder", "TransDecoder"):
+        for i in range(6):
+            _attn_layer(s, f"{prefix}{part}.layers.{i}.")
+    s[prefix + "query_embed.weight"] = ((1296, 256), "emb")
+    u = prefix + "update_block."
+    s[u + "flow_head.conv1.weight"] = ((256, 256, 3, 3), "w")
+    s[u + "flow_head.conv1.bias"] = ((256,), "b")
+    s[u + "flow_head.conv2.weight"] = ((2, 256, 3, 3), "w")
+    s[u + "flow_head.conv2.bias"] = ((2,), "b")
+    s[u + "mask.0.weight"] = ((256, 256, 3, 3), "w")
+    s[u + "mask.0.bias"] = ((256,), "b")
+    s[u + "mask.2.weight"] = ((576, 256, 1, 1), "w")
+    s[u + "mask.2.bias"] = ((576,), "b")
+    return s
+
+
+def synth_geotr_state_dict(seed: int = 0, prefix: str = ""):
+    """Deterministic stand-in GeoTr weights (the layout of geotr_spec): std-1/sqrt(fan_in) projections, post-norm LayerNorms
+    near the identity, a unit-variance query embedding.  The flow head's last conv carries a gain of 4, so the prior's
+    init_flow = bm / 287 reaches a few hundredths, the size of a real document's (unit gain: a few thousandths)."""
+    out = OrderedDict()
+    for k, (shape, knd) in geotr_spec(prefix).items():
+        if knd == "emb":
+            t = uniform(f"geotr/{k}", shape, -1.7, 1.7, seed)
+        else:
+            t = synth_tensor(f"geotr/{k}", shape, knd, seed)
+        if k.endswith("flow_head.conv2.weight"):
+            t = (t * np.float32(4.0)).astype(np.float32)
+        out[k] = t
+    return out
+
+
 def synth_convnet_state_dict(kind: str, seed: int = 0, prefix: str = ""):
     """Synthetic state dict of 'u2netp' (keys optionally prefixed, e.g. 'msk.') or 'unet'.  ReLU-BN stacks with
     std-1/sqrt(fan_in) uniform weights lose variance layer by layer, so conv weights carry a gain of 1.2 (activations

@@ -36,9 +36,6 @@ def run(settings):
         device=dist_util.dev(), train_mode=env.train_mode, tv=env.time_variant, grid_size=env.grid_size,
         **args_to_dict(settings, model_and_diffusion_defaults().keys()))
     setattr(diffusion, "settings", settings)
-    if getattr(env, "use_init_flow", False):
-        raise NotImplementedError("env.use_init_flow needs GeoTr's `ref_bm`, whose weights the reference itself never "
-                                  "loads (val_TDiff.py:57-58 only reloads `.msk`): not a live configuration")
     # rank 0 alone reads the checkpoint (val_TDiff.py:79); the other ranks receive the packed blob below.  A failure on
     # rank 0 (missing / corrupt file) is agreed on by every rank BEFORE the broadcast, so all ranks raise together.
     failure = None
@@ -61,17 +58,11 @@ def run(settings):
     model.to(dist_util.dev())
     print(get_parameter_number(model))
     model.eval()
-    pre, failure = None, None
-    if getattr(env, "use_prestage_nets", False):
-        try:
-            pre = load_prestage_models(env)
-        except Exception as e:  # noqa: BLE001
-            failure = e
-        dist_util.raise_together(failure, "loading the pre-stage checkpoints")
+    pre = load_prestage(env)
     # the path's ONE collective, issued eagerly and unconditionally by every rank BEFORE the documents are sharded:
-    # rank 0 packs every model (denoiser + the three pre-stage nets) into one flat buffer, one broadcast (a rank whose
-    # shard is empty still takes part, then goes to the barrier)
-    dist_util.materialize_blobs([model] + list(pre or ()))
+    # rank 0 packs every model (denoiser + the pre-stage nets, + GeoTr under env.use_init_flow) into one flat buffer, one
+    # broadcast (a rank whose shard is empty still takes part, then goes to the barrier)
+    dist_util.materialize_blobs(blob_models(model, pre, env))
 
     if env.eval_dataset_name == "synthetic":
         n_docs = env.num_synthetic_docs
@@ -101,6 +92,33 @@ def run(settings):
             dist.destroy_process_group()
     logger.log("sampling complete")
     return results
+
+
+def load_prestage(env):
+    """The pre-stage models of a run as (dewarp, seg, line) or None: the three nets under env.use_prestage_nets; under
+    env.use_init_flow also GeoTr inside the dewarp model (with the other nets off: the dewarp model alone).  COLLECTIVE:
+    a failure on rank 0 raises on every rank."""
+    use_nets, use_init_flow = bool(getattr(env, "use_prestage_nets", False)), bool(getattr(env, "use_init_flow", False))
+    if not (use_nets or use_init_flow):
+        return None
+    pre, failure = None, None
+    try:
+        pre = load_prestage_models(env) if use_nets else (load_dewarp_model(env), None, None)
+        if use_init_flow:
+            load_geotr(pre[0], env)
+    except Exception as e:  # noqa: BLE001 - re-raised on every rank by raise_together
+        failure = e
+    dist_util.raise_together(failure, "loading the pre-stage checkpoints")
+    return pre
+
+
+def blob_models(model, pre, env):
+    """The models of the one flat weight broadcast, in order: the denoiser, the loaded pre-stage nets, then - only under
+    env.use_init_flow - GeoTr (once)."""
+    out = [model] + [m for m in (pre or ()) if m is not None]
+    if getattr(env, "use_init_flow", False):
+        out.append(pre[0].GeoTr)
+    return out
 
 
 def load_prestage_models(env):
@@ -133,6 +151,49 @@ def load_prestage_models(env):
         m.to(dist_util.dev())
         m.eval()
     return dewarp, seg, line
+
+
+def _load_or_synthesize(path, from_file, synthetic, env):
+    if os.path.exists(path):
+        from_file(path)
+        logger.log(f"loaded {path}")
+    elif _want_synthetic_weights(env):
+        synthetic()
+        logger.log(f"{path} not found: using deterministic synthetic weights")
+    else:
+        raise FileNotFoundError(path)
+
+
+def load_dewarp_model(env):
+    """GeoTr_Seg_Inf alone (its `.msk` from env.seg_model_path, val_TDiff.py:57-58): the init-flow prior's document mask
+    when the other pre-stage nets are off (documents with ready conditioning tensors)."""
+    from .prestage import GeoTr_Seg_Inf, reload_segmodel
+    dewarp = GeoTr_Seg_Inf()
+    if dist_util.rank() == 0:
+        _load_or_synthesize(env.seg_model_path, lambda p: reload_segmodel(dewarp.msk, p),
+                            lambda: dewarp.msk.load_state_dict(
+                                {k: torch.from_numpy(np.asarray(v)) for k, v in synth.synth_convnet_state_dict("u2netp", 11).items()},
+                                strict=True), env)
+    dewarp.to(dist_util.dev())
+    dewarp.eval()
+    return dewarp
+
+
+def load_geotr(dewarp, env):
+    """env.use_init_flow: GeoTr's weights as train_TDiff.py:89 loads them - reload_model(model.GeoTr,
+    env.dewarping_model_path) - on rank 0; the other ranks construct the child and receive its blob in the broadcast.
+    A missing checkpoint raises (on every rank, through raise_together) unless synthetic weights are allowed."""
+    from .prestage import reload_model
+    geo = dewarp.GeoTr
+    if dist_util.rank() == 0:
+        path = getattr(env, "dewarping_model_path", "") or ""
+        _load_or_synthesize(path, lambda p: reload_model(geo, p),
+                            lambda: geo.load_state_dict({k: torch.from_numpy(np.asarray(v))
+                                                         for k, v in synth.synth_geotr_state_dict(31).items()}, strict=True),
+                            env)
+    geo.to(dist_util.dev())
+    geo.eval()
+    return geo
 
 
 def _require_gpu():

@@ -155,7 +155,7 @@ const char* dvd_gemm_kernel_name(const dvd_gemm_desc* desc);
  *   Vt [kv_batch, heads*head_dim, tk] row stride ldvt  (V TRANSPOSED: keys contiguous)
  *   O  [batch, tq, heads*head_dim]  row stride ldo
  * kv batch of query batch b is b / kv_batch_div (hypotheses of one document share its conditioning
- * K/V).  head_dim in {64, 256}; tk % 8 == 0. */
+ * K/V).  head_dim in {64, 256}; tk % 8 == 0.  (head_dim 32 runs in f32: dvd_flash_attn_f32.) */
 typedef struct {
   int head_dim, heads, batch, tq, tk, kv_batch_div;
   const void* Q; int ldq; long strideQ;
@@ -167,7 +167,8 @@ typedef struct {
 
 int dvd_flash_attn(const dvd_attn_desc* desc, void* stream);
 /* Name of the kernel dvd_flash_attn launches for a problem shape (the choice depends on head_dim, tq and tk only -
- * never on the batch or the environment).  Measurement tooling matches rocprofv3 / PMC records against it. */
+ * never on the batch or the environment).  Measurement tooling matches rocprofv3 / PMC records against it.  head_dim 32
+ * names the kernel of dvd_flash_attn_f32. */
 const char* dvd_flash_attn_kernel_name(int head_dim, int tq, int tk);
 
 /* ------------------------------------------------------------------------------------------
@@ -247,18 +248,21 @@ int dvd_nhwc_to_nchw(const float* in, float* out, int c, int h, int w, void* str
  * conv weight as [cout, kpad] with K order (ky*ks+kx)*cin + c, kpad = ks*ks*cin rounded up to 16,
  * followed by the bias [cout] padded to a multiple of 4 floats; convs packed in op order).  Activations are channels-last f32; convs run
  * on the exact-f32 MFMA GEMM. */
-enum { DVD_CN_CONV = 0, DVD_CN_POOL = 1, DVD_CN_RESIZE = 2, DVD_CN_ADD = 3, DVD_CN_SIGMOID = 4 };
+enum { DVD_CN_CONV = 0, DVD_CN_POOL = 1, DVD_CN_RESIZE = 2, DVD_CN_ADD = 3, DVD_CN_SIGMOID = 4, DVD_CN_INSTNORM = 5 };
 typedef struct {
   int op;           /* DVD_CN_* */
   int a, b;         /* input slots; b = -1 when unused.  conv: b is concatenated after a along channels
                        (torch.cat((a, b), 1)); add: second operand; resize: the slot whose size is the target */
   int dst;          /* output slot (each slot is written once) */
-  int ks, dil;      /* conv: kernel size 1 or 3, dilation (padding = dil * (ks / 2)) */
-  int cout, act;    /* conv: output channels; 0 none, 2 ReLU */
+  int ks, dil;      /* conv: kernel size 1, 3 or 7, dilation (padding = dil * (ks / 2)) */
+  int cout, act;    /* conv: output channels; act 0 none, 2 ReLU - also for add (relu(a + b)) and instnorm */
   long w_off;       /* conv: offset, in floats, of this conv's [cout, kpad] weights (+ bias) in the blob */
   int h, w;         /* resize with b = -1: explicit target size */
-  int flag;         /* resize: align_corners; pool: ceil_mode */
+  int flag;         /* resize: align_corners; pool: ceil_mode; conv: stride (0 or 1 = stride 1; 2 = stride 2, single
+                       source) */
 } dvd_cn_op;
+/* DVD_CN_INSTNORM: nn.InstanceNorm2d without affine parameters (per image and channel over h*w, biased variance,
+ * eps 1e-5; extractor.py:31-35,62-63), then ReLU when act == 2. */
 
 int dvd_convnet_create(const dvd_cn_op* ops, int n_ops, int n_slots, int in_c, int in_h, int in_w, void** handle);
 /* The same net for `batch` images per run (the documents of a batch, evaluation.py:162-216 is called per document in the
@@ -285,6 +289,28 @@ int dvd_threshold_mask_mul(const float* d0, const float* x_nchw, float* out_nchw
 /* the same for n images in one launch: d0 [n, hw], x / out [n, c, hw], mask_out [n, hw] */
 int dvd_threshold_mask_mul_batch(const float* d0, const float* x_nchw, float* out_nchw, float* mask_out, int n, int c,
                                  long hw, float thr, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * GeoTr, DocTr's geometry transformer (the init-flow prior of env.use_init_flow; train_settings/models/geotr/
+ * geotr_core.py:337-480,496-581,690-742, evaluation.py:172-178).  Its convolutions run on the conv-net executor above,
+ * its projections and FFNs on dvd_gemm_nt dtype 1; these are the remaining pieces, all exact f32.
+ * Attention core at head_dim 32 on f32 operands (dvd_attn_desc as for dvd_flash_attn; Q, K, Vt, O point to floats):
+ * O = softmax(scale * Q K^T) V, q scaled before the products as nn.MultiheadAttention does. */
+int dvd_flash_attn_f32(const dvd_attn_desc* desc, void* stream);
+/* nn.LayerNorm(256) with affine over `rows` contiguous rows: out = (x - mean) / sqrt(var + eps) * gamma + beta. */
+int dvd_layernorm256_f32(const float* in, float* out, long rows, const float* gamma, const float* beta, float eps,
+                         void* stream);
+/* out[r, c] = a[r, c] + pos[r % pos_rows, c] (c % 4 == 0). */
+int dvd_add_rows_f32(const float* a, const float* pos, float* out, long rows, int pos_rows, int c, void* stream);
+/* [n, rows, cols] -> [n, cols, rows]. */
+int dvd_transpose_f32(const float* in, float* out, int n, int rows, int cols, void* stream);
+/* out = msk * x with a [n, hw] soft mask (no threshold; GeoTr_Seg_Inf.forward, geotr_core.py:1007); x / out [n, c, hw]. */
+int dvd_soft_mask_mul_batch(const float* msk, const float* x_nchw, float* out_nchw, int n, int c, long hw, void* stream);
+/* GeoTr.upsample_flow(coords1 - coords0, 0.25 * mask): mask [n, 576, h, w] (the mask head's raw conv output), dflow
+ * [n, 2, h, w].  bm (optional) [n, 2, 8h, 8w]; init_flow (optional) [n, 2, g, g] = F.interpolate(bm / norm, g, bilinear,
+ * align_corners=True) computed without materialising bm. */
+int dvd_convex_upsample(const float* mask, const float* dflow, int n, int h, int w, float* bm, float* init_flow, int g,
+                        float norm, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Image ingest (datasets/doc_dataset/doc_benchmark.py:75-97 after the decode):
