@@ -113,8 +113,8 @@ class DvdDenoiser(nn.Module):
         Like the reference's forward it is a PURE function of its arguments: on grids whose GEMM weights are dithered the
         phase is `dither_step` when given (diffusion.ddim_sample / p_mean_variance pass the loop's S-1-i, so a hand-rolled
         chain reproduces ddim_sample_loop bit for bit), else schedule.dither_phase(t) - never the engine's history."""
-        if src_feat is not None or not (tv is True) or not iter:
-            raise NotImplementedError("only the src_feat=None, tv=True, iter=True path is live (admin/local.py:27-29)")
+        if src_feat is not None or not (tv is True):
+            raise NotImplementedError("only the src_feat=None, tv=True path is live (admin/local.py:27-29)")
         n, _, g, _ = x.shape
         t0 = float(t[0])
         if not bool((t.float() == t0).all()):
@@ -124,7 +124,7 @@ class DvdDenoiser(nn.Module):
         f32 = lambda a: a.to(x.device, torch.float32).contiguous()  # noqa: E731
         eng.prepare(f32(y512), f32(mask_cat), f32(mask_y512), f32(line_msk))
         flow = f32(init_flow) if init_flow is not None else torch.zeros_like(x)
-        if t0 > 600 or (n > 1 and t0 == 2.0):
+        if iter == True and (t0 > 600 or (n > 1 and t0 == 2.0)):  # noqa: E712  (both replacements of init_feat need iter == True, :597-601)
             fmode, feat_in = 1, None
         elif init_feat is None:
             fmode, feat_in = 0, None

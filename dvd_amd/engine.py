@@ -162,6 +162,15 @@ class Engine:
             self._io = {"img": [mk(), mk()], "x0": [mk(), mk()], "flow0": mk()}
         return self._io
 
+    def io_feat0(self):
+        """Persistent init_feat [n,256,G,G] of a roll-out without feedback (sampler.sample(iterate=False)) with a non-zero
+        init_feat; made on first use and then kept for the life of the engine: n * 256 * G * G * 4 bytes, 1.36 GB at
+        n = 16, G = 288.  An all-zero init_feat (the evaluation path's) never gets here."""
+        io = self.io_buffers()
+        if "feat0" not in io:
+            io["feat0"] = torch.empty((self.n, 256, self.grid, self.grid), dtype=torch.float32, device=self.device)
+        return io["feat0"]
+
     def set_option(self, name: str, value: int):
         lib.call("dvd_engine_set_option", self._h, name.encode(), int(value))
 

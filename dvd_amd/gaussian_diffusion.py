@@ -103,11 +103,13 @@ class GaussianDiffusion:
                          time_variant=False, pyramid=None, sampler_kind="ddim"):
         """Same call as idf/gaussian_diffusion.py:494-534.  `shape` is (B, 2, G, G): B = 1 in the reference
         (one document per call); B > 1 samples B documents x n_batch hypotheses in one engine batch
-        (model_kwargs tensors then carry B rows).  Returns (sample [B,2,G,G], final dict)."""
-        if clip_denoised or denoised_fn is not None:
-            raise NotImplementedError("clip_denoised / denoised_fn are off on the DvD path (admin/local.py:65)")
-        if not time_variant or not model_kwargs.get("iter", True):
-            raise NotImplementedError("only the live time_variant=True / iter=True configuration is mirrored")
+        (model_kwargs tensors then carry B rows).  Returns (sample [B,2,G,G], final dict).
+        clip_denoised / denoised_fn are process_xstart (:380-385) at every step: see sampler.sample.
+        model_kwargs['iter'] other than True is the loop's second branch (:579-594): no feedback of the prediction."""
+        if not time_variant:
+            raise NotImplementedError("time_variant=False is a different network (three streams, d = 1152): only "
+                                      "time_variant=True is mirrored")
+        iterate = bool(model_kwargs.get("iter", True) == True)  # noqa: E712  (the reference's `iter_flag != True`, :579)
         B, C, G, G2 = shape
         assert C == 2 and G == G2
         dev = device or next(model.parameters()).device
@@ -124,19 +126,24 @@ class GaussianDiffusion:
         if sampler_kind == "ddpm" or eta != 0.0:
             noise_fn = lambda i: th.randn((B * n_batch, 2, G, G), device=dev)  # noqa: E731
         sample = sampler.sample(eng, self.tables, x_T, sampler=sampler_kind, eta=eta, noise_fn=noise_fn,
-                                **self._first_step_kwargs(kw, n_batch))
+                                clip_denoised=bool(clip_denoised), denoised_fn=denoised_fn, iterate=iterate,
+                                **self._first_step_kwargs(kw, n_batch, every_step=not iterate))
         final = {"sample": sample, "pred_xstart": sample, "feat_dict": eng.feat_nchw()}
         return sample, final
 
-    def _first_step_kwargs(self, kw, n_batch):
+    def _first_step_kwargs(self, kw, n_batch, every_step=False):
         """model_kwargs['init_flow'] / ['init_feat'] reach the denoiser at the first step only, tiled over the
         hypotheses like every model_kwarg (idf/gaussian_diffusion.py:574,578; sample index = doc * n_batch + h).
         init_feat is dead while the first step's model time is > 600 (the model overwrites it, idf/cross_model.py:597-598:
-        every schedule with >= 3 steps), so it is only tiled when it can be read."""
+        every schedule with >= 3 steps), so it is only tiled when it can be read.  every_step: the loop without feedback
+        (iter != True) hands both to EVERY step and the model never overwrites init_feat, so it is always read."""
         out = {}
+        if every_step and kw.get("init_feat") is not None and not bool(kw["init_feat"].any()):
+            kw = {k: v for k, v in kw.items() if k != "init_feat"}     # all zero (what run_sample_lr_dewarping passes): feature
+            #                                                           mode 0, decided on the [B,...] tensor before it is tiled
         if kw.get("init_flow") is not None:
             out["init_flow"] = kw["init_flow"].repeat_interleave(n_batch, dim=0)
-        if kw.get("init_feat") is not None and self.tables.model_time(self.num_timesteps - 1) <= 600:
+        if kw.get("init_feat") is not None and (every_step or self.tables.model_time(self.num_timesteps - 1) <= 600):
             out["init_feat"] = kw["init_feat"].repeat_interleave(n_batch, dim=0)
         return out
 
@@ -169,10 +176,12 @@ class GaussianDiffusion:
     def ddim_sample_for_training(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None,
                                  model_kwargs=None, device=None, progress=False, eta=0.0, logger=None, n_batch=1,
                                  time_variant=False, iter=False, mode="train", timestep=None, pyramid=None):
-        if clip_denoised or denoised_fn is not None:
-            raise NotImplementedError("clip_denoised / denoised_fn are off on the DvD path")
-        if not time_variant or not iter:
-            raise NotImplementedError("only the live time_variant=True / iter=True configuration is mirrored")
+        if not time_variant:
+            raise NotImplementedError("time_variant=False is a different network: only time_variant=True is mirrored")
+        if not iter:
+            raise NotImplementedError("iter=False is not mirrored in the training roll-out: this loop feeds the previous "
+                                      "prediction back whatever `iter` says (idf/gaussian_diffusion.py:738-759) and only "
+                                      "the model's init_feat rule changes; ddim_sample_loop has the no-feedback branch")
         if timestep is None or not -1 <= int(timestep) < self.num_timesteps - 1:
             raise ValueError(f"timestep must be in [-1, {self.num_timesteps - 2}]")
         B, C, G, G2 = shape
@@ -190,6 +199,7 @@ class GaussianDiffusion:
         noise_fn = (lambda i: th.randn((B * n_batch, 2, G, G), device=dev)) if eta != 0.0 else None   # noqa: E731
         sample = sampler.sample(eng, self.tables, x_T, eta=eta, noise_fn=noise_fn, mean_hyp=False,
                                 last_step=int(timestep) + 1, t_override=mode is None,
+                                clip_denoised=bool(clip_denoised), denoised_fn=denoised_fn,
                                 **self._first_step_kwargs(kw, n_batch))
         yield {"sample": sample, "pred_xstart": sample, "feat_dict": eng.feat_nchw()}
 
@@ -246,17 +256,26 @@ class GaussianDiffusion:
             return wrapped(x, t.long(), **kw)
         return wrapped(x, self._scale_timesteps(t), **kw)
 
+    def _process_xstart(self, model, x0, clip_denoised, denoised_fn):
+        """process_xstart (idf/gaussian_diffusion.py:380-385) up to the clamp: denoised_fn first; the clamp itself is
+        fused into the scheduler launch, IN PLACE on the tensor returned here.  What a model or a denoised_fn returns may
+        be memory the caller keeps, and the reference's clamp is out of place: the clamp works on a copy (one [N,2,G,G]
+        copy on a single-step call; the loop clamps the engine's own buffer and copies nothing)."""
+        if denoised_fn is not None:
+            x0 = denoised_fn(x0)
+        x0 = x0.float().contiguous()
+        return x0.clone() if clip_denoised else x0
+
     def p_mean_variance(self, model, x, t, clip_denoised=True, denoised_fn=None, model_kwargs=None):
-        """idf/gaussian_diffusion.py:294-415 for the live configuration (START_X, FIXED_LARGE/SMALL, no clipping):
+        """idf/gaussian_diffusion.py:294-415 for the live configuration (START_X, FIXED_LARGE/SMALL):
         {'mean','variance','log_variance','pred_xstart','feat_dict'}; the denoiser runs on the HIP engine, the posterior
-        mean on the fused scheduler kernel."""
-        if clip_denoised or denoised_fn is not None:
-            raise NotImplementedError("clip_denoised / denoised_fn are off on the DvD path")
+        mean - and process_xstart's clamp, so 'mean' and 'pred_xstart' come from one launch - on the fused scheduler kernel."""
         i = self._step_index(t)
         x0, feat = self._call_model(model, x, t, i, model_kwargs)
+        x0 = self._process_xstart(model, x0, clip_denoised, denoised_fn)
         c = self.tables.ddpm_coef(i)
         c.sigma = 0.0                                                  # mean only
-        mean = ops.sched_step(c, x.float().contiguous(), x0)
+        mean = ops.sched_step(c, x.float().contiguous(), x0, clip=bool(clip_denoised))
         if self.model_var_type == ModelVarType.FIXED_LARGE:
             logvar = float(self.tables.fixed_large_log_variance[i])
         else:
@@ -266,14 +285,14 @@ class GaussianDiffusion:
 
     def ddim_sample(self, model, x, t, clip_denoised=True, denoised_fn=None, model_kwargs=None, eta=0.0):
         """One DDIM step with the reference's signature (idf/gaussian_diffusion.py:445-491):
-        {'sample','pred_xstart','feat_dict'}."""
-        if clip_denoised or denoised_fn is not None:
-            raise NotImplementedError("clip_denoised / denoised_fn are off on the DvD path")
+        {'sample','pred_xstart','feat_dict'}; 'pred_xstart' is the processed prediction (denoised_fn, then the clamp)."""
         i = self._step_index(t)
         x0, feat = self._call_model(model, x, t, i, model_kwargs)
+        x0 = self._process_xstart(model, x0, clip_denoised, denoised_fn)
         coef = self.tables.ddim_coef(i, eta)
         noise = th.randn_like(x0) if coef.sigma != 0.0 else None
-        return {"sample": ops.sched_step(coef, x.float().contiguous(), x0, noise), "pred_xstart": x0, "feat_dict": feat}
+        sample = ops.sched_step(coef, x.float().contiguous(), x0, noise, clip=bool(clip_denoised))
+        return {"sample": sample, "pred_xstart": x0, "feat_dict": feat}
 
     # reference-compatible single step (idf/gaussian_diffusion.py:445-491) on an explicit x0 prediction
     def ddim_step(self, x_t, x0, i, eta=0.0, noise=None):

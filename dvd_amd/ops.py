@@ -101,7 +101,9 @@ def ingest_u8(img_hwc: torch.Tensor, swap_rb: bool = False, out_size: int = 512,
     return (y, rgb_out if swap_rb else img_hwc) if want_rgb else y
 
 
-def sched_step(coef: lib.SchedCoef, x_t, x0, noise=None, want_grid=False, out=None):
+def sched_step(coef: lib.SchedCoef, x_t, x0, noise=None, want_grid=False, out=None, clip=False):
+    """clip=True is process_xstart's clamp fused in front (dvd_sched_step_clip): `x0` is clamped to [-1, 1] IN PLACE and
+    the step (and the grid) are computed from the clamped value, in the one launch."""
     _chk(x_t, torch.float32, "x_t")
     _chk(x0, torch.float32, "x0")
     n, _, g, _ = x_t.shape
@@ -113,7 +115,10 @@ def sched_step(coef: lib.SchedCoef, x_t, x0, noise=None, want_grid=False, out=No
     ngrid = torch.empty_like(x_t) if want_grid else None
     if noise is not None:
         _chk(noise, torch.float32, "noise")
-    lib.call("dvd_sched_step", C.byref(coef), ptr(x_t), ptr(x0), ptr(noise), ptr(out), ptr(ngrid), n, g, stream_ptr())
+    if clip and x0.data_ptr() in (x_t.data_ptr(), out.data_ptr(), None if noise is None else noise.data_ptr()):
+        raise lib.DvdError("sched_step(clip=True) updates x0 in place: it must not share memory with x_t, noise or out")
+    lib.call("dvd_sched_step_clip" if clip else "dvd_sched_step", C.byref(coef), ptr(x_t), ptr(x0), ptr(noise), ptr(out),
+             ptr(ngrid), n, g, stream_ptr())
     return (out, ngrid) if want_grid else out
 
 

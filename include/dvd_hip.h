@@ -93,6 +93,13 @@ typedef struct {
 int dvd_sched_step(const dvd_sched_coef* coef, const float* x_t, const float* x0, const float* noise,
                    float* x_prev, float* next_grid, int n, int g, void* stream);
 
+/* The same step behind process_xstart's clamp (idf/gaussian_diffusion.py:380-385, clip_denoised=True), in ONE launch:
+ * x0 is clamped to [-1, 1] IN PLACE with torch.clamp's result bit for bit (NaN stays NaN, -0 stays -0) - so the buffer
+ * the next denoiser evaluation reads as its init_flow holds pred_xstart - and x_prev / next_grid are computed from the
+ * clamped value with dvd_sched_step's arithmetic.  x0 must not alias x_t, noise, x_prev or next_grid. */
+int dvd_sched_step_clip(const dvd_sched_coef* coef, const float* x_t, float* x0, const float* noise,
+                        float* x_prev, float* next_grid, int n, int g, void* stream);
+
 /* mean over the H hypotheses of each document + clamp to [-1,1]
  * (idf/gaussian_diffusion.py:639-640): x0 [docs*H,2,G,G] -> out [docs,2,G,G]. */
 int dvd_hyp_mean_clamp(const float* x0, float* out, int docs, int n_hyp, int g, void* stream);
