@@ -1878,12 +1878,35 @@ extern "C" int dvd_attn_debug_stamps(void* dev_u64) { g_attn_stamps = (unsigned 
 // takes the same kernel, and the same online-softmax tile order, alone or in a batch (bit-identical results).
 static constexpr int R64_MIN_TQ = 5376;
 
+// One of the six product kernels: name as rocprofv3 prints it, entry point, query rows per workgroup, dynamic LDS bytes.
+struct AttnKernel {
+  const char* name;
+  void (*fn)(AttnArgs);
+  int rows, lds;
+};
+constexpr int GLDS256_LDS = 2 * (64 * 512 + 256 * 128), GLDS64_LDS = 2 * (64 * 128 + 64 * 128);
+
+// THE choice of kernel (head_dim 64 or 256): the name, the LDS set-up and the launch all come from here.
+//   fast: tk % 64 == 0 - the LDS-DMA kernels stream whole 64-key tiles; ragged key counts take the register-staged kernel
+//         (masked tail)
+//   r64:  tq >= R64_MIN_TQ - 64 query rows per wave (256 per workgroup): the generated kernels r64x / h64x
+static AttnKernel attn_kernel(int head_dim, bool fast, bool r64) {
+  const bool d256 = head_dim == 256;
+  if (fast && d256 && !r64) return {"flash_attn_glds_kernel<256, 0>", flash_attn_glds_kernel<256, 0>, 128, GLDS256_LDS};
+  if (fast && d256) return {"flash_attn_r64x_kernel<0>", flash_attn_r64x_kernel<0>, 256, r64p::LDS_BYTES};
+  if (fast && r64) return {"flash_attn_h64x_kernel<0, true>", flash_attn_h64x_kernel<0, true>, 256, h64m::LDS_BYTES};
+  if (d256) return {"flash_attn_kernel<256>", flash_attn_kernel<256>, 128, 2 * (64 * (2 * 256 + 16) + 256 * (2 * 64 + 16))};
+  if (fast) return {"flash_attn_glds_kernel<64, 0>", flash_attn_glds_kernel<64, 0>, 128, GLDS64_LDS};
+  return {"flash_attn_kernel<64>", flash_attn_kernel<64>, 128, 2 * (64 * (2 * 64 + 16) + 64 * (2 * 64 + 16))};
+}
+static bool attn_fast(int tk) { return tk % 64 == 0; }
+static bool attn_r64(int tq) { return tq >= R64_MIN_TQ; }
+static AttnKernel attn_select(int head_dim, int tq, int tk) { return attn_kernel(head_dim, attn_fast(tk), attn_r64(tq)); }
+
 extern "C" const char* dvd_flash_attn_kernel_name(int head_dim, int tq, int tk) {
   if (head_dim == 32) return "flash_attn_f32_hd32_kernel";     // f32 operands: dvd_flash_attn_f32 (geotr.hip)
   if (head_dim != 64 && head_dim != 256) return "";
-  if (tk % 64 != 0) return head_dim == 256 ? "flash_attn_kernel<256>" : "flash_attn_kernel<64>";
-  if (head_dim == 256) return tq >= R64_MIN_TQ ? "flash_attn_r64x_kernel<0>" : "flash_attn_glds_kernel<256, 0>";
-  return tq >= R64_MIN_TQ ? "flash_attn_h64x_kernel<0, true>" : "flash_attn_glds_kernel<64, 0>";
+  return attn_select(head_dim, tq, tk).name;
 }
 
 template <typename KernelT>
@@ -1914,19 +1937,19 @@ extern "C" int dvd_flash_attn(const dvd_attn_desc* d, void* stream) {
   const long nwg = (long)p.nqb * d->heads * d->batch;
   DVD_REQUIRE(nwg < (1l << 31), "flash_attn: grid too large");
   hipStream_t st = (hipStream_t)stream;
-  bool fast = d->tk % 64 == 0;      // the LDS-DMA kernels stream whole 64-key tiles; ragged key counts take the
-                                    // register-staged kernel (masked tail)
-  bool r64 = d->tq >= R64_MIN_TQ;      // 64 query rows per wave (256 per workgroup): the generated kernels r64x / h64x
+  bool fast = attn_fast(d->tk), r64 = attn_r64(d->tq);   // attn_select()'s two predicates (a lab build may override them)
   // hipFuncSetAttribute is per DEVICE: remember which devices have been set up (one bit each), lock-free - the
   // attribute call is idempotent, so two threads racing on a device's first launch both set it and both are right
   static DeviceOnce attr_done;
   const unsigned long long dev_bit = DeviceOnce::current_bit();
   const bool first_on_device = attr_done.need(dev_bit);
   if (first_on_device) {
-    allow_lds(flash_attn_glds_kernel<256, 0>, 2 * (64 * 512 + 256 * 128));
-    allow_lds(flash_attn_r64x_kernel<0>, r64p::LDS_BYTES);
-    allow_lds(flash_attn_h64x_kernel<0, true>, h64m::LDS_BYTES);
-    allow_lds(flash_attn_kernel<256>, 2 * (64 * (2 * 256 + 16) + 256 * (2 * 64 + 16)));
+    for (int hd : {256, 64})
+      for (bool f : {false, true})
+        for (bool r : {false, true}) {
+          const AttnKernel k = attn_kernel(hd, f, r);
+          allow_lds(k.fn, k.lds);
+        }
     attr_done.done(dev_bit);
   }
 #ifdef DVD_LAB
@@ -1940,7 +1963,7 @@ extern "C" int dvd_flash_attn(const dvd_attn_desc* d, void* stream) {
     r64 = true;
   if (getenv("DVD_ATTN_R32") || getenv("DVD_ATTN_PIPE") || getenv("DVD_ATTN_GLDS64") || bulk) r64 = false;
   if (first_on_device) {
-    constexpr int LDS = 2 * (64 * 512 + 256 * 128);
+    constexpr int LDS = GLDS256_LDS;
     allow_lds(flash_attn_dsplit_kernel, LDS);
     allow_lds(flash_attn_glds_kernel<256, 1>, LDS);
     allow_lds(flash_attn_glds_kernel<256, 2>, LDS);
@@ -1964,7 +1987,7 @@ extern "C" int dvd_flash_attn(const dvd_attn_desc* d, void* stream) {
     allow_lds(flash_attn_r64m_kernel<7>, r64p::LDS_BYTES);
   }
   if (fast && d->head_dim == 256) {
-    constexpr int LDS = 2 * (64 * 512 + 256 * 128);
+    constexpr int LDS = GLDS256_LDS;
     if (getenv("DVD_ATTN_DSPLIT")) {   // measured slower (732 vs 812 TF/s)
       flash_attn_dsplit_kernel<<<(unsigned)nwg, 512, LDS, st>>>(p);
       return check_launch("flash_attn(lab dsplit)");
@@ -2025,7 +2048,7 @@ extern "C" int dvd_flash_attn(const dvd_attn_desc* d, void* stream) {
       return check_launch("flash_attn(lab glds variant)");
     }
   } else if (fast) {
-    constexpr int LDS = 2 * (64 * 128 + 64 * 128);
+    constexpr int LDS = GLDS64_LDS;
     if (getenv("DVD_ATTN_H64X") || (r64 && (getenv("DVD_ATTN_H64X_ABL") || getenv("DVD_ATTN_H64X_NOLM")))) {   // the production kernel forced at any size; _ABL: ablations
       p.nqb = cdiv(d->tq, 256);
       const unsigned g = (unsigned)((long)p.nqb * d->heads * d->batch);
@@ -2071,20 +2094,8 @@ extern "C" int dvd_flash_attn(const dvd_attn_desc* d, void* stream) {
   }
 #endif
   // ---- product dispatch: six kernels, chosen by (head_dim, tq, tk) ----
-  if (fast && r64 && d->head_dim == 256) {
-    p.nqb = cdiv(d->tq, 256);
-    flash_attn_r64x_kernel<0><<<(unsigned)((long)p.nqb * d->heads * d->batch), 256, r64p::LDS_BYTES, st>>>(p);
-  } else if (fast && d->head_dim == 256) {
-    flash_attn_glds_kernel<256, 0><<<(unsigned)nwg, 256, 2 * (64 * 512 + 256 * 128), st>>>(p);
-  } else if (fast && r64) {            // head_dim 64 at production sizes: the generated 16x16x32 loop, 256-row workgroups
-    p.nqb = cdiv(d->tq, 256);
-    flash_attn_h64x_kernel<0, true><<<(unsigned)((long)p.nqb * d->heads * d->batch), 256, h64m::LDS_BYTES, st>>>(p);
-  } else if (fast) {
-    flash_attn_glds_kernel<64, 0><<<(unsigned)nwg, 256, 2 * (64 * 128 + 64 * 128), st>>>(p);
-  } else if (d->head_dim == 256) {
-    flash_attn_kernel<256><<<(unsigned)nwg, 256, 2 * (64 * (2 * 256 + 16) + 256 * (2 * 64 + 16)), st>>>(p);
-  } else {
-    flash_attn_kernel<64><<<(unsigned)nwg, 256, 2 * (64 * (2 * 64 + 16) + 64 * (2 * 64 + 16)), st>>>(p);
-  }
+  const AttnKernel k = attn_kernel(d->head_dim, fast, r64);
+  p.nqb = cdiv(d->tq, k.rows);
+  k.fn<<<(unsigned)((long)p.nqb * d->heads * d->batch), 256, k.lds, st>>>(p);
   return check_launch("flash_attn");
 }

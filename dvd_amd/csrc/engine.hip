@@ -45,6 +45,7 @@ namespace dvd {
 
 constexpr int HID = 384, DEC = 1536, FFN = 2048, RK = 1088 /* 4*258 = 1032 padded to 64 */;
 constexpr int COLCHUNKS = 64;
+constexpr int DEC_LAYERS = 6, PYR_LAYERS = 7;
 
 struct TensorSpec {
   std::string name;
@@ -57,85 +58,102 @@ static const int PYR_CIN[7] = {4, 64, 64, 128, 128, 256, 256};
 static const int PYR_COUT[7] = {64, 64, 128, 128, 256, 256, 256};
 static inline int pyr_kpad(int i) { return ((9 * PYR_CIN[i] + 63) / 64) * 64; }
 
+// THE weight table, in the order dvd_engine_tensor_info exposes: the head, six decoder layers ("d<j>_" + name), the tail,
+// seven pyramid layers ("pyr<i>_" + name).  F(name, elements) is an f32 tensor.  H(name, elements, wide) is an f16 weight
+// and comes as a (hi, lo) pair, name and name_lo: W = hi + lo, lo unscaled  (see dvd_gemm_desc.B_lo).  `wide`: its GEMM has
+// N % 256 == 0 (B-side weights: N = output features; A-side V^T projections: N = tokens) and runs ONE pass on a dithered
+// copy on large grids.  The DiT block's 384-wide GEMMs keep the (hi, lo) pair: measured (round 3), dithering them too
+// saves 0.3 % of the step (they are memory-bound) and costs 8-35 % more roll-out error.
+// The element counts see T = tokens, side = G / 2 and, in the pyramid, the layer i.
+#define DVD_W_HEAD(F, H)                                                                                           \
+  F(obs_w, HID * 8) F(obs_b, HID) F(pos, T * HID)                                                                  \
+  H(r_w16, (long)HID * RK, false) F(r_b, HID)                                                                      \
+  F(c_w, (long)HID * 1024) F(c_b, HID) F(m_w, (long)HID * 1536) F(m_b, HID) F(l_w, (long)HID * 256) F(l_b, HID)    \
+  F(t_w0, HID * 256) F(t_b0, HID) F(t_w2, HID * HID) F(t_b2, HID) F(ada_w, 6 * HID * HID) F(ada_b, 6 * HID)        \
+  H(ca_wq16, HID * HID, false) F(ca_bq, HID) H(ca_wk16, HID * HID, false) F(ca_bk, HID)                            \
+  H(ca_wv16, HID * HID, true) F(ca_bv, HID) F(ca_wk32, HID * HID) F(ca_wv32, HID * HID)                            \
+  H(ca_wo16, HID * HID, false) F(ca_bo, HID)                                                                       \
+  H(sa_wqk16, 2 * HID * HID, true) F(sa_bqk, 2 * HID) H(sa_wv16, HID * HID, true) F(sa_bv, HID)                    \
+  H(sa_wp16, HID * HID, false) F(sa_bp, HID)                                                                       \
+  H(fc1_w16, 4 * HID * HID, true) F(fc1_b, 4 * HID) H(fc2_w16, 4 * HID * HID, false) F(fc2_b, HID)                 \
+  F(pe_h0_w, (long)DEC * DEC) F(pe_h0_b, DEC) F(pe_h2_w, (long)DEC * DEC) F(pe_h2_b, DEC)                          \
+  F(pe_w0_w, (long)DEC * DEC) F(pe_w0_b, DEC) F(pe_w2_w, (long)DEC * DEC) F(pe_w2_b, DEC)                          \
+  F(pe_htab, side * DEC) F(pe_wtab, side * DEC)
+#define DVD_W_DEC(F, H)                                                                                            \
+  F(n1w, DEC) F(n1b, DEC)                                                                                          \
+  H(wqk16, 2L * DEC * DEC, true) H(wv16, (long)DEC * DEC, true) H(wfc16, (long)DEC * DEC, true)                    \
+  F(n2w, DEC) F(n2b, DEC) H(c1w16, (long)FFN * DEC, true) F(c1b, FFN) F(dww, 9 * FFN) F(dwb, FFN)                  \
+  H(c2w16, (long)DEC * FFN, true) F(c2b, DEC)
+#define DVD_W_TAIL(F, H)                                                                                           \
+  F(dec_nw, DEC) F(dec_nb, DEC) F(fin_ada_w, 2L * DEC * DEC) F(fin_ada_b, 2 * DEC) F(fin_w, 8 * DEC) F(fin_b, 8)
+#define DVD_W_PYR(F, H) F(w, (long)PYR_COUT[i] * pyr_kpad(i)) F(b, PYR_COUT[i])
+
+// THE workspace table, in layout order: name, bytes (each rounded up to 256 by plan(), which also defines docs, N, G, T, NT, dith_bytes).
+#define DVD_B_STEP(X)                                                                                              \
+  /* persistent per-document conditioning */                                                                       \
+  X(feat, docs * G * G * 256 * 4)                                                                                  \
+  X(kc16, docs * T * HID * 2) X(km16, docs * T * HID * 2) X(kl16, docs * T * HID * 2)                              \
+  X(vtc16, docs * T * HID * 2) X(vtm16, docs * T * HID * 2) X(vtl16, docs * T * HID * 2)                           \
+  /* small per-step vectors */                                                                                     \
+  X(tbuf, 256) X(th, HID * 4) X(cvec, HID * 4) X(mod, 6 * HID * 4) X(finmod, 2 * DEC * 4)                          \
+  X(pooled, N * DEC * 4) X(petmp, N * DEC * 4) X(hs, N * DEC * 4) X(wsc, N * DEC * 4)                              \
+  X(part, N * COLCHUNKS * DEC * 4)                                                                                 \
+  /* dithered single-f16 copies of the 256-wide GEMMs' weights (persistent: rewritten before every evaluation) */    \
+  X(w16dith, dith_bytes)                                                                                           \
+  /* per-step activations */                                                                                       \
+  X(xtok32, NT * HID * 4) X(xq16, NT * HID * 2) X(arows16, NT * RK * 2) X(rtok16, NT * HID * 2)                    \
+  X(q16, NT * HID * 2) X(kr16, NT * HID * 2) X(vtr16, NT * HID * 2)                                                \
+  X(att16, NT * DEC * 2) X(z, NT * DEC * 4) X(h16, NT * DEC * 2) X(qk16, NT * 2 * DEC * 2)                         \
+  X(vt16, NT * DEC * 2) X(mlp16, NT * 4 * DEC * 2)
+// prepare-time scratch: laid over the per-step activations, from xtok32 on (prepare never overlaps a step)
+#define DVD_B_PREP(X)                                                                                              \
+  X(p_cat4, (size_t)4 * 512 * 512 * 4) X(p_col, (size_t)512 * 512 * 576 * 4) X(p_actA, (size_t)512 * 512 * 64 * 4) \
+  X(p_actB, (size_t)512 * 512 * 64 * 4) X(p_rows, T * 1536 * 4) X(p_tok32, T * HID * 4)
+
+// Every weight tensor and workspace buffer the step touches is addressed by an INDEX that is a compile-time constant
+// generated from the tables: no string is built, hashed or compared on the launch path.
+//   W_<name>: head and tail tensors; W_dec(j, WD_<name>): decoder layer j; W_pyr(i, WP_w | WP_b): pyramid layer i;
+//   an f16 weight's lo part is the next index;  B_<name>: workspace buffers
+#define F(n, e) PFX(n),
+#define H(n, e, wide) PFX(n), PFX(n##_lo),
+#define PFX(n) WD_##n
+enum { DVD_W_DEC(F, H) WD_COUNT };
+#undef PFX
+#define PFX(n) WP_##n
+enum { DVD_W_PYR(F, H) WP_COUNT };
+#undef PFX
+#define PFX(n) W_##n
+enum {
+  DVD_W_HEAD(F, H) W_DEC0, W_DEC_LAST = W_DEC0 + DEC_LAYERS * WD_COUNT - 1,
+  DVD_W_TAIL(F, H) W_PYR0, W_COUNT = W_PYR0 + PYR_LAYERS * WP_COUNT
+};
+#undef PFX
+#undef F
+#undef H
+constexpr int W_dec(int j, int k) { return W_DEC0 + j * WD_COUNT + k; }
+constexpr int W_pyr(int i, int k) { return W_PYR0 + i * WP_COUNT + k; }
+#define X(n, bytes) B_##n,
+enum { DVD_B_STEP(X) DVD_B_PREP(X) B_COUNT };
+#undef X
+
 static std::vector<TensorSpec> tensor_specs(int G) {
   const long T = (long)(G / 2) * (G / 2), side = G / 2;
   std::vector<TensorSpec> v;
-  auto f32 = [&](const std::string& n, long e) { v.push_back({n, 0, e, false}); };
-  // every f16 weight comes as a (hi, lo) pair: W = hi + lo, lo unscaled  (see dvd_gemm_desc.B_lo).  `wide`: its GEMM has
-  // N % 256 == 0 (B-side weights: N = output features; A-side V^T projections: N = tokens) and runs ONE pass on a dithered
-  // copy on large grids.  The DiT block's 384-wide GEMMs keep the (hi, lo) pair: measured (round 3), dithering them too
-  // saves 0.3 % of the step (they are memory-bound) and costs 8-35 % more roll-out error.
-  auto f16 = [&](const std::string& n, long e, bool wide = false) {
-    v.push_back({n, 1, e, wide});
-    v.push_back({n + "_lo", 1, e, false});
-  };
-  f32("obs_w", HID * 8); f32("obs_b", HID); f32("pos", T * HID);
-  f16("r_w16", (long)HID * RK); f32("r_b", HID);
-  f32("c_w", (long)HID * 1024); f32("c_b", HID);
-  f32("m_w", (long)HID * 1536); f32("m_b", HID);
-  f32("l_w", (long)HID * 256); f32("l_b", HID);
-  f32("t_w0", HID * 256); f32("t_b0", HID); f32("t_w2", HID * HID); f32("t_b2", HID);
-  f32("ada_w", 6 * HID * HID); f32("ada_b", 6 * HID);
-  f16("ca_wq16", HID * HID); f32("ca_bq", HID);
-  f16("ca_wk16", HID * HID); f32("ca_bk", HID); f16("ca_wv16", HID * HID, true); f32("ca_bv", HID);
-  f32("ca_wk32", HID * HID); f32("ca_wv32", HID * HID);
-  f16("ca_wo16", HID * HID); f32("ca_bo", HID);
-  f16("sa_wqk16", 2 * HID * HID, true); f32("sa_bqk", 2 * HID); f16("sa_wv16", HID * HID, true); f32("sa_bv", HID);
-  f16("sa_wp16", HID * HID); f32("sa_bp", HID);
-  f16("fc1_w16", 4 * HID * HID, true); f32("fc1_b", 4 * HID); f16("fc2_w16", 4 * HID * HID); f32("fc2_b", HID);
-  for (const char* hw : {"pe_h", "pe_w"}) {
-    f32(std::string(hw) + "0_w", (long)DEC * DEC); f32(std::string(hw) + "0_b", DEC);
-    f32(std::string(hw) + "2_w", (long)DEC * DEC); f32(std::string(hw) + "2_b", DEC);
-  }
-  f32("pe_htab", side * DEC); f32("pe_wtab", side * DEC);
-  for (int j = 0; j < 6; ++j) {
-    const std::string p = "d" + std::to_string(j) + "_";
-    f32(p + "n1w", DEC); f32(p + "n1b", DEC);
-    f16(p + "wqk16", 2L * DEC * DEC, true); f16(p + "wv16", (long)DEC * DEC, true); f16(p + "wfc16", (long)DEC * DEC, true);
-    f32(p + "n2w", DEC); f32(p + "n2b", DEC);
-    f16(p + "c1w16", (long)FFN * DEC, true); f32(p + "c1b", FFN);
-    f32(p + "dww", 9 * FFN); f32(p + "dwb", FFN);
-    f16(p + "c2w16", (long)DEC * FFN, true); f32(p + "c2b", DEC);
-  }
-  f32("dec_nw", DEC); f32("dec_nb", DEC);
-  f32("fin_ada_w", 2L * DEC * DEC); f32("fin_ada_b", 2 * DEC); f32("fin_w", 8 * DEC); f32("fin_b", 8);
-  for (int i = 0; i < 7; ++i) {
-    f32("pyr" + std::to_string(i) + "_w", (long)PYR_COUT[i] * pyr_kpad(i));
-    f32("pyr" + std::to_string(i) + "_b", PYR_COUT[i]);
-  }
+  std::string p;   // name prefix of the part of the table being expanded
+#define F(n, e) v.push_back({p + #n, 0, (long)(e), false});
+#define H(n, e, wide) v.push_back({p + #n, 1, (long)(e), wide}); v.push_back({p + #n "_lo", 1, (long)(e), false});
+  DVD_W_HEAD(F, H)
+  for (int j = 0; j < DEC_LAYERS; ++j) { p = "d" + std::to_string(j) + "_"; DVD_W_DEC(F, H) }
+  p.clear();
+  DVD_W_TAIL(F, H)
+  for (int i = 0; i < PYR_LAYERS; ++i) { p = "pyr" + std::to_string(i) + "_"; DVD_W_PYR(F, H) }
+#undef F
+#undef H
   return v;
 }
 
-// Every weight tensor and workspace buffer the step touches is addressed by an INDEX resolved once, in
-// dvd_engine_create: no string is built, hashed or compared on the launch path.
-#define DVD_W_LIST(X)                                                                                              \
-  X(obs_w) X(obs_b) X(pos) X(r_w16) X(r_b) X(c_w) X(c_b) X(m_w) X(m_b) X(l_w) X(l_b) X(t_w0) X(t_b0) X(t_w2) X(t_b2) \
-  X(ada_w) X(ada_b) X(ca_wq16) X(ca_bq) X(ca_wk16) X(ca_bk) X(ca_wv16) X(ca_bv) X(ca_wk32) X(ca_wv32) X(ca_wo16)   \
-  X(ca_bo) X(sa_wqk16) X(sa_bqk) X(sa_wv16) X(sa_bv) X(sa_wp16) X(sa_bp) X(fc1_w16) X(fc1_b) X(fc2_w16) X(fc2_b)   \
-  X(pe_h0_w) X(pe_h0_b) X(pe_h2_w) X(pe_h2_b) X(pe_w0_w) X(pe_w0_b) X(pe_w2_w) X(pe_w2_b) X(pe_htab) X(pe_wtab)    \
-  X(dec_nw) X(dec_nb) X(fin_ada_w) X(fin_ada_b) X(fin_w) X(fin_b)
-#define DVD_WD_LIST(X) \
-  X(n1w) X(n1b) X(wqk16) X(wv16) X(wfc16) X(n2w) X(n2b) X(c1w16) X(c1b) X(dww) X(dwb) X(c2w16) X(c2b)
-#define DVD_B_LIST(X)                                                                                              \
-  X(feat) X(kc16) X(km16) X(kl16) X(vtc16) X(vtm16) X(vtl16) X(tbuf) X(th) X(cvec) X(mod) X(finmod) X(pooled)      \
-  X(petmp) X(hs) X(wsc) X(part) X(xtok32) X(xq16) X(arows16) X(rtok16) X(q16) X(kr16) X(vtr16) X(att16) X(z) X(h16) \
-  X(qk16) X(vt16) X(mlp16) X(p_cat4) X(p_col) X(p_actA) X(p_actB) X(p_rows) X(p_tok32) X(w16dith)
-
-struct WIdx {
-#define X(n) int n = -1;
-  DVD_W_LIST(X)
-  struct Dec { DVD_WD_LIST(X) } d[6];
-#undef X
-  int pyr_w[7], pyr_b[7];
-};
-struct BIdx {
-#define X(n) int n = -1;
-  DVD_B_LIST(X)
-#undef X
-};
-
 struct Buf {
-  std::string name;
+  const char* name;
   size_t off, bytes;
 };
 
@@ -161,8 +179,6 @@ struct Engine {
   char* ws = nullptr;
   size_t ws_bytes = 0, need_bytes = 0;
   std::vector<Buf> bufs;
-  WIdx wi;
-  BIdx bi;
   bool prepared = false;
   // ---- options (dvd_engine_set_option; fixed for the life of a captured graph) ----
   bool split_weights = true;   // use the lo parts (fp32-grade weights, 2x GEMM MFMAs)
@@ -190,24 +206,21 @@ struct Engine {
   hipStream_t cap_stream = nullptr;
 
   const float* F(int i) const { return (const float*)wptr[i]; }
-  // `wide`: the GEMM that consumes weight i takes the 256-wide kernels (its N is a multiple of 256 on a large grid)
-  bool dithered(int i, bool wide) const { return dither && wide && !small_tiles && dith_off[i] >= 0; }
-  const void* H(int i, bool wide = false) const {
-    return dithered(i, wide) ? (const void*)((const _Float16*)(ws + bufs[bi.w16dith].off) + dith_off[i]) : wptr[i];
-  }
-  const void* L(int i, bool wide = false) const {                      // (hi, lo) pairs are adjacent
-    return (split_weights && !dithered(i, wide)) ? wptr[i + 1] : nullptr;
-  }
-  const void* Lffn(int i, bool wide = false) const { return ffn_lo ? L(i, wide) : nullptr; }
   char* B(int i) const { return ws + bufs[i].off; }
-  int find_w(const std::string& name) const {
-    for (size_t i = 0; i < specs.size(); ++i)
-      if (specs[i].name == name) return (int)i;
-    return -1;
+  float* f32(int i) const { return (float*)B(i); }
+  _Float16* f16(int i) const { return (_Float16*)B(i); }
+  // The (hi, lo) operand of f16 weight i ((hi, lo) pairs are adjacent tensors).  A wide weight (specs[i].wide: its GEMM
+  // takes the 256-wide kernels on a large grid) is dithered iff dither && !small_tiles: its GEMM then reads the
+  // re-rounded copy in w16dith and runs one pass.  Otherwise lo is used iff split_weights - and, for the decoder FFN's
+  // two convolutions (`ffn`), ffn_lo.
+  struct Pair { const void *hi, *lo; };
+  Pair W16(int i, bool ffn = false) const {
+    if (dither && !small_tiles && specs[i].wide) return {f16(B_w16dith) + dith_off[i], nullptr};
+    return {wptr[i], split_weights && (ffn_lo || !ffn) ? wptr[i + 1] : nullptr};
   }
-  int find_b(const std::string& name) const {
+  int find_b(const char* name) const {
     for (size_t i = 0; i < bufs.size(); ++i)
-      if (bufs[i].name == name) return (int)i;
+      if (strcmp(bufs[i].name, name) == 0) return (int)i;
     return -1;
   }
   unsigned long graph_clock = 0;
@@ -255,27 +268,6 @@ static int prof_drain_one(Engine* e) {
   return DVD_OK;
 }
 
-static bool resolve_indices(Engine* e) {
-  bool ok = true;
-#define X(n) ok = ok && (e->wi.n = e->find_w(#n)) >= 0;
-  DVD_W_LIST(X)
-#undef X
-  for (int j = 0; j < 6; ++j) {
-    const std::string p = "d" + std::to_string(j) + "_";
-#define X(n) ok = ok && (e->wi.d[j].n = e->find_w(p + #n)) >= 0;
-    DVD_WD_LIST(X)
-#undef X
-  }
-  for (int i = 0; i < 7; ++i) {
-    ok = ok && (e->wi.pyr_w[i] = e->find_w("pyr" + std::to_string(i) + "_w")) >= 0;
-    ok = ok && (e->wi.pyr_b[i] = e->find_w("pyr" + std::to_string(i) + "_b")) >= 0;
-  }
-#define X(n) ok = ok && (e->bi.n = e->find_b(#n)) >= 0;
-  DVD_B_LIST(X)
-#undef X
-  return ok;
-}
-
 static void plan(Engine* e) {
   size_t off = 0;
   auto add = [&](const char* n, size_t bytes) {
@@ -284,14 +276,7 @@ static void plan(Engine* e) {
     off += bytes;
   };
   const size_t T = e->T, NT = e->NT, docs = e->docs, N = e->N, G = e->G;
-  // persistent per-document conditioning
-  add("feat", docs * G * G * 256 * 4);
-  for (const char* s : {"kc16", "km16", "kl16", "vtc16", "vtm16", "vtl16"}) add(s, docs * T * HID * 2);
-  // small per-step vectors
-  add("tbuf", 256); add("th", HID * 4); add("cvec", HID * 4); add("mod", 6 * HID * 4); add("finmod", 2 * DEC * 4);
-  add("pooled", N * DEC * 4); add("petmp", N * DEC * 4); add("hs", N * DEC * 4); add("wsc", N * DEC * 4);
-  add("part", N * COLCHUNKS * DEC * 4);
-  // dithered single-f16 copies of the weights of the 256-wide GEMMs (persistent: rewritten before every evaluation)
+  // every wide weight's dithered copy: its element offset inside w16dith
   e->dith_off.assign(e->specs.size(), -1);
   e->dith_list.clear();
   e->dith_total = 0;
@@ -301,63 +286,65 @@ static void plan(Engine* e) {
     e->dith_list.push_back((int)i);
     e->dith_total += (e->specs[i].nelem + 127) / 128 * 128;
   }
-  add("w16dith", (size_t)e->dith_total * 2);
-  const size_t scratch0 = off;
-  // per-step activations
-  add("xtok32", NT * HID * 4); add("xq16", NT * HID * 2); add("arows16", NT * RK * 2); add("rtok16", NT * HID * 2);
-  add("q16", NT * HID * 2); add("kr16", NT * HID * 2); add("vtr16", NT * HID * 2);
-  add("att16", NT * DEC * 2); add("z", NT * DEC * 4); add("h16", NT * DEC * 2); add("qk16", NT * 2 * DEC * 2);
-  add("vt16", NT * DEC * 2); add("mlp16", NT * 4 * DEC * 2);
+  const size_t dith_bytes = (size_t)e->dith_total * 2;
+#define X(n, bytes) add(#n, bytes);
+  DVD_B_STEP(X)
   const size_t step_end = off;
-  // prepare-time scratch aliases the per-step region (prepare never overlaps a step)
-  off = scratch0;
-  add("p_cat4", (size_t)4 * 512 * 512 * 4);
-  add("p_col", (size_t)512 * 512 * 576 * 4);
-  add("p_actA", (size_t)512 * 512 * 64 * 4);
-  add("p_actB", (size_t)512 * 512 * 64 * 4);
-  add("p_rows", T * 1536 * 4);
-  add("p_tok32", T * HID * 4);
+  off = e->bufs[B_xtok32].off;
+  DVD_B_PREP(X)
+#undef X
   e->need_bytes = off > step_end ? off : step_end;
 }
 
-static int gemm(int dtype, int M, int N, int K, int batch, const void* A, int lda, long sA, const void* Bm, int ldb,
-                long sB, float* C32, int ldc, long sC32, void* C16, int ldc16, long sC16, const float* bias,
-                int bias_row, int act, const float* pos, int pos_rows, const float* gate, int gate_rows,
-                const float* res, int ldres, long sRes, void* stream, const void* Alo = nullptr,
-                const void* Blo = nullptr) {
+// One engine GEMM / attention launch: the public descriptor, zeroed, filled by the constructor (problem) and by chained
+// setters (operands as pointer, leading dimension, batch stride in elements); what a call site does not name stays null / 0.
+// Lives on the caller's stack.
+constexpr int GELU = 1, RELU = 2;
+struct Gemm : dvd_gemm_desc {
+  // dtype: 0 f16 operands, 1 f32, and the engine's codes 2 = f16 on 128x128 tiles (small grids), 3 = the same family, many
+  // rows (dvd_gemm_desc.small_tiles 1 and 2)
+  Gemm(int dtype_, int M_, int N_, int K_, int batch_ = 1) {
+    memset(static_cast<dvd_gemm_desc*>(this), 0, sizeof(dvd_gemm_desc));
+    dtype = dtype_ == 1 ? 1 : 0; small_tiles = dtype_ == 2 ? 1 : dtype_ == 3 ? 2 : 0;
+    M = M_; N = N_; K = K_; batch = batch_;
+    lo_scale = 1.f; ldpos = N_; ldgate = N_;
+  }
+  Gemm& a(const void* p, int ld, long stride = 0) { A = p; lda = ld; strideA = stride; return *this; }
+  Gemm& b(const void* p, int ld, long stride = 0) { B = p; ldb = ld; strideB = stride; return *this; }
+  Gemm& a(Engine::Pair w, int ld) { A_lo = w.lo; return a(w.hi, ld); }                 // a weight on the A side
+  Gemm& b(Engine::Pair w, int ld) { B_lo = w.lo; return b(w.hi, ld); }
+  Gemm& out32(float* p, int ld, long stride = 0) { C32 = p; ldc = ld; strideC32 = stride; return *this; }
+  Gemm& out16(void* p, int ld, long stride = 0) { C16 = p; ldc16 = ld; strideC16 = stride; return *this; }
+  Gemm& bias_col(const float* p) { bias = p; bias_row = 0; return *this; }               // bias[col]
+  Gemm& bias_rows(const float* p) { bias = p; bias_row = 1; return *this; }              // bias[row]
+  Gemm& act_fn(int f) { act = f; return *this; }
+  Gemm& add_pos(const float* p, int rows) { pos = p; pos_rows = rows; return *this; }     // + pos[row % rows][col]
+  Gemm& mul_gate(const float* p, int rows) { gate = p; gate_rows = rows; return *this; }  // * gate[row / rows][col]
+  Gemm& add_res(const float* p, int ld, long stride = 0) { res = p; ldres = ld; strideRes = stride; return *this; }
+};
+
+static int gemm(const Gemm& d, void* stream) {
   // every pointer an engine GEMM gets is 16-byte aligned (256-byte workspace buffers, 16-byte weights, offsets in whole
   // rows): an unaligned output or epilogue operand would move a 384 x 256-tile call site to a kernel with other bits
   // (tests/test_gemm_dispatch.py), so it is an error here rather than a silent change of kernel
   auto a16 = [](const void* q) { return ((uintptr_t)q % 16) == 0; };
-  DVD_REQUIRE(a16(C32) && a16(C16) && a16(bias) && a16(pos) && a16(gate) && a16(res),
+  DVD_REQUIRE(a16(d.C32) && a16(d.C16) && a16(d.bias) && a16(d.pos) && a16(d.gate) && a16(d.res),
               "engine gemm: output / epilogue pointers must be 16-byte aligned");
-  dvd_gemm_desc d;
-  memset(&d, 0, sizeof(d));
-  d.A_lo = Alo; d.B_lo = Blo; d.lo_scale = 1.f;
-  d.dtype = dtype; d.M = M; d.N = N; d.K = K; d.batch = batch;
-  d.A = A; d.lda = lda; d.strideA = sA;
-  d.B = Bm; d.ldb = ldb; d.strideB = sB;
-  d.C32 = C32; d.ldc = ldc; d.strideC32 = sC32;
-  d.C16 = C16; d.ldc16 = ldc16; d.strideC16 = sC16;
-  d.bias = bias; d.bias_row = bias_row; d.act = act;
-  d.pos = pos; d.ldpos = N; d.pos_rows = pos_rows;
-  d.gate = gate; d.ldgate = N; d.gate_rows = gate_rows;
-  d.res = res; d.ldres = ldres; d.strideRes = sRes;
-  if (dtype == 2) { d.dtype = 0; d.small_tiles = 1; }     // dtype 2 = f16 operands on 128x128 tiles (small grids)
-  if (dtype == 3) { d.dtype = 0; d.small_tiles = 2; }     // dtype 3 = the same family, many rows (see dvd_gemm_desc)
   return dvd_gemm_nt(&d, stream);
 }
 
-static int attn(int hd, int heads, int batch, int tq, int tk, int kv_div, const void* Q, int ldq, long sQ,
-                const void* K, int ldk, long sK, const void* Vt, int ldvt, long sVt, void* O, int ldo, long sO,
-                float scale, void* stream) {
-  dvd_attn_desc d;
-  memset(&d, 0, sizeof(d));
-  d.head_dim = hd; d.heads = heads; d.batch = batch; d.tq = tq; d.tk = tk; d.kv_batch_div = kv_div;
-  d.Q = Q; d.ldq = ldq; d.strideQ = sQ; d.K = K; d.ldk = ldk; d.strideK = sK;
-  d.Vt = Vt; d.ldvt = ldvt; d.strideVt = sVt; d.O = O; d.ldo = ldo; d.strideO = sO; d.scale = scale;
-  return dvd_flash_attn(&d, stream);
-}
+struct Attn : dvd_attn_desc {
+  Attn(int hd, int heads_, int batch_, int tq_, int tk_, int kv_div, float scale_) {
+    memset(static_cast<dvd_attn_desc*>(this), 0, sizeof(dvd_attn_desc));
+    head_dim = hd; heads = heads_; batch = batch_; tq = tq_; tk = tk_; kv_batch_div = kv_div; scale = scale_;
+  }
+  Attn& q(const void* p, int ld, long stride) { Q = p; ldq = ld; strideQ = stride; return *this; }
+  Attn& k(const void* p, int ld, long stride) { K = p; ldk = ld; strideK = stride; return *this; }
+  Attn& vt(const void* p, int ld, long stride) { Vt = p; ldvt = ld; strideVt = stride; return *this; }
+  Attn& out(void* p, int ld, long stride) { O = p; ldo = ld; strideO = stride; return *this; }
+};
+
+static int attn(const Attn& d, void* stream) { return dvd_flash_attn(&d, stream); }
 
 __global__ void set_scalar_kernel(float* p, float v) { *p = v; }
 
@@ -386,9 +373,9 @@ extern "C" int dvd_engine_create(int grid, int docs, int n_hyp, void** handle) {
   // Decided from the GRID only (never the batch): a document gets the same kernels alone or in a batch.
   e->small_tiles = e->T <= 1024;
   e->dither = !e->small_tiles;
-  if (!resolve_indices(e)) {
+  if (e->specs.size() != (size_t)W_COUNT || e->bufs.size() != (size_t)B_COUNT) {   // the enumerators index these vectors
     delete e;
-    set_error("engine_create: internal tensor/buffer table mismatch");
+    set_error("engine_create: the index enumerators and the expanded tables differ in length");
     return DVD_E_STATE;
   }
   *handle = e;
@@ -518,11 +505,8 @@ extern "C" int dvd_engine_prepare_docs(void* handle, const float* y512, const fl
   hipStream_t st = (hipStream_t)stream;
   const int G = e->G;
   const long T = e->T;
-  float* cat4 = (float*)e->B(e->bi.p_cat4);
-  float* col = (float*)e->B(e->bi.p_col);
-  float* actA = (float*)e->B(e->bi.p_actA);
-  float* actB = (float*)e->B(e->bi.p_actB);
-  const float* pos = e->F(e->wi.pos);
+  float *cat4 = e->f32(B_p_cat4), *col = e->f32(B_p_col);
+  const float* pos = e->F(W_pos);
   for (int d = 0; d < e->docs; ++d) {
     // cat([y512, mask_cat], dim=1)  (:586-587)
     if (hipMemcpyAsync(cat4, y512 + (size_t)d * 3 * 512 * 512, (size_t)3 * 512 * 512 * 4, hipMemcpyDeviceToDevice, st) != hipSuccess ||
@@ -536,21 +520,20 @@ extern "C" int dvd_engine_prepare_docs(void* handle, const float* y512, const fl
                          {4, 128, false}, {5, 128, false}, {6, 128, true}};
     const float* cur = cat4;
     long sc = 512L * 512, sy = 512, sx = 1;   // first layer reads the planar input
-    float* act[2] = {actA, actB};
+    float* act[2] = {e->f32(B_p_actA), e->f32(B_p_actB)};
     int wi = 0;
     for (const L& l : layers) {
       const int cin = PYR_CIN[l.idx], cout = PYR_COUT[l.idx], kp = pyr_kpad(l.idx);
+      const float *w = e->F(W_pyr(l.idx, WP_w)), *b = e->F(W_pyr(l.idx, WP_b));
       float* outp = act[wi];
       wi ^= 1;
       if (sc == 1 && cin % 16 == 0 && kp == 9 * cin) {
         // every layer but the first (4 planar input channels): implicit GEMM with the arithmetic - and the bits - of the
         // im2col + GEMM pair it replaces (level_1's second conv alone wrote and read a 604 MB matrix)
-        TRY(dvd_conv3x3_nhwc(cur, cin, e->F(e->wi.pyr_w[l.idx]), kp, e->F(e->wi.pyr_b[l.idx]), outp, cout, l.hw, l.hw,
-                                    1, stream));
+        TRY(dvd_conv3x3_nhwc(cur, cin, w, kp, b, outp, cout, l.hw, l.hw, 1, stream));
       } else {
         TRY(dvd_im2col3x3(cur, sc, sy, sx, col, kp, cin, l.hw, l.hw, stream));
-        TRY(gemm(1, l.hw * l.hw, cout, kp, 1, col, kp, 0, e->F(e->wi.pyr_w[l.idx]), kp, 0, outp, cout, 0, nullptr, 0, 0,
-                 e->F(e->wi.pyr_b[l.idx]), 0, /*relu*/ 2, nullptr, 0, nullptr, 0, nullptr, 0, 0, stream));
+        TRY(gemm(Gemm(1, l.hw * l.hw, cout, kp).a(col, kp).b(w, kp).out32(outp, cout).bias_col(b).act_fn(RELU), stream));
       }
       int hw = l.hw;
       if (l.pool) {
@@ -563,7 +546,7 @@ extern "C" int dvd_engine_prepare_docs(void* handle, const float* y512, const fl
       sc = 1; sy = (long)hw * cout; sx = cout;
     }
     // cur = level_3 output [64,64,256]; resize to the coordinate grid (:590-593 generalised)
-    float* feat = (float*)e->B(e->bi.feat) + (size_t)d * G * G * 256;
+    float* feat = e->f32(B_feat) + (size_t)d * G * G * 256;
     if (G == 64) {
       if (hipMemcpyAsync(feat, cur, (size_t)64 * 64 * 256 * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) {
         set_error("engine_prepare_docs: device copy failed");
@@ -584,40 +567,38 @@ extern "C" int dvd_engine_prepare_docs(void* handle, const float* y512, const fl
     const size_t per_doc = (size_t)T * (1536 + HID) * 4;
     {   // the grouping below treats the five regions as ONE contiguous scratch - say so where a re-ordered
         // plan() would otherwise underflow `avail` and let rows_g / tok_g run into live buffers
-      const int chain[5] = {e->bi.p_col, e->bi.p_actA, e->bi.p_actB, e->bi.p_rows, e->bi.p_tok32};
+      const int chain[5] = {B_p_col, B_p_actA, B_p_actB, B_p_rows, B_p_tok32};
       for (int i = 0; i + 1 < 5; ++i)
         DVD_REQUIRE(e->bufs[chain[i]].off < e->bufs[chain[i + 1]].off &&
                         e->bufs[chain[i]].off + e->bufs[chain[i]].bytes <= e->bufs[chain[i + 1]].off &&
                         e->bufs[chain[i + 1]].off - (e->bufs[chain[i]].off + e->bufs[chain[i]].bytes) < 4096,
                     "engine_prepare_docs: the prepare-time scratch regions are not laid out back to back (plan() changed?)");
     }
-    const size_t avail = e->bufs[e->bi.p_tok32].off + e->bufs[e->bi.p_tok32].bytes - e->bufs[e->bi.p_col].off;
+    const size_t avail = e->bufs[B_p_tok32].off + e->bufs[B_p_tok32].bytes - e->bufs[B_p_col].off;
     DVD_REQUIRE(avail >= per_doc, "engine_prepare_docs: prepare scratch smaller than one document's rows");
     const int gmax = (int)std::max<size_t>(1, std::min<size_t>((size_t)e->docs, avail / per_doc));
-    const WIdx& wx = e->wi;
-    const BIdx& bx = e->bi;
     for (int d0 = 0; d0 < e->docs; d0 += gmax) {
       const int gd = std::min(gmax, e->docs - d0);
       float* rows_g = col;
       float* tok_g = col + (size_t)gd * T * 1536;
       struct S { const float* src; long sn, sc, sy, sx; int c; int w, b, k16, vt16; };
       const S streams[3] = {
-          {(const float*)e->B(bx.feat) + (size_t)d0 * G * G * 256, (long)G * G * 256, 1, (long)G * 256, 256, 256, wx.c_w, wx.c_b,
-           bx.kc16, bx.vtc16},
-          {mask_y512 + (size_t)d0 * 384 * G * G, 384L * G * G, (long)G * G, G, 1, 384, wx.m_w, wx.m_b, bx.km16, bx.vtm16},
-          {line_msk + (size_t)d0 * 64 * G * G, 64L * G * G, (long)G * G, G, 1, 64, wx.l_w, wx.l_b, bx.kl16, bx.vtl16}};
+          {e->f32(B_feat) + (size_t)d0 * G * G * 256, (long)G * G * 256, 1, (long)G * 256, 256, 256, W_c_w, W_c_b, B_kc16,
+           B_vtc16},
+          {mask_y512 + (size_t)d0 * 384 * G * G, 384L * G * G, (long)G * G, G, 1, 384, W_m_w, W_m_b, B_km16, B_vtm16},
+          {line_msk + (size_t)d0 * 64 * G * G, 64L * G * G, (long)G * G, G, 1, 64, W_l_w, W_l_b, B_kl16, B_vtl16}};
       for (const S& s : streams) {
         const int K4 = 4 * s.c;
         DVD_REQUIRE((long)gd * T < (1l << 31), "engine_prepare_docs: group too large");
         TRY(dvd_patch_rows(s.src, s.sn, s.sc, s.sy, s.sx, rows_g, K4, gd, s.c, G, stream));
-        TRY(gemm(1, (int)(gd * T), HID, K4, 1, rows_g, K4, 0, e->F(s.w), K4, 0, tok_g, HID, 0, nullptr, 0, 0, e->F(s.b), 0, 0,
-                 pos, (int)T, nullptr, 0, nullptr, 0, 0, stream));
-        _Float16* k16 = (_Float16*)e->B(s.k16) + (size_t)d0 * T * HID;
-        _Float16* vt16 = (_Float16*)e->B(s.vt16) + (size_t)d0 * T * HID;
-        TRY(gemm(1, (int)(gd * T), HID, HID, 1, tok_g, HID, 0, e->F(e->wi.ca_wk32), HID, 0, nullptr, 0, 0, k16, HID, 0,
-                 e->F(e->wi.ca_bk), 0, 0, nullptr, 0, nullptr, 0, nullptr, 0, 0, stream));
-        TRY(gemm(1, HID, (int)T, HID, gd, e->F(e->wi.ca_wv32), HID, 0, tok_g, HID, (long)T * HID, nullptr, 0, 0, vt16, (int)T,
-                 (long)T * HID, e->F(e->wi.ca_bv), 1, 0, nullptr, 0, nullptr, 0, nullptr, 0, 0, stream));
+        TRY(gemm(Gemm(1, (int)(gd * T), HID, K4).a(rows_g, K4).b(e->F(s.w), K4).out32(tok_g, HID).bias_col(e->F(s.b))
+                     .add_pos(pos, (int)T), stream));
+        _Float16* k16 = e->f16(s.k16) + (size_t)d0 * T * HID;
+        _Float16* vt16 = e->f16(s.vt16) + (size_t)d0 * T * HID;
+        TRY(gemm(Gemm(1, (int)(gd * T), HID, HID).a(tok_g, HID).b(e->F(W_ca_wk32), HID).out16(k16, HID)
+                     .bias_col(e->F(W_ca_bk)), stream));
+        TRY(gemm(Gemm(1, HID, (int)T, HID, gd).a(e->F(W_ca_wv32), HID).b(tok_g, HID, (long)T * HID)
+                     .out16(vt16, (int)T, (long)T * HID).bias_rows(e->F(W_ca_bv)), stream));
       }
     }
   }
@@ -630,7 +611,7 @@ extern "C" int dvd_engine_feat_nchw(void* handle, float* out, void* stream) {
   Engine* e = (Engine*)handle;
   TRY(require_ready(e, true));
   for (int d = 0; d < e->docs; ++d)
-    TRY(dvd_nhwc_to_nchw((const float*)e->B(e->bi.feat) + (size_t)d * e->G * e->G * 256,
+    TRY(dvd_nhwc_to_nchw(e->f32(B_feat) + (size_t)d * e->G * e->G * 256,
                          out + (size_t)d * 256 * e->G * e->G, 256, e->G, e->G, stream));
   return DVD_OK;
 }
@@ -655,109 +636,90 @@ static int enqueue_step(Engine* e, const float* x_t, int feat_mode, const float*
   const int F16 = e->small_tiles ? (e->NT >= 16384 ? 3 : 2) : 0;
   constexpr int F16S = 2;                     // ... and 128x128 tiles on every grid (a function of the GEMM, not of the batch)
 
-  float* tbuf = (float*)e->B(e->bi.tbuf);
-  float* th = (float*)e->B(e->bi.th);
-  float* cvec = (float*)e->B(e->bi.cvec);
-  float* mod = (float*)e->B(e->bi.mod);
-  float* finmod = (float*)e->B(e->bi.finmod);
-  float* xtok32 = (float*)e->B(e->bi.xtok32);
-  _Float16* xq16 = (_Float16*)e->B(e->bi.xq16);
-  _Float16* arows16 = (_Float16*)e->B(e->bi.arows16);
-  _Float16* rtok16 = (_Float16*)e->B(e->bi.rtok16);
-  _Float16* q16 = (_Float16*)e->B(e->bi.q16);
-  _Float16* kr16 = (_Float16*)e->B(e->bi.kr16);
-  _Float16* vtr16 = (_Float16*)e->B(e->bi.vtr16);
-  _Float16* att16 = (_Float16*)e->B(e->bi.att16);
-  float* z = (float*)e->B(e->bi.z);
-  _Float16* h16 = (_Float16*)e->B(e->bi.h16);
-  _Float16* qk16 = (_Float16*)e->B(e->bi.qk16);
-  _Float16* vt16 = (_Float16*)e->B(e->bi.vt16);
-  _Float16* mlp16 = (_Float16*)e->B(e->bi.mlp16);
+  auto f32 = [e](int i) { return e->f32(i); };      // a workspace buffer by its index, typed
+  auto f16 = [e](int i) { return e->f16(i); };
+  const long TH = (long)T * HID, TD = (long)T * DEC;   // one sample's tokens, elements
 
   // --- timestep embedding and the two adaLN tables (one row: t is batch-global in sampling) ---
-  TRY(dvd_small_linear(tbuf, 1, e->F(e->wi.t_w0), e->F(e->wi.t_b0), th, HID, 1, 256, HID, 256, 2, 1, stream));
-  TRY(dvd_small_linear(th, HID, e->F(e->wi.t_w2), e->F(e->wi.t_b2), cvec, HID, 1, HID, HID, HID, 0, 0, stream));
-  TRY(dvd_small_linear(cvec, HID, e->F(e->wi.ada_w), e->F(e->wi.ada_b), mod, 6 * HID, 1, HID, 6 * HID, HID, 1, 0, stream));
-  TRY(dvd_small_linear(cvec, HID, e->F(e->wi.fin_ada_w), e->F(e->wi.fin_ada_b), finmod, 2 * DEC, 1, DEC, 2 * DEC, HID, 1, 0,
+  TRY(dvd_small_linear(f32(B_tbuf), 1, e->F(W_t_w0), e->F(W_t_b0), f32(B_th), HID, 1, 256, HID, 256, 2, 1, stream));
+  TRY(dvd_small_linear(f32(B_th), HID, e->F(W_t_w2), e->F(W_t_b2), f32(B_cvec), HID, 1, HID, HID, HID, 0, 0, stream));
+  TRY(dvd_small_linear(f32(B_cvec), HID, e->F(W_ada_w), e->F(W_ada_b), f32(B_mod), 6 * HID, 1, HID, 6 * HID, HID, 1, 0,
                        stream));
+  TRY(dvd_small_linear(f32(B_cvec), HID, e->F(W_fin_ada_w), e->F(W_fin_ada_b), f32(B_finmod), 2 * DEC, 1, DEC, 2 * DEC, HID,
+                       1, 0, stream));
+  const float* mod = f32(B_mod);
   const float *sh_a = mod, *sc_a = mod + HID, *g_a = mod + 2 * HID, *sh_m = mod + 3 * HID, *sc_m = mod + 4 * HID,
               *g_m = mod + 5 * HID;
 
   // --- tokens ---
-  TRY(dvd_embed_obs_ln(x_t, e->F(e->wi.obs_w), e->F(e->wi.obs_b), e->F(e->wi.pos), xtok32, xq16, N, G, stream));
-  TRY(dvd_build_r_rows((const float*)e->B(e->bi.feat), init_feat_nchw, init_flow, arows16, RK, N, G, hyp, feat_mode,
-                       stream));
-  TRY(gemm(F16, (int)NT, HID, RK, 1, arows16, RK, 0, e->H(e->wi.r_w16), RK, 0, nullptr, 0, 0, rtok16, HID, 0, e->F(e->wi.r_b), 0,
-           0, e->F(e->wi.pos), T, nullptr, 0, nullptr, 0, 0, stream, nullptr, e->L(e->wi.r_w16)));
+  TRY(dvd_embed_obs_ln(x_t, e->F(W_obs_w), e->F(W_obs_b), e->F(W_pos), f32(B_xtok32), f16(B_xq16), N, G, stream));
+  TRY(dvd_build_r_rows(f32(B_feat), init_feat_nchw, init_flow, f16(B_arows16), RK, N, G, hyp, feat_mode, stream));
+  TRY(gemm(Gemm(F16, (int)NT, HID, RK).a(f16(B_arows16), RK).b(e->W16(W_r_w16), RK).out16(f16(B_rtok16), HID)
+               .bias_col(e->F(W_r_b)).add_pos(e->F(W_pos), T), stream));
 
   // --- parallel cross-attention of the shared query against the 4 streams (:237-265) ---
-  TRY(gemm(F16, (int)NT, HID, HID, 1, xq16, HID, 0, e->H(e->wi.ca_wq16), HID, 0, nullptr, 0, 0, q16, HID, 0, e->F(e->wi.ca_bq),
-           0, 0, nullptr, 0, nullptr, 0, nullptr, 0, 0, stream, nullptr, e->L(e->wi.ca_wq16)));
-  TRY(gemm(F16, (int)NT, HID, HID, 1, rtok16, HID, 0, e->H(e->wi.ca_wk16), HID, 0, nullptr, 0, 0, kr16, HID, 0,
-           e->F(e->wi.ca_bk), 0, 0, nullptr, 0, nullptr, 0, nullptr, 0, 0, stream, nullptr, e->L(e->wi.ca_wk16)));
+  TRY(gemm(Gemm(F16, (int)NT, HID, HID).a(f16(B_xq16), HID).b(e->W16(W_ca_wq16), HID).out16(f16(B_q16), HID)
+               .bias_col(e->F(W_ca_bq)), stream));
+  TRY(gemm(Gemm(F16, (int)NT, HID, HID).a(f16(B_rtok16), HID).b(e->W16(W_ca_wk16), HID).out16(f16(B_kr16), HID)
+               .bias_col(e->F(W_ca_bk)), stream));
   // (the two 384 x T x 384 V^T projections take the 128 x 128 kernel on every grid: K = 384 is six 64-deep slabs and a
   //  token panel is read by two row tiles only, so the 256 x 256 kernel - one workgroup per CU, every slab's loads waited
   //  for at its end - runs them latency-bound: 2.13 vs 0.93 ms and 0.58 vs 0.21 ms at the bench shape, benchmarks/gemm_vt384_time.py)
-  TRY(gemm(F16S, HID, T, HID, N, e->H(e->wi.ca_wv16, true), HID, 0, rtok16, HID, (long)T * HID, nullptr, 0, 0, vtr16, T,
-           (long)HID * T, e->F(e->wi.ca_bv), 1, 0, nullptr, 0, nullptr, 0, nullptr, 0, 0, stream, e->L(e->wi.ca_wv16, true), nullptr));
+  TRY(gemm(Gemm(F16S, HID, T, HID, N).a(e->W16(W_ca_wv16), HID).b(f16(B_rtok16), HID, TH).out16(f16(B_vtr16), T, TH)
+               .bias_rows(e->F(W_ca_bv)), stream));
   {
-    const int kn[3] = {e->bi.kc16, e->bi.km16, e->bi.kl16};
-    const int vn[3] = {e->bi.vtc16, e->bi.vtm16, e->bi.vtl16};
+    // streams cond, msk6, line against the documents' K / V^T (shared by a document's hypotheses), then r
+    const int kn[3] = {B_kc16, B_km16, B_kl16}, vn[3] = {B_vtc16, B_vtm16, B_vtl16};
     for (int s = 0; s < 3; ++s)
-      TRY(attn(64, 6, N, T, T, hyp, q16, HID, (long)T * HID, e->B(kn[s]), HID, (long)T * HID, e->B(vn[s]), T,
-               (long)HID * T, att16 + (size_t)s * NT * HID, HID, (long)T * HID, 0.125f, stream));
-    TRY(attn(64, 6, N, T, T, 1, q16, HID, (long)T * HID, kr16, HID, (long)T * HID, vtr16, T, (long)HID * T,
-             att16 + (size_t)3 * NT * HID, HID, (long)T * HID, 0.125f, stream));
+      TRY(attn(Attn(64, 6, N, T, T, hyp, 0.125f).q(f16(B_q16), HID, TH).k(f16(kn[s]), HID, TH).vt(f16(vn[s]), T, TH)
+                   .out(f16(B_att16) + (size_t)s * NT * HID, HID, TH), stream));
+    TRY(attn(Attn(64, 6, N, T, T, 1, 0.125f).q(f16(B_q16), HID, TH).k(f16(B_kr16), HID, TH).vt(f16(B_vtr16), T, TH)
+                 .out(f16(B_att16) + (size_t)3 * NT * HID, HID, TH), stream));
   }
   // x_s = x + out_proj(attn_s)  -> z[:, 384 s : 384 (s+1)]   (stream order cond, msk6, line, r == cat order :623)
-  TRY(gemm(F16, (int)NT, HID, HID, 4, att16, HID, NT * HID, e->H(e->wi.ca_wo16), HID, 0, z, DEC, HID, nullptr, 0, 0,
-           e->F(e->wi.ca_bo), 0, 0, nullptr, 0, nullptr, 0, xtok32, HID, 0, stream, nullptr, e->L(e->wi.ca_wo16)));
+  TRY(gemm(Gemm(F16, (int)NT, HID, HID, 4).a(f16(B_att16), HID, NT * HID).b(e->W16(W_ca_wo16), HID).out32(f32(B_z), DEC, HID)
+               .bias_col(e->F(W_ca_bo)).add_res(f32(B_xtok32), HID), stream));
 
   if (e->debug_stop == 1) return check_launch("engine_denoise_step(stop 1)");
   // --- per stream: gated self-attention (:268-289) ---
-  TRY(dvd_layernorm_rows(z, DEC, HID, h16, HID, NT * HID, 4, NT, HID, nullptr, nullptr, sh_a, sc_a, 0, (int)NT, 1e-6f,
-                         stream));
-  TRY(gemm(F16, (int)(4 * NT), 2 * HID, HID, 1, h16, HID, 0, e->H(e->wi.sa_wqk16, true), HID, 0, nullptr, 0, 0, qk16, 2 * HID, 0,
-           e->F(e->wi.sa_bqk), 0, 0, nullptr, 0, nullptr, 0, nullptr, 0, 0, stream, nullptr, e->L(e->wi.sa_wqk16, true)));
-  TRY(gemm(F16S, HID, T, HID, 4 * N, e->H(e->wi.sa_wv16, true), HID, 0, h16, HID, (long)T * HID, nullptr, 0, 0, vt16, T,
-           (long)HID * T, e->F(e->wi.sa_bv), 1, 0, nullptr, 0, nullptr, 0, nullptr, 0, 0, stream, e->L(e->wi.sa_wv16, true), nullptr));
-  TRY(attn(64, 6, 4 * N, T, T, 1, qk16, 2 * HID, (long)T * 2 * HID, qk16 + HID, 2 * HID, (long)T * 2 * HID, vt16, T,
-           (long)HID * T, att16, HID, (long)T * HID, 0.125f, stream));
-  TRY(gemm(F16, (int)NT, HID, HID, 4, att16, HID, NT * HID, e->H(e->wi.sa_wp16), HID, 0, z, DEC, HID, nullptr, 0, 0,
-           e->F(e->wi.sa_bp), 0, 0, nullptr, 0, g_a, (int)NT, z, DEC, HID, stream, nullptr, e->L(e->wi.sa_wp16)));
+  TRY(dvd_layernorm_rows(f32(B_z), DEC, HID, f16(B_h16), HID, NT * HID, 4, NT, HID, nullptr, nullptr, sh_a, sc_a, 0, (int)NT,
+                         1e-6f, stream));
+  TRY(gemm(Gemm(F16, (int)(4 * NT), 2 * HID, HID).a(f16(B_h16), HID).b(e->W16(W_sa_wqk16), HID).out16(f16(B_qk16), 2 * HID)
+               .bias_col(e->F(W_sa_bqk)), stream));
+  TRY(gemm(Gemm(F16S, HID, T, HID, 4 * N).a(e->W16(W_sa_wv16), HID).b(f16(B_h16), HID, TH).out16(f16(B_vt16), T, TH)
+               .bias_rows(e->F(W_sa_bv)), stream));
+  TRY(attn(Attn(64, 6, 4 * N, T, T, 1, 0.125f).q(f16(B_qk16), 2 * HID, 2 * TH).k(f16(B_qk16) + HID, 2 * HID, 2 * TH)
+               .vt(f16(B_vt16), T, TH).out(f16(B_att16), HID, TH), stream));
+  TRY(gemm(Gemm(F16, (int)NT, HID, HID, 4).a(f16(B_att16), HID, NT * HID).b(e->W16(W_sa_wp16), HID).out32(f32(B_z), DEC, HID)
+               .bias_col(e->F(W_sa_bp)).mul_gate(g_a, (int)NT).add_res(f32(B_z), DEC, HID), stream));
   // --- per stream: gated MLP (:271-292) ---
-  TRY(dvd_layernorm_rows(z, DEC, HID, h16, HID, NT * HID, 4, NT, HID, nullptr, nullptr, sh_m, sc_m, 0, (int)NT, 1e-6f,
-                         stream));
-  TRY(gemm(F16, (int)(4 * NT), 4 * HID, HID, 1, h16, HID, 0, e->H(e->wi.fc1_w16, true), HID, 0, nullptr, 0, 0, mlp16, 4 * HID, 0,
-           e->F(e->wi.fc1_b), 0, /*gelu*/ 1, nullptr, 0, nullptr, 0, nullptr, 0, 0, stream, nullptr, e->L(e->wi.fc1_w16, true)));
-  TRY(gemm(F16, (int)NT, HID, 4 * HID, 4, mlp16, 4 * HID, NT * 4 * HID, e->H(e->wi.fc2_w16), 4 * HID, 0, z, DEC, HID,
-           nullptr, 0, 0, e->F(e->wi.fc2_b), 0, 0, nullptr, 0, g_m, (int)NT, z, DEC, HID, stream, nullptr, e->L(e->wi.fc2_w16)));
+  TRY(dvd_layernorm_rows(f32(B_z), DEC, HID, f16(B_h16), HID, NT * HID, 4, NT, HID, nullptr, nullptr, sh_m, sc_m, 0, (int)NT,
+                         1e-6f, stream));
+  TRY(gemm(Gemm(F16, (int)(4 * NT), 4 * HID, HID).a(f16(B_h16), HID).b(e->W16(W_fc1_w16), HID).out16(f16(B_mlp16), 4 * HID)
+               .bias_col(e->F(W_fc1_b)).act_fn(GELU), stream));
+  TRY(gemm(Gemm(F16, (int)NT, HID, 4 * HID, 4).a(f16(B_mlp16), 4 * HID, NT * 4 * HID).b(e->W16(W_fc2_w16), 4 * HID)
+               .out32(f32(B_z), DEC, HID).bias_col(e->F(W_fc2_b)).mul_gate(g_m, (int)NT).add_res(f32(B_z), DEC, HID), stream));
 
   if (e->debug_stop == 2) return check_launch("engine_denoise_step(stop 2)");
   // --- decoder: adaptive 2-D positional encoding (idf/cross_attn.py:143-157) ---
-  float* pooled = (float*)e->B(e->bi.pooled);
-  float* petmp = (float*)e->B(e->bi.petmp);
-  float* hs = (float*)e->B(e->bi.hs);
-  float* wsc = (float*)e->B(e->bi.wsc);
-  TRY(dvd_colmean(z, (float*)e->B(e->bi.part), pooled, N, T, DEC, COLCHUNKS, stream));
-  TRY(dvd_small_linear(pooled, DEC, e->F(e->wi.pe_h0_w), e->F(e->wi.pe_h0_b), petmp, DEC, N, DEC, DEC, DEC, 0, 2, stream));
-  TRY(dvd_small_linear(petmp, DEC, e->F(e->wi.pe_h2_w), e->F(e->wi.pe_h2_b), hs, DEC, N, DEC, DEC, DEC, 0, 3, stream));
-  TRY(dvd_small_linear(pooled, DEC, e->F(e->wi.pe_w0_w), e->F(e->wi.pe_w0_b), petmp, DEC, N, DEC, DEC, DEC, 0, 2, stream));
-  TRY(dvd_small_linear(petmp, DEC, e->F(e->wi.pe_w2_w), e->F(e->wi.pe_w2_b), wsc, DEC, N, DEC, DEC, DEC, 0, 3, stream));
-  TRY(dvd_posenc_add(z, hs, wsc, e->F(e->wi.pe_htab), e->F(e->wi.pe_wtab), N, side, DEC, stream));
+  TRY(dvd_colmean(f32(B_z), f32(B_part), f32(B_pooled), N, T, DEC, COLCHUNKS, stream));
+  TRY(dvd_small_linear(f32(B_pooled), DEC, e->F(W_pe_h0_w), e->F(W_pe_h0_b), f32(B_petmp), DEC, N, DEC, DEC, DEC, 0, 2, stream));
+  TRY(dvd_small_linear(f32(B_petmp), DEC, e->F(W_pe_h2_w), e->F(W_pe_h2_b), f32(B_hs), DEC, N, DEC, DEC, DEC, 0, 3, stream));
+  TRY(dvd_small_linear(f32(B_pooled), DEC, e->F(W_pe_w0_w), e->F(W_pe_w0_b), f32(B_petmp), DEC, N, DEC, DEC, DEC, 0, 2, stream));
+  TRY(dvd_small_linear(f32(B_petmp), DEC, e->F(W_pe_w2_w), e->F(W_pe_w2_b), f32(B_wsc), DEC, N, DEC, DEC, DEC, 0, 3, stream));
+  TRY(dvd_posenc_add(f32(B_z), f32(B_hs), f32(B_wsc), e->F(W_pe_htab), e->F(W_pe_wtab), N, side, DEC, stream));
 
   if (e->debug_stop == 3) return check_launch("engine_denoise_step(stop 3)");
   // --- decoder layers (idf/cross_attn.py:377-396) ---
-  _Float16* f1 = mlp16;
-  _Float16* f2 = mlp16 + (size_t)NT * FFN;
-  for (int j = 0; j < 6; ++j) {
-    const WIdx::Dec& dw = e->wi.d[j];
-    TRY(dvd_layernorm_rows(z, DEC, 0, h16, DEC, 0, 1, NT, DEC, e->F(dw.n1w), e->F(dw.n1b), nullptr, nullptr, 0,
-                           1, 1e-5f, stream));
-    TRY(gemm(F16, (int)NT, 2 * DEC, DEC, 1, h16, DEC, 0, e->H(dw.wqk16, true), DEC, 0, nullptr, 0, 0, qk16, 2 * DEC, 0,
-             nullptr, 0, 0, nullptr, 0, nullptr, 0, nullptr, 0, 0, stream, nullptr, e->L(dw.wqk16, true)));
-    TRY(gemm(F16, DEC, T, DEC, N, e->H(dw.wv16, true), DEC, 0, h16, DEC, (long)T * DEC, nullptr, 0, 0, vt16, T,
-             (long)DEC * T, nullptr, 0, 0, nullptr, 0, nullptr, 0, nullptr, 0, 0, stream, e->L(dw.wv16, true), nullptr));
+  _Float16* f1 = f16(B_mlp16);
+  _Float16* f2 = f1 + (size_t)NT * FFN;
+  for (int j = 0; j < DEC_LAYERS; ++j) {
+    auto w = [j](int k) { return W_dec(j, k); };   // this layer's weight indices
+    TRY(dvd_layernorm_rows(f32(B_z), DEC, 0, f16(B_h16), DEC, 0, 1, NT, DEC, e->F(w(WD_n1w)), e->F(w(WD_n1b)), nullptr, nullptr,
+                           0, 1, 1e-5f, stream));
+    TRY(gemm(Gemm(F16, (int)NT, 2 * DEC, DEC).a(f16(B_h16), DEC).b(e->W16(w(WD_wqk16)), DEC).out16(f16(B_qk16), 2 * DEC),
+             stream));
+    TRY(gemm(Gemm(F16, DEC, T, DEC, N).a(e->W16(w(WD_wv16)), DEC).b(f16(B_h16), DEC, TD).out16(f16(B_vt16), T, TD), stream));
     const bool timed = e->prof_on;
     size_t slot = 0;
     if (timed) {
@@ -765,24 +727,25 @@ static int enqueue_step(Engine* e, const float* x_t, int feat_mode, const float*
       slot = (e->prof_head + e->prof_inflight) % PROF_PAIRS;
       (void)hipEventRecord(e->prof_ev[2 * slot], st);
     }
-    TRY(attn(256, 6, N, T, T, 1, qk16, 2 * DEC, (long)T * 2 * DEC, qk16 + DEC, 2 * DEC, (long)T * 2 * DEC, vt16, T,
-             (long)DEC * T, att16, DEC, (long)T * DEC, 0.0625f, stream));
+    TRY(attn(Attn(256, 6, N, T, T, 1, 0.0625f).q(f16(B_qk16), 2 * DEC, 2 * TD).k(f16(B_qk16) + DEC, 2 * DEC, 2 * TD)
+                 .vt(f16(B_vt16), T, TD).out(f16(B_att16), DEC, TD), stream));
     if (timed) { (void)hipEventRecord(e->prof_ev[2 * slot + 1], st); e->prof_inflight += 1; }
-    TRY(gemm(F16, (int)NT, DEC, DEC, 1, att16, DEC, 0, e->H(dw.wfc16, true), DEC, 0, z, DEC, 0, nullptr, 0, 0, nullptr, 0,
-             0, nullptr, 0, nullptr, 0, z, DEC, 0, stream, nullptr, e->L(dw.wfc16, true)));
-    TRY(dvd_layernorm_rows(z, DEC, 0, h16, DEC, 0, 1, NT, DEC, e->F(dw.n2w), e->F(dw.n2b), nullptr, nullptr, 0,
-                           1, 1e-5f, stream));
-    TRY(gemm(F16, (int)NT, FFN, DEC, 1, h16, DEC, 0, e->H(dw.c1w16, true), DEC, 0, nullptr, 0, 0, f1, FFN, 0,
-             e->F(dw.c1b), 0, 2, nullptr, 0, nullptr, 0, nullptr, 0, 0, stream, nullptr, e->Lffn(dw.c1w16, true)));
-    TRY(dvd_dwconv3x3(f1, f2, e->F(dw.dww), e->F(dw.dwb), N, side, FFN, stream));
-    TRY(gemm(F16, (int)NT, DEC, FFN, 1, f2, FFN, 0, e->H(dw.c2w16, true), FFN, 0, z, DEC, 0, nullptr, 0, 0,
-             e->F(dw.c2b), 0, 2, nullptr, 0, nullptr, 0, z, DEC, 0, stream, nullptr, e->Lffn(dw.c2w16, true)));
+    TRY(gemm(Gemm(F16, (int)NT, DEC, DEC).a(f16(B_att16), DEC).b(e->W16(w(WD_wfc16)), DEC).out32(f32(B_z), DEC)
+                 .add_res(f32(B_z), DEC), stream));
+    TRY(dvd_layernorm_rows(f32(B_z), DEC, 0, f16(B_h16), DEC, 0, 1, NT, DEC, e->F(w(WD_n2w)), e->F(w(WD_n2b)), nullptr, nullptr,
+                           0, 1, 1e-5f, stream));
+    TRY(gemm(Gemm(F16, (int)NT, FFN, DEC).a(f16(B_h16), DEC).b(e->W16(w(WD_c1w16), /*ffn*/ true), DEC).out16(f1, FFN)
+                 .bias_col(e->F(w(WD_c1b))).act_fn(RELU), stream));
+    TRY(dvd_dwconv3x3(f1, f2, e->F(w(WD_dww)), e->F(w(WD_dwb)), N, side, FFN, stream));
+    TRY(gemm(Gemm(F16, (int)NT, DEC, FFN).a(f2, FFN).b(e->W16(w(WD_c2w16), /*ffn*/ true), FFN).out32(f32(B_z), DEC)
+                 .bias_col(e->F(w(WD_c2b))).act_fn(RELU).add_res(f32(B_z), DEC), stream));
     if (e->debug_stop == 4 + j) return check_launch("engine_denoise_step(stop 4+j)");
   }
 
   // --- final LayerNorm + FinalLayer2 + unpatchify + init_flow (:457; idf/cross_model.py:329-336,553-566,645-646) ---
-  TRY(dvd_final_tokens(z, e->F(e->wi.dec_nw), e->F(e->wi.dec_nb), finmod, finmod + DEC, 0, (int)NT, e->F(e->wi.fin_w),
-                       e->F(e->wi.fin_b), init_flow, x0_out, nullptr, N, G, stream));
+  const float* finmod = f32(B_finmod);
+  TRY(dvd_final_tokens(f32(B_z), e->F(W_dec_nw), e->F(W_dec_nb), finmod, finmod + DEC, 0, (int)NT, e->F(W_fin_w),
+                       e->F(W_fin_b), init_flow, x0_out, nullptr, N, G, stream));
   return check_launch("engine_denoise_step");
 }
 
@@ -796,10 +759,10 @@ extern "C" int dvd_engine_denoise_step(void* handle, const float* x_t, float t_e
   TRY(require_ready(e, true));
   DVD_REQUIRE(4 * e->NT < (1L << 31), "engine_denoise_step: batch too large for 32-bit row indices (NT=%ld)", e->NT);
   hipStream_t st = (hipStream_t)stream;
-  set_scalar_kernel<<<1, 1, 0, st>>>((float*)e->B(e->bi.tbuf), t_embed);
+  set_scalar_kernel<<<1, 1, 0, st>>>(e->f32(B_tbuf), t_embed);
   if (e->dither && !e->small_tiles) {
     // re-round the weights of the 256-wide GEMMs for this evaluation (outside any captured graph: the phase changes)
-    _Float16* dst = (_Float16*)e->B(e->bi.w16dith);
+    _Float16* dst = e->f16(B_w16dith);
     for (int i : e->dith_list)
       TRY(dvd_dither_f16(e->wptr[i], e->wptr[i + 1], dst + e->dith_off[i], e->specs[i].nelem, (unsigned)e->dith_off[i],
                          e->dither_step, stream));

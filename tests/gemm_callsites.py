@@ -64,11 +64,11 @@ class Call:
 
     @property
     def ldpos(self):
-        return self.N                  # engine.hip gemm(): d.ldpos = N
+        return self.N                  # engine.hip Gemm(): ldpos = N
 
     @property
     def ldgate(self):
-        return self.N                  # d.ldgate = N
+        return self.N                  # ldgate = N
 
     def esz(self):
         return 4 if self.dtype == 1 else 2
@@ -99,10 +99,10 @@ def calls(G, docs, hyp, split_weights=True, ffn_lo=True):
     def dt(code):
         return {0: (0, 0), 1: (1, 0), 2: (0, 1), 3: (0, 2)}[code]
 
-    def H(w, wide=False):                 # Engine::H
+    def H(w, wide=False):                 # Engine::W16(...).hi  (wide: TensorSpec::wide)
         return (("w16dith:" + w), 0) if (dither and wide) else (w, 0)
 
-    def L(w, wide=False, ffn=False):      # Engine::L / Lffn ((hi, lo) pairs are adjacent tensors)
+    def L(w, wide=False, ffn=False):      # Engine::W16(...).lo ((hi, lo) pairs are adjacent tensors)
         if ffn and not ffn_lo:
             return None
         return (w + "_lo", 0) if (split_weights and not (dither and wide)) else None
