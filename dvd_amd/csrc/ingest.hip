@@ -9,6 +9,7 @@
 // ((b0*(S0>>4))>>16) + ((b1*(S1>>4))>>16) + 2) >> 2; an exactly-2x downscale takes cv::resize's INTER_AREA switch).  Integer arithmetic throughout: bit-exact against
 // oracle/ingest_oracle.py; parity with a real cv2 build is UNPINNED.
 #include "common.h"
+#include "ragged.h"
 
 namespace dvd {
 
@@ -17,10 +18,8 @@ struct ResizeAxis {   // per destination index: source index and the two 11-bit 
   short a0, a1;
 };
 
-// coefficients of one axis; launched once per axis (<= 512 threads of work)
-__global__ void resize_axis_kernel(ResizeAxis* __restrict__ tab, int ssize, int dsize) {
-  const int d = blockIdx.x * blockDim.x + threadIdx.x;
-  if (d >= dsize) return;
+// coefficients of one axis at destination index d (shared by resize_axis_kernel and the ragged batch's table kernel)
+__device__ __forceinline__ void resize_axis_at(ResizeAxis* __restrict__ tab, int ssize, int dsize, int d) {
   const double scale = (double)ssize / (double)dsize;
   float f = (float)(((double)d + 0.5) * scale - 0.5);
   int s = (int)floorf(f);
@@ -33,12 +32,17 @@ __global__ void resize_axis_kernel(ResizeAxis* __restrict__ tab, int ssize, int 
   tab[d].a1 = (short)__float2int_rn(f * 2048.f);
 }
 
-__global__ void __launch_bounds__(256) ingest_resize_kernel(const uint8_t* __restrict__ src, int h, int w, int swap_rb,
-                                                            const ResizeAxis* __restrict__ tx,
-                                                            const ResizeAxis* __restrict__ ty, float* __restrict__ out,
-                                                            int osize) {
-  const int dx = blockIdx.x * blockDim.x + threadIdx.x, dy = blockIdx.y;
-  if (dx >= osize) return;
+// launched once per axis (<= 512 threads of work)
+__global__ void resize_axis_kernel(ResizeAxis* __restrict__ tab, int ssize, int dsize) {
+  const int d = blockIdx.x * blockDim.x + threadIdx.x;
+  if (d >= dsize) return;
+  resize_axis_at(tab, ssize, dsize, d);
+}
+
+// one output pixel (dx, dy) of one image, all three channels; shared by ingest_resize_kernel and ingest_resize_ragged_kernel
+__device__ __forceinline__ void ingest_resize_at(const uint8_t* __restrict__ src, int h, int w, int swap_rb,
+                                                 const ResizeAxis* __restrict__ tx, const ResizeAxis* __restrict__ ty,
+                                                 float* __restrict__ out, int osize, int dx, int dy) {
   if (h == 2 * osize && w == 2 * osize) {
     // exactly 2x in both axes: cv::resize switches INTER_LINEAR to INTER_AREA, whose 8-bit fast path is the rounded
     // mean of the 2x2 block (resizeAreaFast_: (S00 + S01 + S10 + S11 + 2) >> 2)
@@ -67,11 +71,52 @@ __global__ void __launch_bounds__(256) ingest_resize_kernel(const uint8_t* __res
   }
 }
 
+__global__ void __launch_bounds__(256) ingest_resize_kernel(const uint8_t* __restrict__ src, int h, int w, int swap_rb,
+                                                            const ResizeAxis* __restrict__ tx,
+                                                            const ResizeAxis* __restrict__ ty, float* __restrict__ out,
+                                                            int osize) {
+  const int dx = blockIdx.x * blockDim.x + threadIdx.x, dy = blockIdx.y;
+  if (dx >= osize) return;
+  ingest_resize_at(src, h, w, swap_rb, tx, ty, out, osize, dx, dy);
+}
+
 __global__ void __launch_bounds__(256) swap_rb_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, long px) {
   const long i = (long)blockIdx.x * 256 + threadIdx.x;
   if (i >= px) return;
   const uint8_t b = src[i * 3], g = src[i * 3 + 1], r = src[i * 3 + 2];
   dst[i * 3] = r; dst[i * 3 + 1] = g; dst[i * 3 + 2] = b;
+}
+
+// ---- n images of n sizes per launch (dvd_ingest_u8_ragged).  The tables of image d are scratch[(2 d) * osize ..]: x, then y.
+// Table and resize work is the same for every image (osize entries / osize^2 pixels), so those two grids carry the image in
+// z; the full-resolution RGB copies differ by an order of magnitude and take the flat grid of ragged.h.
+__global__ void resize_axis_ragged_kernel(ResizeAxis* __restrict__ scratch, RaggedTab tab, int dsize) {
+  const int d = blockIdx.x * blockDim.x + threadIdx.x;
+  if (d >= dsize) return;
+  const int img = blockIdx.z, axis = blockIdx.y;     // axis 0: x (source size w), 1: y (h)
+  resize_axis_at(scratch + ((size_t)img * 2 + axis) * dsize, axis ? tab.h[img] : tab.w[img], dsize, d);
+}
+
+__global__ void __launch_bounds__(256) ingest_resize_ragged_kernel(RaggedTab tab, int swap_rb,
+                                                                   const ResizeAxis* __restrict__ scratch,
+                                                                   float* __restrict__ out, int osize) {
+  const int dx = blockIdx.x * blockDim.x + threadIdx.x, dy = blockIdx.y, img = blockIdx.z;
+  if (dx >= osize) return;
+  const ResizeAxis* tx = scratch + (size_t)img * 2 * osize;
+  ingest_resize_at(tab.src[img], tab.h[img], tab.w[img], swap_rb, tx, tx + osize, out + (size_t)img * 3 * osize * osize, osize,
+                   dx, dy);
+}
+
+// the RGB-order full-resolution copies: one thread per pixel, 256 pixels per block, flat over the images that want one
+__global__ void __launch_bounds__(256) rgb_copy_ragged_kernel(RaggedTab tab, int swap_rb) {
+  const unsigned tile = blockIdx.x;
+  const int d = ragged_doc_of(tab, tile);
+  const long i = (long)(tile - (d ? tab.tile_end[d - 1] : 0u)) * 256 + threadIdx.x;
+  if (i >= (long)tab.h[d] * tab.w[d]) return;
+  const uint8_t* src = tab.src[d];
+  uint8_t* dst = tab.out[d];
+  const uint8_t a = src[i * 3], g = src[i * 3 + 1], b = src[i * 3 + 2];
+  dst[i * 3] = swap_rb ? b : a; dst[i * 3 + 1] = g; dst[i * 3 + 2] = swap_rb ? a : b;
 }
 
 }  // namespace dvd
@@ -103,4 +148,48 @@ extern "C" int dvd_ingest_u8(const uint8_t* src_hwc, int h, int w, int swap_rb, 
     }
   }
   return check_launch("ingest_u8");
+}
+
+extern "C" long dvd_ingest_ragged_scratch_bytes(int out_size, int n) {
+  return (long)(n > 0 ? n : 0) * dvd_ingest_scratch_bytes(out_size);
+}
+
+extern "C" int dvd_ingest_u8_ragged(const dvd_ragged_image* docs, int n, int swap_rb, float* y_nchw, int out_size,
+                                    void* scratch, void* stream) {
+  DVD_REQUIRE(docs && y_nchw && scratch, "ingest_u8_ragged: null pointer");
+  DVD_REQUIRE(n >= 0, "ingest_u8_ragged: bad batch %d", n);
+  DVD_REQUIRE(out_size >= 1 && out_size <= 65535, "ingest_u8_ragged: bad output size %d", out_size);
+  for (int d = 0; d < n; ++d) {       // every image is checked before the first launch
+    DVD_REQUIRE(docs[d].src, "ingest_u8_ragged: null pointer in image %d", d);
+    DVD_REQUIRE(docs[d].h >= 1 && docs[d].w >= 1 && docs[d].h <= 65535, "ingest_u8_ragged: bad shape h=%d w=%d of image %d",
+                docs[d].h, docs[d].w, d);
+    DVD_REQUIRE(!(swap_rb && docs[d].out == docs[d].src), "ingest_u8_ragged: image %d cannot be swapped in place", d);
+    DVD_REQUIRE((long)docs[d].h * docs[d].w <= 256l * 0x7fffffffl, "ingest_u8_ragged: image %d too large", d);
+  }
+  hipStream_t st = (hipStream_t)stream;
+  for (int d0 = 0; d0 < n;) {
+    RaggedTab tab;
+    size_t tiles = 0;
+    int m = 0;
+    for (; m < kRaggedCap && d0 + m < n; ++m) {
+      const dvd_ragged_image& im = docs[d0 + m];
+      const bool copy = im.out && (swap_rb || im.out != im.src);
+      const size_t t = copy ? (size_t)cdiv((long)im.h * im.w, 256) : 0;
+      if (tiles + t >= (1ull << 31)) break;
+      tiles += t;
+      tab.src[m] = im.src; tab.out[m] = im.out; tab.h[m] = im.h; tab.w[m] = im.w; tab.tile_end[m] = (unsigned)tiles;
+    }
+    for (int k = m; k < kRaggedCap; ++k) {    // unused entries: defined values in the kernel argument
+      tab.src[k] = nullptr; tab.out[k] = nullptr; tab.h[k] = tab.w[k] = 0; tab.tile_end[k] = (unsigned)tiles;
+    }
+    tab.n = m;
+    ResizeAxis* axes = (ResizeAxis*)scratch + (size_t)d0 * 2 * out_size;
+    resize_axis_ragged_kernel<<<dim3(cdiv(out_size, 256), 2, m), 256, 0, st>>>(axes, tab, out_size);
+    ingest_resize_ragged_kernel<<<dim3(cdiv(out_size, 256), out_size, m), 256, 0, st>>>(
+        tab, swap_rb ? 1 : 0, axes, y_nchw + (size_t)d0 * 3 * out_size * out_size, out_size);
+    if (tiles) rgb_copy_ragged_kernel<<<(unsigned)tiles, 256, 0, st>>>(tab, swap_rb ? 1 : 0);
+    if (int e = check_launch("ingest_u8_ragged")) return e;
+    d0 += m;
+  }
+  return DVD_OK;
 }

@@ -11,6 +11,7 @@
 // reach 3.5 TB/s.
 #include "common.h"
 #include "mfma.h"
+#include "ragged.h"
 
 namespace dvd {
 
@@ -584,14 +585,12 @@ __global__ void __launch_bounds__(256) unwarp_f32_kernel(const float* __restrict
   }
 }
 
-__global__ void __launch_bounds__(256) unwarp_u8_kernel(const float* __restrict__ flow,
-                                                        const uint8_t* __restrict__ src, uint8_t* __restrict__ out,
-                                                        UpParams p) {
-  flow += (size_t)blockIdx.z * 2 * p.g * p.g;        // one document per grid z (batched launch)
-  src += (size_t)blockIdx.z * 3 * p.h * p.w;
-  out += (size_t)blockIdx.z * 3 * p.h * p.w;
-  const int i0 = blockIdx.y * PX;
-  const int j = blockIdx.x * blockDim.x + threadIdx.x;
+// The u8 tail of ONE document, scalar path: the block (bx, by) of 256 columns x PX rows.  Shared by unwarp_u8_kernel (one
+// size per launch) and unwarp_u8_ragged_kernel (one size per document), so both give the same bytes.
+__device__ __forceinline__ void unwarp_u8_block(const float* __restrict__ flow, const uint8_t* __restrict__ src,
+                                                uint8_t* __restrict__ out, const UpParams& p, unsigned bx, unsigned by) {
+  const int i0 = by * PX;
+  const int j = bx * 256 + threadIdx.x;
   if (j >= p.w) return;
   Taps t[PX];
 #pragma unroll
@@ -621,6 +620,15 @@ __global__ void __launch_bounds__(256) unwarp_u8_kernel(const float* __restrict_
       o[ch] = (uint8_t)(int)a;   // truncation, as numpy .astype(uint8) for 0 <= a < 256
     }
   }
+}
+
+__global__ void __launch_bounds__(256) unwarp_u8_kernel(const float* __restrict__ flow,
+                                                        const uint8_t* __restrict__ src, uint8_t* __restrict__ out,
+                                                        UpParams p) {
+  flow += (size_t)blockIdx.z * 2 * p.g * p.g;        // one document per grid z (batched launch)
+  src += (size_t)blockIdx.z * 3 * p.h * p.w;
+  out += (size_t)blockIdx.z * 3 * p.h * p.w;
+  unwarp_u8_block(flow, src, out, p, blockIdx.x, blockIdx.y);
 }
 
 
@@ -677,17 +685,15 @@ __device__ __forceinline__ void load_rgb_pair(const uint8_t* __restrict__ src, u
   hi = __builtin_amdgcn_alignbyte(d2, d1, sh);
 }
 
-__global__ void __launch_bounds__(256) unwarp_u8_rows_kernel(const float* __restrict__ flow,
-                                                             const uint8_t* __restrict__ src,
-                                                             uint8_t* __restrict__ out, UpParams p) {
-  flow += (size_t)blockIdx.z * 2 * p.g * p.g;        // one document per grid z (batched launch)
-  src += (size_t)blockIdx.z * 3 * p.h * p.w;
-  out += (size_t)blockIdx.z * 3 * p.h * p.w;
+// ... and its fast path: the block (bx, by) of 256 columns x 4 rows; shared by unwarp_u8_rows_kernel and
+// unwarp_u8_ragged_kernel.  last_base is the document's own: no 12-byte access leaves [src, src + 3 h w).
+__device__ __forceinline__ void unwarp_u8_rows_block(const float* __restrict__ flow, const uint8_t* __restrict__ src,
+                                                     uint8_t* __restrict__ out, const UpParams& p, unsigned bx, unsigned by) {
   const int lane = threadIdx.x & 63;
   const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int i = blockIdx.y * 4 + wv;
+  const int i = by * 4 + wv;
   if (i >= p.h) return;
-  const uint32_t j0 = (blockIdx.x * 64 + lane) * 4;
+  const uint32_t j0 = (bx * 64 + lane) * 4;
   if (j0 >= (uint32_t)p.w) return;
   const uint32_t last_base = (uint32_t)p.h * (uint32_t)p.w * 3u - 12u;
   PTaps t[4];
@@ -722,6 +728,48 @@ __global__ void __launch_bounds__(256) unwarp_u8_rows_kernel(const float* __rest
   o.b = ob[4] | (ob[5] << 8) | (ob[6] << 16) | (ob[7] << 24);
   o.c = ob[8] | (ob[9] << 8) | (ob[10] << 16) | (ob[11] << 24);
   *reinterpret_cast<PackedU3*>(out + ((size_t)i * p.w + j0) * 3) = o;
+}
+
+__global__ void __launch_bounds__(256) unwarp_u8_rows_kernel(const float* __restrict__ flow,
+                                                             const uint8_t* __restrict__ src,
+                                                             uint8_t* __restrict__ out, UpParams p) {
+  flow += (size_t)blockIdx.z * 2 * p.g * p.g;        // one document per grid z (batched launch)
+  src += (size_t)blockIdx.z * 3 * p.h * p.w;
+  out += (size_t)blockIdx.z * 3 * p.h * p.w;
+  unwarp_u8_rows_block(flow, src, out, p, blockIdx.x, blockIdx.y);
+}
+
+// The u8 tail for documents of DIFFERENT sizes in one launch.  A flat 1-D grid over the 256-column x 4-row blocks of all
+// documents (the block shape of both kernels above): real pages differ in area by an order of magnitude, so a
+// dim3(.., .., n) grid sized for the largest would mostly launch blocks that return at once.  A block finds its document
+// in the by-value table (ragged_doc_of), builds that document's UpParams from scalar loads - they stay in SGPRs, as the
+// kernel argument of the single-size kernels does - and runs the block function the document's shape takes alone
+// (up.fast: the host's shape rule, dvd_unwarp_u8_batch), a block-uniform branch.
+struct RaggedUp {
+  float sy[kRaggedCap], sx[kRaggedCap], sby[kRaggedCap], sbx[kRaggedCap];   // make_up of each document
+  int fast[kRaggedCap];
+};
+
+__global__ void __launch_bounds__(256) unwarp_u8_ragged_kernel(const float* __restrict__ flow, int g, float scale,
+                                                               RaggedTab tab, RaggedUp up) {
+  const unsigned tile = blockIdx.x;
+  const int d = ragged_doc_of(tab, tile);
+  UpParams p;
+  p.g = g;
+  p.h = tab.h[d];
+  p.w = tab.w[d];
+  p.sy = up.sy[d];
+  p.sx = up.sx[d];
+  p.sby = up.sby[d];
+  p.sbx = up.sbx[d];
+  p.scale = scale;
+  p.small = (p.h + p.w <= 128) ? 1 : 0;
+  const unsigned local = tile - (d ? tab.tile_end[d - 1] : 0u);
+  const unsigned ntx = ((unsigned)p.w + 255u) >> 8;
+  const unsigned by = local / ntx, bx = local - by * ntx;
+  const float* f = flow + (size_t)d * 2 * g * g;
+  if (up.fast[d]) unwarp_u8_rows_block(f, tab.src[d], tab.out[d], p, bx, by);
+  else unwarp_u8_block(f, tab.src[d], tab.out[d], p, bx, by);
 }
 
 #ifdef DVD_LAB
@@ -926,12 +974,18 @@ extern "C" int dvd_unwarp_f32(const float* flow, int g, const float* src_chw, fl
   return dvd_unwarp_f32_batch(flow, g, src_chw, out_hwc, 1, h, w, scale, stream);
 }
 
+// the shape rule of the fast u8 tail (unwarp_u8_rows_kernel): a function of ONE document's shape, so a document takes the
+// same path alone, in a same-size batch and in a ragged batch
+static bool u8_rows_shape(int h, int w) {
+  return w % 4 == 0 && (size_t)h * w * 3 < (1ull << 32) && (size_t)h * w * 3 >= 12 && !scalar_warp();
+}
+
 extern "C" int dvd_unwarp_u8_batch(const float* flow, int g, const uint8_t* src_hwc, uint8_t* out_hwc, int n, int h,
                                    int w, float scale, void* stream) {
   if (int e = unwarp_args(flow, src_hwc, out_hwc, g, h, w)) return e;
   DVD_REQUIRE(n >= 0 && n <= 65535, "unwarp: bad batch %d", n);
   if (n == 0) return DVD_OK;
-  if (w % 4 == 0 && (size_t)h * w * 3 < (1ull << 32) && (size_t)h * w * 3 >= 12 && !scalar_warp()) {
+  if (u8_rows_shape(h, w)) {
 #ifdef DVD_LAB
     if (const char* e = getenv("DVD_WARP_U8_UB")) {      // lab: band height x unrolled or not
       const int ub = atoi(e);
@@ -961,6 +1015,44 @@ extern "C" int dvd_unwarp_u8(const float* flow, int g, const uint8_t* src_hwc, u
   return dvd_unwarp_u8_batch(flow, g, src_hwc, out_hwc, 1, h, w, scale, stream);
 }
 
+extern "C" int dvd_unwarp_u8_ragged(const float* flow, int g, const dvd_ragged_image* docs, int n, float scale,
+                                    void* stream) {
+  DVD_REQUIRE(flow && docs, "unwarp_u8_ragged: null pointer");
+  DVD_REQUIRE(n >= 0, "unwarp_u8_ragged: bad batch %d", n);
+  DVD_REQUIRE(g >= 2, "unwarp_u8_ragged: bad grid g=%d", g);
+  for (int d = 0; d < n; ++d) {       // every document is checked before the first launch
+    DVD_REQUIRE(docs[d].src && docs[d].out, "unwarp_u8_ragged: null pointer in document %d", d);
+    DVD_REQUIRE(docs[d].h >= 1 && docs[d].w >= 1 && docs[d].h <= 65535, "unwarp_u8_ragged: bad shape h=%d w=%d of document %d",
+                docs[d].h, docs[d].w, d);
+    DVD_REQUIRE((size_t)cdiv(docs[d].w, 256) * cdiv(docs[d].h, 4) < (1ull << 31), "unwarp_u8_ragged: document %d too large", d);
+  }
+  for (int d0 = 0; d0 < n;) {
+    // one launch: up to kRaggedCap documents and fewer than 2^31 blocks
+    RaggedTab tab;
+    RaggedUp up;
+    size_t tiles = 0;
+    int m = 0;
+    for (; m < kRaggedCap && d0 + m < n; ++m) {
+      const dvd_ragged_image& im = docs[d0 + m];
+      const size_t t = (size_t)cdiv(im.w, 256) * cdiv(im.h, 4);
+      if (tiles + t >= (1ull << 31)) break;
+      tiles += t;
+      const UpParams p = make_up(g, im.h, im.w, scale);
+      tab.src[m] = im.src; tab.out[m] = im.out; tab.h[m] = im.h; tab.w[m] = im.w; tab.tile_end[m] = (unsigned)tiles;
+      up.sy[m] = p.sy; up.sx[m] = p.sx; up.sby[m] = p.sby; up.sbx[m] = p.sbx;
+      up.fast[m] = u8_rows_shape(im.h, im.w) ? 1 : 0;
+    }
+    for (int k = m; k < kRaggedCap; ++k) {    // unused entries: defined values in the kernel argument
+      tab.src[k] = nullptr; tab.out[k] = nullptr; tab.h[k] = tab.w[k] = 0; tab.tile_end[k] = (unsigned)tiles;
+      up.sy[k] = up.sx[k] = up.sby[k] = up.sbx[k] = 0.f; up.fast[k] = 0;
+    }
+    tab.n = m;
+    unwarp_u8_ragged_kernel<<<(unsigned)tiles, 256, 0, (hipStream_t)stream>>>(flow + (size_t)d0 * 2 * g * g, g, scale, tab, up);
+    if (int e = check_launch("unwarp_u8_ragged")) return e;
+    d0 += m;
+  }
+  return DVD_OK;
+}
 
 #ifdef DVD_LAB
 // ---------------------------------------------------------------------------------------

@@ -72,10 +72,15 @@ def prepare_conditioning(batch, device, grid, prestage_models, use_init_flow=Fal
     `init_flow` [2,G,G] from GeoTr (evaluation.py:172-178), in the same pre-stage pass when that runs."""
     from . import prestage
     need_ingest = [d for d in batch if "image_u8" in d and "y512" not in d]
-    for d in need_ingest:
-        img = d["image_u8"]
-        img = (img if th.is_tensor(img) else th.from_numpy(img)).to(device).contiguous()
-        d["y512"], d["src_u8"] = ops.ingest_u8(img, swap_rb=False, out_size=512, want_rgb=True)
+    imgs = [(d["image_u8"] if th.is_tensor(d["image_u8"]) else th.from_numpy(d["image_u8"])).to(device).contiguous()
+            for d in need_ingest]
+    if len({tuple(im.shape) for im in imgs}) > 1:          # images of different sizes: one launch per stage for the batch
+        y, rgbs = ops.ingest_u8_ragged(imgs, swap_rb=False, out_size=512, want_rgb=True)
+        for j, d in enumerate(need_ingest):
+            d["y512"], d["src_u8"] = y[j], rgbs[j]
+    else:                                                   # one image, or images of one size: per image, as before
+        for d, img in zip(need_ingest, imgs):
+            d["y512"], d["src_u8"] = ops.ingest_u8(img, swap_rb=False, out_size=512, want_rgb=True)
     todo = [d for d in batch if any(k not in d for k in ("mask_cat", "mask_y512", "line_msk"))]
     if use_init_flow and (prestage_models is None or prestage_models[0] is None):
         raise RuntimeError("env.use_init_flow needs the GeoTr_Seg_Inf model (pretrained_dewarp_model)")
@@ -144,7 +149,7 @@ def run_evaluation_docunet(settings, logger, val_loader, diffusion, model, pretr
     `val_loader` yields the reference's dicts or this package's documents (`documents_of`); `env.batch_docs` documents are
     batched per pass (the reference: 1): ingest + the three pre-stage nets for documents that arrive as images
     (:162-216), the sampler (:247-265), then the tail (:301-306 + visualization_utils.py:75-77) as ONE fused u8 launch per
-    batch, and - if env.visualize - `visualize_dewarping` writes the PNG where the reference writes it.
+    batch (documents of one size or of different sizes alike), and - if env.visualize - `visualize_dewarping` writes the PNG where the reference writes it.
     The pre-stage models may all be None when every document carries ready conditioning tensors.
     Returns [(path, uint8 [H,W,3] device tensor)] (the reference returns None)."""
     from utils_flow.visualization_utils import visualize_dewarping
@@ -181,17 +186,22 @@ def run_evaluation_docunet(settings, logger, val_loader, diffusion, model, pretr
                                        th.zeros(nb, 256, G, G, device=device))
         th.cuda.synchronize()
         times.append((time.time() - t0) / nb)
-        # :301-306 + viz :75-77 - one launch for the batch when its documents are byte images of one full-resolution size
+        # :301-306 + viz :75-77 - one launch for the batch when its documents are byte images
         if all("src_u8" in d for d in batch) and len({tuple(d["src_u8"].shape) for d in batch}) == 1:
             outs = ops.unwarp_u8_batch(flow.contiguous(), stack("src_u8"))
         else:
-            outs = []
+            # byte images of different sizes: still one launch (the ragged tail); a float source that is not a byte image
+            # takes the fused f32 tail on its own, truncated like numpy's astype(uint8)
+            outs = [None] * nb
+            u8 = [j for j, d in enumerate(batch) if "src_u8" in d]
+            if u8:
+                fl = flow.contiguous() if len(u8) == nb else flow[u8].contiguous()
+                for j, out in zip(u8, ops.unwarp_u8_ragged(fl, [dev_t(batch[j]["src_u8"]).contiguous() for j in u8])):
+                    outs[j] = out
             for j, d in enumerate(batch):
-                fj = flow[j:j + 1].contiguous()
-                if "src_u8" in d:
-                    outs.append(ops.unwarp_u8(fj, dev_t(d["src_u8"]).contiguous()))
-                else:   # a float source that is not a byte image: the fused f32 tail, truncated like numpy's astype(uint8)
-                    outs.append(ops.unwarp_f32(fj, d["source_vis"].to(device).float()[None].contiguous()).to(th.uint8))
+                if outs[j] is None:
+                    outs[j] = ops.unwarp_f32(flow[j:j + 1].contiguous(),
+                                             d["source_vis"].to(device).float()[None].contiguous()).to(th.uint8)
         for j, d in enumerate(batch):
             out = outs[j]
             results.append((d["path"], out))

@@ -75,9 +75,16 @@ class CnOp(C.Structure):
                 ("flag", C.c_int)]
 
 
+class RaggedImage(C.Structure):
+    """dvd_ragged_image: one document of a ragged batch (device pointers, its own size)."""
+    _fields_ = [("src", C.c_void_p), ("out", C.c_void_p), ("h", C.c_int), ("w", C.c_int)]
+
+
+RAGGED_CAP = 64   # DVD_RAGGED_CAP: documents per launch of the ragged entry points (larger batches are cut by the library)
+
 NON_STATUS = {"dvd_last_error", "dvd_version", "dvd_engine_workspace_bytes", "dvd_engine_tensor_count",
               "dvd_flash_attn_kernel_name", "dvd_gemm_kernel_name", "dvd_convnet_workspace_bytes", "dvd_convnet_weight_floats",
-              "dvd_ingest_scratch_bytes"}
+              "dvd_ingest_scratch_bytes", "dvd_ingest_ragged_scratch_bytes"}
 
 # name -> argtypes; kept in one table so tests can check every symbol of include/dvd_hip.h
 SIGNATURES = {
@@ -88,6 +95,7 @@ SIGNATURES = {
     "dvd_unwarp_f32_batch": [c_void, C.c_int, c_void, c_void, C.c_int, C.c_int, C.c_int, C.c_float, c_void],
     "dvd_unwarp_u8_batch": [c_void, C.c_int, c_void, c_void, C.c_int, C.c_int, C.c_int, C.c_float, c_void],
     "dvd_unwarp_grid": [c_void, C.c_int, c_void, C.c_int, C.c_int, C.c_float, c_void],
+    "dvd_unwarp_u8_ragged": [c_void, C.c_int, C.POINTER(RaggedImage), C.c_int, C.c_float, c_void],
     "dvd_sched_step": [C.POINTER(SchedCoef), c_void, c_void, c_void, c_void, c_void, C.c_int, C.c_int, c_void],
     "dvd_sched_step_clip": [C.POINTER(SchedCoef), c_void, c_void, c_void, c_void, c_void, C.c_int, C.c_int, c_void],
     "dvd_hyp_mean_clamp": [c_void, c_void, C.c_int, C.c_int, C.c_int, c_void],
@@ -128,6 +136,8 @@ SIGNATURES = {
     "dvd_soft_mask_mul_batch": [c_void, c_void, c_void, C.c_int, C.c_int, C.c_long, c_void],
     "dvd_convex_upsample": [c_void, c_void, C.c_int, C.c_int, C.c_int, c_void, c_void, C.c_int, C.c_float, c_void],
     "dvd_ingest_u8": [c_void, C.c_int, C.c_int, C.c_int, c_void, C.c_int, c_void, c_void, c_void],
+    "dvd_ingest_ragged_scratch_bytes": [C.c_int, C.c_int],
+    "dvd_ingest_u8_ragged": [C.POINTER(RaggedImage), C.c_int, C.c_int, c_void, C.c_int, c_void, c_void],
     "dvd_dither_f16": [c_void, c_void, c_void, C.c_long, C.c_uint, C.c_uint, c_void],
     "dvd_engine_create": [C.c_int, C.c_int, C.c_int, C.POINTER(c_void)],
     "dvd_engine_destroy": [c_void],
@@ -147,7 +157,7 @@ SIGNATURES = {
 
 
 # entries of SIGNATURES that return something other than a status
-RESTYPES = {"dvd_gemm_kernel_name": C.c_char_p}
+RESTYPES = {"dvd_gemm_kernel_name": C.c_char_p, "dvd_ingest_ragged_scratch_bytes": C.c_long}
 
 # entry points that exist only in the lab build (benchmarks/lab/dvd_hip_lab.h; loaded through use_library)
 LAB_SIGNATURES = {"dvd_gemm_debug_stamps": [c_void], "dvd_attn_debug_stamps": [c_void]}

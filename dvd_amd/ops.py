@@ -76,6 +76,42 @@ def unwarp_u8_batch(flow: torch.Tensor, src_nhwc: torch.Tensor, scale: float = 0
     return out
 
 
+def _carve(sizes, device, align=256):
+    """One uint8 allocation cut into len(sizes) pieces, each starting on an `align`-byte boundary."""
+    offs, total = [], 0
+    for sz in sizes:
+        offs.append(total)
+        total += -(-sz // align) * align
+    buf = torch.empty(max(total, 1), dtype=torch.uint8, device=device)
+    return [buf[o:o + sz] for o, sz in zip(offs, sizes)]
+
+
+def _ragged_table(srcs, outs):
+    tab = (lib.RaggedImage * max(len(srcs), 1))()
+    for d, (s, o) in enumerate(zip(srcs, outs)):
+        tab[d].src, tab[d].out = s.data_ptr(), (None if o is None else o.data_ptr())
+        tab[d].h, tab[d].w = s.shape[0], s.shape[1]
+    return tab
+
+
+def unwarp_u8_ragged(flow: torch.Tensor, srcs, scale: float = 0.987):
+    """flow [n,2,G,G]; srcs: n [h_d,w_d,3] uint8 tensors of ANY sizes -> n uint8 tensors, each the bytes of
+    unwarp_u8(flow[d:d+1], srcs[d]): the batch's documents in ONE launch (per lib.RAGGED_CAP documents).  The outputs are
+    views of one allocation."""
+    _chk(flow, torch.float32, "flow")
+    srcs = list(srcs)
+    assert flow.dim() == 4 and flow.shape[0] == len(srcs) and flow.shape[1] == 2
+    for d, s in enumerate(srcs):
+        _chk(s, torch.uint8, f"srcs[{d}]")
+        assert s.dim() == 3 and s.shape[2] == 3, f"srcs[{d}]: expected [H,W,3]"
+    if not srcs:
+        return []
+    outs = [o.view(s.shape) for o, s in zip(_carve([s.numel() for s in srcs], flow.device), srcs)]
+    lib.call("dvd_unwarp_u8_ragged", ptr(flow), flow.shape[-1], _ragged_table(srcs, outs), len(srcs), C.c_float(scale),
+             stream_ptr())
+    return outs
+
+
 def unwarp_f32_batch(flow: torch.Tensor, src_nchw: torch.Tensor, scale: float = 0.987) -> torch.Tensor:
     """flow [B,2,G,G]; src [B,3,H,W] f32 0..255 -> [B,H,W,3] f32."""
     _chk(flow, torch.float32, "flow")
@@ -99,6 +135,27 @@ def ingest_u8(img_hwc: torch.Tensor, swap_rb: bool = False, out_size: int = 512,
     scratch = torch.empty(lib.raw().dvd_ingest_scratch_bytes(out_size), dtype=torch.uint8, device=img_hwc.device)
     lib.call("dvd_ingest_u8", ptr(img_hwc), h, w, int(swap_rb), ptr(y), out_size, ptr(rgb_out), ptr(scratch), stream_ptr())
     return (y, rgb_out if swap_rb else img_hwc) if want_rgb else y
+
+
+def ingest_u8_ragged(imgs, swap_rb: bool = False, out_size: int = 512, want_rgb: bool = False):
+    """n decoded images [h_d,w_d,3] uint8 of ANY sizes -> y [n,3,out,out] f32, y[d] the bits of ingest_u8(imgs[d]), in one
+    launch per stage for the batch; with want_rgb also the list of full-resolution RGB images (the inputs themselves when
+    swap_rb is off, views of one allocation otherwise)."""
+    imgs = list(imgs)
+    for d, im in enumerate(imgs):
+        _chk(im, torch.uint8, f"imgs[{d}]")
+        assert im.dim() == 3 and im.shape[2] == 3, f"imgs[{d}]: expected [H,W,3]"
+    if not imgs:
+        raise lib.DvdError("ingest_u8_ragged: no image (the device of the result is the images')")
+    n, dev = len(imgs), imgs[0].device
+    y = torch.empty((n, 3, out_size, out_size), dtype=torch.float32, device=dev)
+    if want_rgb and swap_rb:
+        rgbs = [o.view(im.shape) for o, im in zip(_carve([im.numel() for im in imgs], dev), imgs)]
+    else:
+        rgbs = [None] * n
+    scratch = torch.empty(lib.raw().dvd_ingest_ragged_scratch_bytes(out_size, n), dtype=torch.uint8, device=dev)
+    lib.call("dvd_ingest_u8_ragged", _ragged_table(imgs, rgbs), n, int(swap_rb), ptr(y), out_size, ptr(scratch), stream_ptr())
+    return (y, rgbs if swap_rb else imgs) if want_rgb else y
 
 
 def sched_step(coef: lib.SchedCoef, x_t, x0, noise=None, want_grid=False, out=None, clip=False):

@@ -67,6 +67,19 @@ int dvd_unwarp_f32_batch(const float* flow, int g, const float* src_chw, float* 
                          int n, int h, int w, float scale, void* stream);
 int dvd_unwarp_u8_batch(const float* flow, int g, const uint8_t* src_hwc, uint8_t* out_hwc,
                         int n, int h, int w, float scale, void* stream);
+/* Documents of DIFFERENT sizes in one launch (real evaluation sets are photographs of many sizes; the reference runs one
+ * document at a time, evaluation.py:245-306).  docs is a HOST array of n entries holding DEVICE pointers to separate
+ * buffers; it is read during the call only (the table travels as a kernel argument).  At most DVD_RAGGED_CAP documents go
+ * into one launch: a larger n is cut into ceil(n / DVD_RAGGED_CAP) launches by the entry point. */
+#define DVD_RAGGED_CAP 64
+typedef struct {
+  const uint8_t* src; /* [h,w,3] uint8 */
+  uint8_t* out;       /* [h,w,3] uint8 */
+  int h, w;           /* 1 <= h <= 65535, 1 <= w */
+} dvd_ragged_image;
+/* flow [n,2,G,G]: docs[d].out == dvd_unwarp_u8(flow + d*2*G*G, g, docs[d].src, docs[d].out, h_d, w_d, scale) byte for
+ * byte - each document takes the kernel path its own shape takes alone.  src and out of all documents must not overlap. */
+int dvd_unwarp_u8_ragged(const float* flow, int g, const dvd_ragged_image* docs, int n, float scale, void* stream);
 /* Materialise the full-resolution sampling grid only ([2,H,W] f32), i.e. evaluation.py:301-306. */
 int dvd_unwarp_grid(const float* flow, int g, float* grid_out, int h, int w, float scale, void* stream);
 
@@ -328,6 +341,14 @@ int dvd_convex_upsample(const float* mask, const float* dflow, int n, int h, int
 long dvd_ingest_scratch_bytes(int out_size);
 int dvd_ingest_u8(const uint8_t* src_hwc, int h, int w, int swap_rb, float* y_chw, int out_size,
                   uint8_t* rgb_hwc_out, void* scratch, void* stream);
+
+/* The same for n images of n sizes in at most three launches (axis tables, resize, RGB copies): y_nchw [n,3,out,out],
+ * y_nchw[d] == dvd_ingest_u8(docs[d].src, ...) bit for bit.  docs[d].out (optional; may equal src when swap_rb == 0, which
+ * copies nothing) receives the full-resolution image in RGB order.  scratch: dvd_ingest_ragged_scratch_bytes(out_size, n)
+ * device bytes.  n above DVD_RAGGED_CAP is cut into several launches per stage. */
+long dvd_ingest_ragged_scratch_bytes(int out_size, int n);
+int dvd_ingest_u8_ragged(const dvd_ragged_image* docs, int n, int swap_rb, float* y_nchw, int out_size, void* scratch,
+                         void* stream);
 
 /* Temporal dithering of the f16 weight rounding (no reference counterpart: the reference is fp32; the GEMMs that consume
  * the result are the per-step nn.Linear / 1x1 convs, idf/cross_attn.py:197-221,52-57, idf/cross_model.py:163-174).
