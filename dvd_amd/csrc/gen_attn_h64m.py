@@ -32,36 +32,19 @@ Schedule of tile t (exp unit numbering as in r64m: 0..15 chunk 0 of both row blo
                                                                    test; packs p01 (g = 0), p11 (tail); rare block
   phase 2b  steps 6, 7   O^T += V^T(t) frag (chunk 1, dt) . P01/P11 | units 4 g .. + 3 of tile t + 1; V^T(t+2) piece (g = 0)
 """
-import os
-import sys
+# r64m's statement class and what it is written against: the S^T buffers and exp unit numbering, the mask pair, the MFMA
+from gen_attn_r64m import MF, S_MASK, SBUF, Stmt as R64mStmt, sreg, urb
+from gen_common import each_variant, lds_dma, main, vr
 
 P00, P10, P01, P11 = 32, 36, 40, 44
 FR0 = 48
-SBUF = (64, 96)
 Q0 = 128
 KS, DT = 4, 2
 KBYTES, VBYTES = 4096, 4096
-S_KG, S_VG, S_TC, S_TMP, S_MASK, S_SEL = 80, 82, 84, 85, 86, 88
+S_KG, S_VG, S_TC, S_TMP, S_SEL = 80, 82, 84, 85, 88
 SGPR_CLOBBERS = [f"s{i}" for i in range(80, 90)]
 RESCALE_THR_BITS = "0x41200000"
-MF = "v_mfma_f32_32x32x16_f16"
-ABL = set()        # timing ablations (lab builds only; garbage results): "eu", "pack", "dma", "read", "wait", "max", "bar"
-
-
-def vr(lo, n=1):
-    return f"v{lo}" if n == 1 else f"v[{lo}:{lo + n - 1}]"
-
-
-def urb(u):
-    return (u & 1) if u < 16 else (0 if u < 24 else 1)
-
-
-def uel(u):
-    return (u >> 1) if u < 16 else (8 + u - 16 if u < 24 else 8 + u - 24)
-
-
-def sreg(buf, u):
-    return SBUF[buf] + 16 * urb(u) + uel(u)
+dma_m0, dma, advance = lds_dma(S_KG, S_VG, S_TC, S_TMP, KBYTES, VBYTES)        # one piece per wave, stream and tile
 
 
 def frag(slot):
@@ -76,52 +59,13 @@ def qreg(rb, ks):
     return vr(Q0 + 4 * (KS * rb + ks), 4)
 
 
-class Stmt:
-    def __init__(self):
-        self.lines = []
-
-    def add(self, s):
-        if "m16" in ABL and s.startswith(MF):
-            # POWER ablation: the same FLOPs from two 16x16x32 MFMAs on the first 8 accumulator registers (garbage math)
-            d, a, b, c = [x.strip() for x in s[len(MF):].split(",")]
-            lo = int(d[2:].split(":")[0])
-            for h in range(2):
-                dd = f"{d[0]}[{lo + 4 * h}:{lo + 4 * h + 3}]"
-                self.lines.append(f"v_mfma_f32_16x16x32_f16 {dd}, {a}, {b}, {dd if c != '0' else '0'}")
-            return
-        if "read" in ABL and s.startswith("ds_read"):
-            return
-        if "wait" in ABL and s.startswith("s_waitcnt lgkmcnt"):
-            return
-        if "bar" in ABL and s.startswith("s_barrier"):
-            return
-        if "max" in ABL and (s.startswith("v_max") or s.startswith("v_cmp")):
-            if s.startswith("v_cmp"):
-                self.lines.append(f"s_mov_b64 s[{S_MASK}:{S_MASK + 1}], 0")
-            return
-        self.lines.append(s)
-
-    def label(self, name):
-        self.lines.append(name + ":")
-
-    def eu(self, buf, u, add_from=None, acc="l", first=False):
-        """exp unit u of the tile in `buf`, in place; then the row-sum add of unit add_from (same buffer) if given"""
-        if "eu" in ABL:
-            return
-        x = vr(sreg(buf, u))
-        self.add(f"v_fma_f32 {x}, {x}, %[c], -%[m{urb(u)}]")
-        self.add(f"v_exp_f32_e32 {x}, {x}")
-        if add_from is not None:
-            a = f"%[{acc}{urb(add_from)}]"
-            if first:
-                self.add(f"v_mov_b32_e32 {a}, {vr(sreg(buf, add_from))}")
-            else:
-                self.add(f"v_add_f32_e32 {a}, {a}, {vr(sreg(buf, add_from))}")
+class Stmt(R64mStmt):
+    """r64m's statement (same eu / pack, same ablations) + the exp units in pairs"""
 
     def eu2(self, buf, u, acc="l", first=()):
         """exp units u and u + 1 interleaved (a unit's v_exp does not follow its own v_fma back to back: two waves per SIMD
         hide much, but 32 dependent pairs per tile showed in the cycles), then the row-sum adds of units u - 1 and u"""
-        if "eu" in ABL:
+        if "eu" in self.abl:
             return
         xs = [vr(sreg(buf, u + i)) for i in range(2)]
         for i in range(2):
@@ -136,35 +80,6 @@ class Stmt:
                 self.add(f"v_mov_b32_e32 {a}, {vr(sreg(buf, w))}")
             else:
                 self.add(f"v_add_f32_e32 {a}, {a}, {vr(sreg(buf, w))}")
-
-    def pack(self, dst, buf, units):
-        if "pack" in ABL:
-            return
-        for j in range(4):
-            self.add(f"v_cvt_pk_f16_f32 {vr(dst + j)}, {vr(sreg(buf, units[2 * j]))}, {vr(sreg(buf, units[2 * j + 1]))}")
-
-    def dma_m0(self, which, slot):
-        if "dma" in ABL:
-            return
-        self.add(f"s_add_i32 m0, %[{which}dst], {slot * (KBYTES if which == 'k' else VBYTES)}")
-
-    def dma(self, which):
-        if "dma" in ABL:
-            return
-        sg = S_KG if which == "k" else S_VG
-        self.add(f"global_load_lds_dwordx4 %[{which}off], s[{sg}:{sg + 1}]")
-
-    def advance(self, which):
-        if "dma" in ABL:
-            return
-        sg = S_KG if which == "k" else S_VG
-        self.add(f"s_cmp_lt_i32 s{S_TC}, %[{which}lim]")
-        self.add(f"s_cselect_b32 s{S_TMP}, %[{which}step], 0")
-        self.add(f"s_add_u32 s{sg}, s{sg}, s{S_TMP}")
-        self.add(f"s_addc_u32 s{sg + 1}, s{sg + 1}, 0")
-
-    def text(self):
-        return "\n".join(f'      "{ln}\\n\\t"' for ln in self.lines)
 
 
 def read_for_step(n, slot):
@@ -189,15 +104,15 @@ def tile(s, var):
         a, off = read_for_step(n + 3, slot)
         s.add(f"ds_read_b128 {frag(n + 3)}, %[{a}] offset:{off}")
         if f == 1:
-            s.dma_m0("k", slot)                           # K(t+3) -> K slot t % 3
+            dma_m0(s, "k", slot)                           # K(t+3) -> K slot t % 3
         s.eu2(sc, 8 + 4 * f)                              # u = 8 adds unit 7, the last early unit, straight to l
-        if f == 0 and "eu" not in ABL:                    # the early units' side sums join l
+        if f == 0 and "eu" not in s.abl:                    # the early units' side sums join l
             s.add("v_add_f32_e32 %[l0], %[l0], %[e0]")
             s.add("v_add_f32_e32 %[l1], %[l1], %[e1]")
         s.add(f"{MF} {sn1}, {frag(n)}, {qreg(1, f)}, {'0' if f == 0 else sn1}")
         if f == 1:
-            s.dma("k")
-            s.advance("k")
+            dma(s, "k")
+            advance(s, "k")
         s.eu2(sc, 10 + 4 * f)
         if f == 2:
             s.pack(P00, sc, [0, 2, 4, 6, 8, 10, 12, 14])
@@ -230,7 +145,7 @@ def tile(s, var):
             s.add(it)
         if g == 0:
             s.pack(P01, sc, [16, 17, 18, 19, 20, 21, 22, 23])
-    if "eu" not in ABL:
+    if "eu" not in s.abl:
         s.add(f"v_add_f32_e32 %[l1], %[l1], {vr(sreg(sc, 31))}")
     s.pack(P11, sc, [24, 25, 26, 27, 28, 29, 30, 31])
     s.add(f"s_cmp_lg_u64 s[{S_MASK}:{S_MASK + 1}], 0")
@@ -243,12 +158,12 @@ def tile(s, var):
         a, off = read_for_step(n + 3, slot)
         s.add(f"ds_read_b128 {frag(n + 3)}, %[{a}] offset:{off}")
         if g == 0:
-            s.dma_m0("v", (slot + 2) % 3)                 # V^T(t+2) -> V slot (t + 2) % 3
+            dma_m0(s, "v", (slot + 2) % 3)                 # V^T(t+2) -> V slot (t + 2) % 3
         s.eu2(sn, 4 * g, acc="e", first=(1, 2))           # early units of tile t + 1: side sums e0 / e1
         s.add(f"{MF} {oreg(1, g)}, {frag(n)}, {vr(P11, 4)}, {oreg(1, g)}")
         if g == 0:
-            s.dma("v")
-            s.advance("v")
+            dma(s, "v")
+            advance(s, "v")
         s.eu2(sn, 4 * g + 2, acc="e", first=(1, 2))
         if g == 1:
             s.add(f"s_add_i32 s{S_TC}, s{S_TC}, 1")
@@ -291,8 +206,8 @@ def rare_block(s):
     s.add("s_branch .Lh64m_back5_%=")
 
 
-def loop_stmt():
-    s = Stmt()
+def loop_stmt(opt):
+    s = Stmt(opt)
     s.add(f"s_mov_b64 s[{S_KG}:{S_KG + 1}], %[kg]")
     s.add(f"s_mov_b64 s[{S_VG}:{S_VG + 1}], %[vg]")
     s.add(f"s_mov_b32 s{S_TC}, 0")
@@ -317,8 +232,8 @@ def loop_stmt():
     return s
 
 
-def prologue_s0():
-    s = Stmt()
+def prologue_s0(opt):
+    s = Stmt(opt)
     s0, s1 = vr(SBUF[0], 16), vr(SBUF[0] + 16, 16)
     for f in range(3):
         s.add(f"ds_read_b128 {frag(f)}, %[kf{f}]")
@@ -338,8 +253,8 @@ def prologue_s0():
     return s
 
 
-def prologue_units():
-    s = Stmt()
+def prologue_units(opt):
+    s = Stmt(opt)
     for f in range(3):
         s.add(f"ds_read_b128 {frag(f)}, %[kf{f}] offset:{KBYTES}")
     for u in range(8):
@@ -351,14 +266,14 @@ VARIANTS = [("", ()), ("noeu", ("eu", "pack", "max")), ("m16", ("m16",)), ("mfma
 KF = ", ".join(f'[kf{i}] "v"(kf[{i}])' for i in range(4))
 
 
-def emit_loop(w, sfx):
+def emit_loop(opt, w, sfx):
     w(f"// ---- the key-tile loop{sfx}: six tile variants, the rare rescale block, the drain")
     w(f"__device__ __forceinline__ void h64m_loop{sfx}(float& l0, float& l1, float& m0, float& m1, float& thr0, float& thr1, float e0, float e1,")
     w("    const char* kg, const char* vg, int nt, const unsigned (&kf)[4], unsigned vrel0, unsigned vrel1, unsigned koff, unsigned voff,")
     w("    float c, unsigned kdst, unsigned vdst, unsigned kstep, unsigned vstep, int klim, int vlim) {")
     w("  float a0, a1, b0, b1, t0, t1, t2, t3, t4;")
     w("  asm volatile(")
-    w(loop_stmt().text())
+    w(loop_stmt(opt).text())
     w('      : [l0] "+v"(l0), [l1] "+v"(l1), [m0] "+v"(m0), [m1] "+v"(m1), [thr0] "+v"(thr0), [thr1] "+v"(thr1), [e0] "+v"(e0), [e1] "+v"(e1),')
     w('        [a0] "=&v"(a0), [a1] "=&v"(a1), [b0] "=&v"(b0), [b1] "=&v"(b1), [t0] "=&v"(t0), [t1] "=&v"(t1), [t2] "=&v"(t2), [t3] "=&v"(t3),')
     w('        [t4] "=&v"(t4)')
@@ -370,7 +285,7 @@ def emit_loop(w, sfx):
     w("")
 
 
-def emit():
+def emit(opt):
     out, lab = [], []
     lab.append("// GENERATED by dvd_amd/csrc/gen_attn_h64m.py --lab - do not edit.  TIMING ABLATIONS of the h64m loop (lab builds only).")
     lab.append("// clang-format off")
@@ -397,7 +312,7 @@ def emit():
     w("")
     w("__device__ __forceinline__ void h64m_prologue_s0(const unsigned (&kf)[4], float& a0, float& a1) {")
     w("  asm volatile(")
-    w(prologue_s0().text())
+    w(prologue_s0(opt).text())
     w('      : [a0] "=&v"(a0), [a1] "=&v"(a1)')
     w(f'      : {KF}')
     w('      : "memory");')
@@ -405,31 +320,18 @@ def emit():
     w("")
     w("__device__ __forceinline__ void h64m_prologue_units(const unsigned (&kf)[4], float c, float m0, float m1, float& e0, float& e1) {")
     w("  asm volatile(")
-    w(prologue_units().text())
+    w(prologue_units(opt).text())
     w('      : [e0] "=&v"(e0), [e1] "=&v"(e1)')
     w(f'      : {KF}, [c] "s"(c), [m0] "v"(m0), [m1] "v"(m1)')
     w('      : "memory");')
     w("}")
     w("")
-    for abl_name, abl in VARIANTS:
-        ABL.clear()
-        ABL.update(abl)
-        emit_loop(out.append if not abl_name else lab.append, "" if not abl_name else "_" + abl_name)
-    ABL.clear()
+    for o, sink, sfx in each_variant(opt, VARIANTS, out, lab):
+        emit_loop(o, sink, sfx)
     w("// clang-format on")
     lab.append("// clang-format on")
     return "\n".join(out) + "\n", "\n".join(lab) + "\n"
 
 
 if __name__ == "__main__":
-    here = os.path.dirname(os.path.abspath(__file__))
-    prod, lab = emit()
-    ppath = os.path.join(here, "attn_h64m_body.inc")
-    lpath = os.path.normpath(os.path.join(here, "..", "..", "benchmarks", "lab", "csrc", "attn_h64m_abl.inc"))
-    arg = sys.argv[1] if len(sys.argv) > 1 else ""
-    if arg == "--check":
-        sys.exit(0 if os.path.exists(ppath) and open(ppath).read() == prod else 1)
-    path, text = (lpath, lab) if arg == "--lab" else (ppath, prod)
-    if not (os.path.exists(path) and open(path).read() == text):      # identical content keeps its mtime (make)
-        open(path, "w").write(text)
-    print(f"wrote {path}: {text.count(chr(10))} lines")
+    main([("attn_h64m", emit)])

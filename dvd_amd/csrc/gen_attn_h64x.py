@@ -25,8 +25,7 @@ Register plan (per wave):
                    2): 32 v_fma per tile gone from a loop in which VALU work does not hide.  The rare block adds its delta to
                    the tuples and subtracts it from the S^T(t+1) already formed against the old m (one block per buffer parity).
 """
-import os
-import sys
+from gen_common import Stmt, each_variant, lds_dma, main, vr
 
 P0 = 32
 FR0 = 48
@@ -48,16 +47,11 @@ MF = "v_mfma_f32_16x16x32_f16"
 # tile and wave in a loop whose VALU port is busier than its matrix pipe: 77.6 % vs 60.6 %, profiles/r5_pmc_*); 176 VGPRs + 80 AGPRs
 # = the 256 registers of a wave at two per SIMD.  The rare block scales the l tiles like the O^T tiles; after the loop l is read
 # from a[64 + 4 qb], complete (no cross-lane reduction).  Generated as a second body (prefix h64l) beside the round-4 one.
-LM = False
-L_SPREAD = os.environ.get("H64X_L_SPREAD") == "1"     # experiment switch of the generator (not a product option): one row-sum
-#                                                        MFMA behind each PV group instead of four at the end of phase 2 - measured
-#                                                        equal (8.52-8.56 vs 8.57 ms at the bench shape, two rounds), not adopted
-PFX = "h64x"
-ABL = set()        # timing ablations (lab builds only; garbage results): "valu", "dma", "read", "wait", "bar"
-
-
-def vr(lo, n=1):
-    return f"v{lo}" if n == 1 else f"v[{lo}:{lo + n - 1}]"
+# Which body is being emitted is the option field `lm` (emit).
+# --l-spread (experiment switch of the generator, not a product option): one row-sum MFMA behind each PV group instead of four at
+# the end of phase 2 - measured equal (8.52-8.56 vs 8.57 ms at the bench shape, two rounds), not adopted.
+# timing ablations (lab builds only; garbage results): the common "read", "wait", "bar"; "dma"; "valu" (emit_gap)
+dma_m0, dma, advance = lds_dma(S_KG, S_VG, S_TC, S_TMP, KBYTES, VBYTES)        # one piece per wave, stream and tile (as h64m)
 
 
 def frag(slot):
@@ -84,26 +78,6 @@ def lreg(qb):
     return f"a[{64 + 4 * qb}:{64 + 4 * qb + 3}]"
 
 
-class Stmt:
-    def __init__(self):
-        self.lines = []
-
-    def add(self, s):
-        if "read" in ABL and s.startswith("ds_read"):
-            return
-        if "wait" in ABL and s.startswith("s_waitcnt lgkmcnt"):
-            return
-        if "bar" in ABL and s.startswith("s_barrier"):
-            return
-        self.lines.append(s)
-
-    def label(self, name):
-        self.lines.append(name + ":")
-
-    def text(self):
-        return "\n".join(f'      "{ln}\\n\\t"' for ln in self.lines)
-
-
 # ---- VALU items (strings; "valu" ablation drops them all, the test then never fires) ----
 def exp_unit(buf, u):
     return f"v_exp_f32_e32 v{SBUF[buf] + u}, v{SBUF[buf] + u}"
@@ -113,15 +87,11 @@ def cvt_word(buf, w):
     return f"v_cvt_pk_f16_f32 v{P0 + w}, v{SBUF[buf] + 2 * w}, v{SBUF[buf] + 2 * w + 1}"
 
 
-SUM_BY_DOT2 = os.environ.get("R64X_SUM_BY_DOT2") == "1"    # experiment switches of the generator (not product options)
-WAIT_EVERY_STEP = os.environ.get("R64X_WAIT_EVERY_STEP") == "1"
-
-
-def sum_word(w, buf):
+def sum_word(opt, w, buf):
     """row sum of the two exponentials of word w.  Two v_add_f32 on the f32 values: one v_dot2c_f32_f16 on the packed word
     measured 2711 instead of 2460 cycles per tile here, and the same 300 cycles in r64m when its row sums were moved to dot2
     (round 4) - DOT instructions wait for the matrix pipe (gen_attn_r64x.py, pk_arg)."""
-    if SUM_BY_DOT2:
+    if opt.sum_by_dot2:                                   # experiment switch --sum-by-dot2
         return f"v_dot2c_f32_f16 %[l{w >> 2}], {ONES_F16X2}, v{P0 + w}"
     return (f"v_add_f32_e32 %[l{w >> 2}], %[l{w >> 2}], v{SBUF[buf] + 2 * w}\\n\\t"
             f"v_add_f32_e32 %[l{w >> 2}], %[l{w >> 2}], v{SBUF[buf] + 2 * w + 1}")
@@ -159,32 +129,9 @@ def read_for_step(n, slot):
     return kfrag_addr(n - 8, (slot + 2) % 3)                           # K(t+2)
 
 
-def dma_m0(s, which, slot):
-    if "dma" in ABL:
-        return
-    s.add(f"s_add_i32 m0, %[{which}dst], {slot * (KBYTES if which == 'k' else VBYTES)}")
-
-
-def dma(s, which):
-    if "dma" in ABL:
-        return
-    sg = S_KG if which == "k" else S_VG
-    s.add(f"global_load_lds_dwordx4 %[{which}off], s[{sg}:{sg + 1}]")
-
-
-def advance(s, which):
-    if "dma" in ABL:
-        return
-    sg = S_KG if which == "k" else S_VG
-    s.add(f"s_cmp_lt_i32 s{S_TC}, %[{which}lim]")
-    s.add(f"s_cselect_b32 s{S_TMP}, %[{which}step], 0")
-    s.add(f"s_add_u32 s{sg}, s{sg}, s{S_TMP}")
-    s.add(f"s_addc_u32 s{sg + 1}, s{sg + 1}, 0")
-
-
 def ring_wait(s, n):
     """before step n uses ring slot n & 3 (as in r64x: `lgkmcnt(1)` at the even steps covers two fragments)"""
-    if WAIT_EVERY_STEP:
+    if s.opt.wait_every_step:                             # experiment switch --wait-every-step
         s.add("s_waitcnt lgkmcnt(2)")
     elif not n & 1:
         s.add("s_waitcnt lgkmcnt(1)")
@@ -195,9 +142,9 @@ def emit_gap(s, items):
         if it.startswith(".L") or it.startswith("s_cbranch"):
             if it.endswith(":"):
                 s.label(it[:-1])
-            elif "valu" not in ABL:                      # without the test there is nothing to branch on
+            elif "valu" not in s.abl:                      # without the test there is nothing to branch on
                 s.add(it)
-        elif "valu" not in ABL:
+        elif "valu" not in s.abl:
             s.add(it)
 
 
@@ -218,13 +165,14 @@ def spread(seq, ngaps):
 def tile(s, var):
     par, slot = var & 1, var % 3
     cur, nxt = par, 1 - par
+    LM, L_SPREAD = s.opt.lm, s.opt.l_spread
     # ---------------- phase 1 (steps 0..3): S^T(t+1); exp units 16..31 of tile t, the 16 packs of P(t) and their row sums
     seq = []
     for j in range(8):
         seq += [exp_unit(cur, 16 + 2 * j), exp_unit(cur, 17 + 2 * j), cvt_word(cur, j)]
-        seq += [] if LM else sum_word(j, cur).split("\\n\\t")
+        seq += [] if LM else sum_word(s.opt, j, cur).split("\\n\\t")
     for j in range(8, 16):
-        seq += [cvt_word(cur, j)] + ([] if LM else sum_word(j, cur).split("\\n\\t"))
+        seq += [cvt_word(cur, j)] + ([] if LM else sum_word(s.opt, j, cur).split("\\n\\t"))
     gaps = spread(seq, 16)
     for f in range(4):
         n, ks, kb2 = f, f >> 1, f & 1
@@ -270,7 +218,7 @@ def tile(s, var):
             if qb == 3 and g == 2:
                 s.add(f"s_add_i32 s{S_TC}, s{S_TC}, 1")
             emit_gap(s, gaps[(5 * g + qb) if (LM and L_SPREAD) else (4 * g + qb)])
-        if LM and L_SPREAD:                                   # experiment (H64X_L_SPREAD=1): one row-sum MFMA behind each PV group
+        if LM and L_SPREAD:                                   # experiment (--l-spread): one row-sum MFMA behind each PV group
             s.add(f"{MF} {lreg(g)}, %[ones], {pfrag(g)}, {lreg(g)}")
             emit_gap(s, gaps[5 * g + 4])
     if LM and not L_SPREAD:                                   # the row sums: O^T's fifth dim block, A = ones (no fragment read)
@@ -283,7 +231,7 @@ def rare_block(s, par):
     """out of line, one per buffer parity, shared by the three variants of that parity (s[S_SEL] = the variant to return to):
     delta = max(row maximum of S^T(t+1), 0) per query; m += delta (the -m tuples), S^T(t+1) -= delta; O^T, l and the packed
     P(t) of the query block scaled by alpha = 2^-delta"""
-    nxt = 1 - par
+    nxt, LM = 1 - par, s.opt.lm
     s.label(f".Lh64x_rare{par}_%=")
     s.add("s_nop 15")                                     # the PV MFMAs issued so far must have written O^T
     s.add("s_nop 7")
@@ -324,8 +272,8 @@ def rare_block(s, par):
     s.add(f"s_branch .Lh64x_back{mine[-1]}_%=")
 
 
-def loop_stmt():
-    s = Stmt()
+def loop_stmt(opt):
+    s = Stmt(opt)
     s.add(f"s_mov_b64 s[{S_KG}:{S_KG + 1}], %[kg]")
     s.add(f"s_mov_b64 s[{S_VG}:{S_VG + 1}], %[vg]")
     s.add(f"s_mov_b32 s{S_TC}, 0")
@@ -351,9 +299,9 @@ def loop_stmt():
     return s
 
 
-def prologue_s0():
+def prologue_s0(opt):
     """S^T(0) into buffer 0 from K slot 0 (un-pipelined), then the lane-local maxima of the four query blocks"""
-    s = Stmt()
+    s = Stmt(opt)
     for f in range(4):
         a, off = kfrag_addr(f, 0)
         s.add(f"ds_read_b128 {frag(f)}, %[{a}] offset:{off}")
@@ -369,10 +317,10 @@ def prologue_s0():
     return s
 
 
-def prologue_units():
+def prologue_units(opt):
     """-m -> the C tuples; tile 0's scores (formed with C = 0) minus m; its exp units 0..15 (what phase 2 of a tile does for the
     next one); the fragment ring primed with K(1) fragments 0..2"""
-    s = Stmt()
+    s = Stmt(opt)
     for f in range(3):
         a, off = kfrag_addr(f, 1)
         s.add(f"ds_read_b128 {frag(f)}, %[{a}] offset:{off}")
@@ -389,7 +337,8 @@ def prologue_units():
 VARIANTS = [("", ()), ("novalu", ("valu",)), ("nobar", ("bar",)), ("mfmaonly", ("valu", "dma", "read", "wait"))]
 
 
-def emit_loop(w, sfx):
+def emit_loop(opt, w, sfx):
+    LM, PFX = opt.lm, ("h64l" if opt.lm else "h64x")
     w(f"// ---- the key-tile loop{sfx}: six tile variants, the rare rescale block, the drain")
     if LM:
         w(f"__device__ __forceinline__ void {PFX}_loop{sfx}(uintx4 ones, const char* kg, const char* vg, int nt,")
@@ -399,7 +348,7 @@ def emit_loop(w, sfx):
     w("    unsigned kstep, unsigned vstep, int klim, int vlim) {")
     w("  float a0, a1, a2, a3, t0, t1, t2, t3, t4;")
     w("  asm volatile(")
-    w(loop_stmt().text())
+    w(loop_stmt(opt).text())
     ls = "" if LM else '[l0] "+v"(l0), [l1] "+v"(l1), [l2] "+v"(l2), [l3] "+v"(l3), '
     w(f'      : {ls}[a0] "=&v"(a0), [a1] "=&v"(a1), [a2] "=&v"(a2), [a3] "=&v"(a3),')
     w('        [t0] "=&v"(t0), [t1] "=&v"(t1), [t2] "=&v"(t2), [t3] "=&v"(t3), [t4] "=&v"(t4)')
@@ -411,9 +360,9 @@ def emit_loop(w, sfx):
     w("")
 
 
-def emit(lm=False):
-    global LM, PFX
+def emit(opt, lm=False):
     LM, PFX = lm, ("h64l" if lm else "h64x")
+    opt = opt.replace(lm=lm)
     nacc = 80 if LM else 64
     U = PFX.upper()
     out, lab = [], []
@@ -463,7 +412,7 @@ def emit(lm=False):
         w("")
     w(f"__device__ __forceinline__ void {PFX}_prologue_s0(unsigned kf0, unsigned kf1, float& a0, float& a1, float& a2, float& a3) {{")
     w("  asm volatile(")
-    w(prologue_s0().text())
+    w(prologue_s0(opt).text())
     w('      : [a0] "=&v"(a0), [a1] "=&v"(a1), [a2] "=&v"(a2), [a3] "=&v"(a3)')
     w('      : [kf0] "v"(kf0), [kf1] "v"(kf1)')
     w('      : "memory");')
@@ -471,36 +420,18 @@ def emit(lm=False):
     w("")
     w(f"__device__ __forceinline__ void {PFX}_prologue_units(unsigned kf0, unsigned kf1, float m0, float m1, float m2, float m3) {{")
     w("  asm volatile(")
-    w(prologue_units().text())
+    w(prologue_units(opt).text())
     w('      :')
     w('      : [kf0] "v"(kf0), [kf1] "v"(kf1), [m0] "v"(m0), [m1] "v"(m1), [m2] "v"(m2), [m3] "v"(m3)')
     w('      : "memory");')
     w("}")
     w("")
-    for abl_name, abl in VARIANTS:
-        ABL.clear()
-        ABL.update(abl)
-        emit_loop(out.append if not abl_name else lab.append, "" if not abl_name else "_" + abl_name)
-    ABL.clear()
+    for o, sink, sfx in each_variant(opt, VARIANTS, out, lab):
+        emit_loop(o, sink, sfx)
     w("// clang-format on")
     lab.append("// clang-format on")
     return "\n".join(out) + "\n", "\n".join(lab) + "\n"
 
 
 if __name__ == "__main__":
-    here = os.path.dirname(os.path.abspath(__file__))
-    labdir = os.path.normpath(os.path.join(here, "..", "..", "benchmarks", "lab", "csrc"))
-    arg = sys.argv[1] if len(sys.argv) > 1 else ""
-    ok = True
-    for lm, stem in ((False, "attn_h64x"), (True, "attn_h64l")):
-        prod, lab = emit(lm)
-        ppath, lpath = os.path.join(here, stem + "_body.inc"), os.path.join(labdir, stem + "_abl.inc")
-        if arg == "--check":
-            ok = ok and os.path.exists(ppath) and open(ppath).read() == prod
-            continue
-        path, text = (lpath, lab) if arg == "--lab" else (ppath, prod)
-        if not (os.path.exists(path) and open(path).read() == text):      # identical content keeps its mtime (make)
-            open(path, "w").write(text)
-        print(f"wrote {path}: {text.count(chr(10))} lines")
-    if arg == "--check":
-        sys.exit(0 if ok else 1)
+    main([("attn_h64x", emit), ("attn_h64l", lambda opt: emit(opt, lm=True))], ("l-spread", "sum-by-dot2", "wait-every-step"))

@@ -50,8 +50,7 @@ sums accumulate straight into l (the early units of the NEXT tile into a side pa
 so the phantom units after the last tile are never counted), the pointers advance in SALU instructions in MFMA shadows,
 and the rare rescale is an out-of-line block at the end of the statement shared by the six variants.
 """
-import os
-import sys
+from gen_common import Stmt as StmtBase, each_variant, lds_dma, main, vr
 
 P00, P10, P01, P11 = 32, 36, 40, 44
 FR0 = 48
@@ -62,10 +61,6 @@ KBYTES, VBYTES = 16 * KPIECE, 16384
 S_KG, S_VG, S_TC, S_TMP, S_MASK, S_SEL = 80, 82, 84, 85, 86, 88
 SGPR_CLOBBERS = [f"s{i}" for i in range(80, 90)]
 RESCALE_THR_BITS = "0x41200000"      # 10.0f (log2 units), as in the other attention kernels
-
-
-def vr(lo, n=1):
-    return f"v{lo}" if n == 1 else f"v[{lo}:{lo + n - 1}]"
 
 
 def urb(u):
@@ -95,16 +90,15 @@ def qreg(rb, ks):
 
 
 MF = "v_mfma_f32_32x32x16_f16"
+dma_m0, dma, advance = lds_dma(S_KG, S_VG, S_TC, S_TMP, KBYTES, VBYTES, KPIECE, 1024)
 
-ABL = set()        # timing ablations (lab builds only; results are garbage): "eu", "pack", "dma", "read", "wait", "max", "bar"
 
-
-class Stmt:
-    def __init__(self):
-        self.lines = []
+class Stmt(StmtBase):
+    """timing ablations (lab builds only; results are garbage): the common "read", "wait", "bar"; "dma"; and this class's
+    "m16", "max", "eu", "pack" (the softmax of r64m and of h64m, gen_attn_h64m.py, which extends this class)"""
 
     def add(self, s):
-        if "m16" in ABL and s.startswith(MF):
+        if "m16" in self.abl and s.startswith(MF):
             # POWER ablation: the same FLOPs from two 16x16x32 MFMAs on the first 8 accumulator registers (garbage math)
             d, a, b, c = [x.strip() for x in s[len(MF):].split(",")]
             lo = int(d[2:].split(":")[0])
@@ -112,24 +106,15 @@ class Stmt:
                 dd = f"{d[0]}[{lo + 4 * h}:{lo + 4 * h + 3}]"
                 self.lines.append(f"v_mfma_f32_16x16x32_f16 {dd}, {a}, {b}, {dd if c != '0' else '0'}")
             return
-        if "read" in ABL and s.startswith("ds_read"):
-            return
-        if "wait" in ABL and s.startswith("s_waitcnt lgkmcnt"):
-            return
-        if "bar" in ABL and s.startswith("s_barrier"):
-            return
-        if "max" in ABL and (s.startswith("v_max") or s.startswith("v_cmp")):
+        if "max" in self.abl and (s.startswith("v_max") or s.startswith("v_cmp")):
             if s.startswith("v_cmp"):
                 self.lines.append(f"s_mov_b64 s[{S_MASK}:{S_MASK + 1}], 0")
             return
-        self.lines.append(s)
-
-    def label(self, name):
-        self.lines.append(name + ":")
+        super().add(s)
 
     def eu(self, buf, u, add_from=None, acc="l", first=False):
         """exp unit u of the tile in `buf`, in place; then the row-sum add of unit add_from (same buffer) if given"""
-        if "eu" in ABL:
+        if "eu" in self.abl:
             return
         x = vr(sreg(buf, u))
         self.add(f"v_fma_f32 {x}, {x}, %[c], -%[m{urb(u)}]")
@@ -143,34 +128,10 @@ class Stmt:
 
     def pack(self, dst, buf, units):
         """four packed words of one P fragment: word j <- (units[2j], units[2j + 1])"""
-        if "pack" in ABL:
+        if "pack" in self.abl:
             return
         for j in range(4):
             self.add(f"v_cvt_pk_f16_f32 {vr(dst + j)}, {vr(sreg(buf, units[2 * j]))}, {vr(sreg(buf, units[2 * j + 1]))}")
-
-    def dma_m0(self, which, slot, i):
-        """first gap: the LDS destination of piece i (the MFMA that follows separates the M0 write from its use)"""
-        if "dma" in ABL:
-            return
-        imm = slot * (KBYTES if which == "k" else VBYTES) + i * (KPIECE if which == "k" else 1024)
-        self.add(f"s_add_i32 m0, %[{which}dst], {imm}")
-
-    def dma(self, which, i):
-        if "dma" in ABL:
-            return
-        sg = S_KG if which == "k" else S_VG
-        self.add(f"global_load_lds_dwordx4 %[{which}off{i}], s[{sg}:{sg + 1}]")
-
-    def advance(self, which):
-        """source pair += one tile, unless the stream has reached its last tile (which is then re-loaded)"""
-        sg = S_KG if which == "k" else S_VG
-        self.add(f"s_cmp_lt_i32 s{S_TC}, %[{which}lim]")
-        self.add(f"s_cselect_b32 s{S_TMP}, %[{which}step], 0")
-        self.add(f"s_add_u32 s{sg}, s{sg}, s{S_TMP}")
-        self.add(f"s_addc_u32 s{sg + 1}, s{sg + 1}, 0")
-
-    def text(self):
-        return "\n".join(f'      "{ln}\\n\\t"' for ln in self.lines)
 
 
 def read_for_step(n, slot):
@@ -197,16 +158,16 @@ def tile(s, var):
         a, off = read_for_step(n + 3, slot)
         s.add(f"ds_read_b128 {frag(n + 3)}, %[{a}] offset:{off}")
         if f in (3, 7, 11, 15):
-            s.dma_m0("k", slot, f >> 2)                   # K(t+3) -> K slot t % 3
+            dma_m0(s, "k", slot, f >> 2)                   # K(t+3) -> K slot t % 3
         s.eu(sc, 8 + f, add_from=7 + f)                   # f = 0 adds unit 7, the last of the early units, straight to l
-        if f in (0, 1) and "eu" not in ABL:               # the early units' side sums (rb f) join l
+        if f in (0, 1) and "eu" not in s.abl:               # the early units' side sums (rb f) join l
             s.add(f"v_add_f32_e32 %[l{f}], %[l{f}], %[e{f}]")
         c_in = "0" if f == 0 else sn1
         s.add(f"{MF} {sn1}, {frag(n)}, {qreg(1, f)}, {c_in}")
         if f in (3, 7, 11, 15):
-            s.dma("k", f >> 2)
-        if f == 15 and "dma" not in ABL:
-            s.advance("k")
+            dma(s, "k", f >> 2)
+        if f == 15:
+            advance(s, "k")
         if f == 9:
             s.pack(P00, sc, [0, 2, 4, 6, 8, 10, 12, 14])
         if f == 10:
@@ -243,7 +204,7 @@ def tile(s, var):
             s.add(f"v_cmp_lt_f32_e64 s[{S_MASK}:{S_MASK + 1}], 0, %[b0]")
         if g == 5:
             s.pack(P01, sc, [16, 17, 18, 19, 20, 21, 22, 23])
-    if "eu" not in ABL:
+    if "eu" not in s.abl:
         s.add(f"v_add_f32_e32 %[l1], %[l1], {vr(sreg(sc, 31))}")
     s.pack(P11, sc, [24, 25, 26, 27, 28, 29, 30, 31])
     # deferred rescale (rare): some lane saw its row's maximum over its 16 keys of tile t + 1 exceed m + THR.  O^T holds the
@@ -261,14 +222,14 @@ def tile(s, var):
         a, off = read_for_step(n + 3, slot)
         s.add(f"ds_read_b128 {frag(n + 3)}, %[{a}] offset:{off}")
         if 1 <= g <= 4:
-            s.dma_m0("v", (slot + 2) % 3, g - 1)          # V^T(t+2) -> V slot (t + 2) % 3
+            dma_m0(s, "v", (slot + 2) % 3, g - 1)          # V^T(t+2) -> V slot (t + 2) % 3
         # units 0..7 of tile t + 1: their sums go to the side pair e0 / e1 (unit 0 -> rb 0 and unit 1 -> rb 1 START them)
         s.eu(sn, g, add_from=(g - 1) if g else None, acc="e", first=g in (1, 2))
         s.add(f"{MF} {oreg(1, g)}, {frag(n)}, {vr(P11, 4)}, {oreg(1, g)}")
         if 1 <= g <= 4:
-            s.dma("v", g - 1)
-        if g == 4 and "dma" not in ABL:
-            s.advance("v")
+            dma(s, "v", g - 1)
+        if g == 4:
+            advance(s, "v")
         if g == 5:
             s.add(f"s_add_i32 s{S_TC}, s{S_TC}, 1")
 
@@ -311,8 +272,8 @@ def rare_block(s):
     s.add("s_branch .Lr64m_back5_%=")
 
 
-def loop_stmt():
-    s = Stmt()
+def loop_stmt(opt):
+    s = Stmt(opt)
     s.add(f"s_mov_b64 s[{S_KG}:{S_KG + 1}], %[kg]")
     s.add(f"s_mov_b64 s[{S_VG}:{S_VG + 1}], %[vg]")
     s.add(f"s_mov_b32 s{S_TC}, 0")
@@ -340,9 +301,9 @@ def loop_stmt():
     return s
 
 
-def prologue_s0():
+def prologue_s0(opt):
     """S^T(0) into buffer 0 from K slot 0 (un-pipelined), then the lane-local maxima of both row blocks"""
-    s = Stmt()
+    s = Stmt(opt)
     s0, s1 = vr(SBUF[0], 16), vr(SBUF[0] + 16, 16)
     for f in range(3):
         s.add(f"ds_read_b128 {frag(f)}, %[kaddr] offset:{f * 32}")
@@ -365,9 +326,9 @@ def prologue_s0():
     return s
 
 
-def prologue_units():
+def prologue_units(opt):
     """units 0..7 of tile 0 in place (buffer 0), the side sums of units 0..6, and the ring primed with K(1) frags 0..2"""
-    s = Stmt()
+    s = Stmt(opt)
     for f in range(3):
         s.add(f"ds_read_b128 {frag(f)}, %[kaddr] offset:{KBYTES + f * 32}")
     for u in range(8):
@@ -379,14 +340,14 @@ VARIANTS = [("", ()), ("m16", ("m16",)), ("noeu", ("eu", "pack", "max")), ("nodm
             ("mfmaonly", ("eu", "pack", "dma", "read", "wait", "max"))]
 
 
-def emit_loop(w, sfx):
+def emit_loop(opt, w, sfx):
     w(f"// ---- the key-tile loop{sfx}: six tile variants, the rare rescale block, the drain")
     w(f"__device__ __forceinline__ void r64m_loop{sfx}(float& l0, float& l1, float& m0, float& m1, float& thr0, float& thr1, float e0, float e1,")
     w("    const char* kg, const char* vg, int nt, unsigned kaddr, unsigned vrel0, unsigned vrel1, const unsigned (&koff)[4],")
     w("    const unsigned (&voff)[4], float c, unsigned kdst, unsigned vdst, unsigned kstep, unsigned vstep, int klim, int vlim) {")
     w("  float a0, a1, b0, b1, t0, t1, t2, t3, t4;")
     w("  asm volatile(")
-    w(loop_stmt().text())
+    w(loop_stmt(opt).text())
     w('      : [l0] "+v"(l0), [l1] "+v"(l1), [m0] "+v"(m0), [m1] "+v"(m1), [thr0] "+v"(thr0), [thr1] "+v"(thr1), [e0] "+v"(e0), [e1] "+v"(e1),')
     w('        [a0] "=&v"(a0), [a1] "=&v"(a1), [b0] "=&v"(b0), [b1] "=&v"(b1), [t0] "=&v"(t0), [t1] "=&v"(t1), [t2] "=&v"(t2), [t3] "=&v"(t3),')
     w('        [t4] "=&v"(t4)')
@@ -399,7 +360,7 @@ def emit_loop(w, sfx):
     w("")
 
 
-def emit():
+def emit(opt):
     """-> (product file text, lab file text: the timing ablations)"""
     out, lab = [], []
     lab.append("// GENERATED by dvd_amd/csrc/gen_attn_r64m.py --lab - do not edit.  TIMING ABLATIONS of the r64m loop (lab builds only:")
@@ -422,7 +383,7 @@ def emit():
     w("")
     w("__device__ __forceinline__ void r64m_prologue_s0(unsigned kaddr, float& a0, float& a1) {")
     w("  asm volatile(")
-    w(prologue_s0().text())
+    w(prologue_s0(opt).text())
     w('      : [a0] "=&v"(a0), [a1] "=&v"(a1)')
     w('      : [kaddr] "v"(kaddr)')
     w('      : "memory");')
@@ -430,17 +391,14 @@ def emit():
     w("")
     w("__device__ __forceinline__ void r64m_prologue_units(unsigned kaddr, float c, float m0, float m1, float& e0, float& e1) {")
     w("  asm volatile(")
-    w(prologue_units().text())
+    w(prologue_units(opt).text())
     w('      : [e0] "=&v"(e0), [e1] "=&v"(e1)')
     w('      : [kaddr] "v"(kaddr), [c] "s"(c), [m0] "v"(m0), [m1] "v"(m1)')
     w('      : "memory");')
     w("}")
     w("")
-    for abl_name, abl in VARIANTS:
-        ABL.clear()
-        ABL.update(abl)
-        emit_loop(out.append if not abl_name else lab.append, "" if not abl_name else "_" + abl_name)
-    ABL.clear()
+    for o, sink, sfx in each_variant(opt, VARIANTS, out, lab):
+        emit_loop(o, sink, sfx)
     w("__device__ __forceinline__ void r64m_zero_o() {")
     w("  asm volatile(")
     for i in range(256):
@@ -466,14 +424,4 @@ def emit():
 
 
 if __name__ == "__main__":
-    here = os.path.dirname(os.path.abspath(__file__))
-    prod, lab = emit()
-    ppath = os.path.join(here, "attn_r64m_body.inc")
-    lpath = os.path.normpath(os.path.join(here, "..", "..", "benchmarks", "lab", "csrc", "attn_r64m_abl.inc"))
-    arg = sys.argv[1] if len(sys.argv) > 1 else ""
-    if arg == "--check":
-        sys.exit(0 if os.path.exists(ppath) and open(ppath).read() == prod else 1)
-    path, text = (lpath, lab) if arg == "--lab" else (ppath, prod)
-    if not (os.path.exists(path) and open(path).read() == text):      # identical content keeps its mtime (make)
-        open(path, "w").write(text)
-    print(f"wrote {path}: {text.count(chr(10))} lines")
+    main([("attn_r64m", emit)])

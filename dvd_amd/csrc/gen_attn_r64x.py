@@ -45,8 +45,7 @@ Schedule of tile t (step = one K / V^T fragment + its FOUR MFMAs, 64 matrix cycl
 The rare block runs INSIDE phase 2, after some of its MFMAs: it scales O^T, l and the packed P(t) by alpha, so the tiles
 of O^T that already took P(t) V^T(t) and those that will take it stay consistent.
 """
-import os
-import sys
+from gen_common import Stmt, each_variant, lds_dma, main, vr
 
 MREG = 28
 P0 = 32
@@ -62,11 +61,8 @@ ONES_F16X2 = "0x3c003c00"
 COMPILER_VGPRS = MREG
 
 MF = "v_mfma_f32_16x16x32_f16"
-ABL = set()        # timing ablations (lab builds only; garbage results): "valu", "dma", "read", "wait", "bar"
-
-
-def vr(lo, n=1):
-    return f"v{lo}" if n == 1 else f"v[{lo}:{lo + n - 1}]"
+# timing ablations (lab builds only; garbage results): the common "read", "wait", "bar"; "dma"; "valu" (emit_gap)
+dma_m0, dma, advance = lds_dma(S_KG, S_VG, S_TC, S_TMP, KBYTES, VBYTES, KPIECE, 1024)
 
 
 def frag(slot):
@@ -89,34 +85,14 @@ def pfrag(qb):
     return vr(P0 + 4 * qb, 4)
 
 
-class Stmt:
-    def __init__(self):
-        self.lines = []
-
-    def add(self, s):
-        if "read" in ABL and s.startswith("ds_read"):
-            return
-        if "wait" in ABL and s.startswith("s_waitcnt lgkmcnt"):
-            return
-        if "bar" in ABL and s.startswith("s_barrier"):
-            return
-        self.lines.append(s)
-
-    def label(self, name):
-        self.lines.append(name + ":")
-
-    def text(self):
-        return "\n".join(f'      "{ln}\\n\\t"' for ln in self.lines)
-
-
 # ---- VALU items (strings; "valu" ablation drops them all, the test then never fires) ----
-def pk_arg(buf, k):
+def pk_arg(opt, buf, k):
     """s * c - m for elements 2k, 2k + 1 of the tile in `buf` (query block k >> 2), in place -> list of instructions.
     Two v_fma_f32, NOT one v_pk_fma_f32: packed-f32 and DOT instructions do not overlap with the matrix pipe on gfx950
     (benchmarks/lab/opsel_lab.hip: MFMA 16x16x32 + v_fma_f32 = 17 cycles per pair, + v_pk_fma_f32 / v_pk_add_f32 /
     v_dot2c_f32_f16 = 34), so a packed instruction costs three times what the two scalar ones cost beside MFMAs."""
     x, q = SBUF[buf] + 2 * k, k >> 2
-    if PK_ARGS:       # experiment switch (even query blocks only: the odd ones, m in the high register of its pair, came out wrong)
+    if opt.pk_args:   # experiment switch --pk-args (even query blocks only: the odd ones, m in the high register of its pair, came out wrong)
         if not q & 1:
             return [f"v_pk_fma_f32 {vr(x, 2)}, {vr(x, 2)}, s[{S_C}:{S_C + 1}], {vr(MREG + q, 2)} op_sel_hi:[1,1,0] neg_lo:[0,0,1] neg_hi:[0,0,1]"]
     return [f"v_fma_f32 v{x + i}, v{x + i}, s{S_C}, -v{MREG + q}" for i in range(2)]
@@ -130,16 +106,11 @@ def cvt_word(buf, w):
     return f"v_cvt_pk_f16_f32 v{P0 + w}, v{SBUF[buf] + 2 * w}, v{SBUF[buf] + 2 * w + 1}"
 
 
-SUM_BY_DOT2 = os.environ.get("R64X_SUM_BY_DOT2") == "1"    # experiment switches of the generator (not product options)
-PK_ARGS = os.environ.get("R64X_PK_ARGS") == "1"
-WAIT_EVERY_STEP = os.environ.get("R64X_WAIT_EVERY_STEP") == "1"
-
-
-def sum_word(w, buf):
+def sum_word(opt, w, buf):
     """row sum of the two exponentials of word w.  Two v_add_f32 on the f32 values: one v_dot2c_f32_f16 on the packed word
     measured 2711 instead of 2460 cycles per tile here, and the same 300 cycles in r64m when its row sums were moved to dot2
     (round 4) - DOT instructions wait for the matrix pipe (see pk_arg)."""
-    if SUM_BY_DOT2:
+    if opt.sum_by_dot2:                                   # experiment switch --sum-by-dot2
         return f"v_dot2c_f32_f16 %[l{w >> 2}], {ONES_F16X2}, v{P0 + w}"
     return (f"v_add_f32_e32 %[l{w >> 2}], %[l{w >> 2}], v{SBUF[buf] + 2 * w}\\n\\t"
             f"v_add_f32_e32 %[l{w >> 2}], %[l{w >> 2}], v{SBUF[buf] + 2 * w + 1}")
@@ -175,35 +146,11 @@ def read_for_step(n, slot):
     return "kaddr", ((slot + 2) % 3) * KBYTES + (n & 1) * 8 * KPIECE + (n >> 1) * 64
 
 
-def dma_m0(s, which, slot, i):
-    if "dma" in ABL:
-        return
-    imm = slot * (KBYTES if which == "k" else VBYTES) + i * (KPIECE if which == "k" else 1024)
-    s.add(f"s_add_i32 m0, %[{which}dst], {imm}")
-
-
-def dma(s, which, i):
-    if "dma" in ABL:
-        return
-    sg = S_KG if which == "k" else S_VG
-    s.add(f"global_load_lds_dwordx4 %[{which}off{i}], s[{sg}:{sg + 1}]")
-
-
-def advance(s, which):
-    if "dma" in ABL:
-        return
-    sg = S_KG if which == "k" else S_VG
-    s.add(f"s_cmp_lt_i32 s{S_TC}, %[{which}lim]")
-    s.add(f"s_cselect_b32 s{S_TMP}, %[{which}step], 0")
-    s.add(f"s_add_u32 s{sg}, s{sg}, s{S_TMP}")
-    s.add(f"s_addc_u32 s{sg + 1}, s{sg + 1}, 0")
-
-
 def ring_wait(s, n):
     """before step n uses ring slot n & 3.  Fragment reads are issued three steps ahead and return in order: at an EVEN step
     `lgkmcnt(1)` (all but the read issued last, fragment n + 2) covers fragments n AND n + 1, so the odd steps need no wait -
     16 instead of 32 s_waitcnt per tile, in a loop where every instruction beside the 128 MFMA issues costs its issue time."""
-    if WAIT_EVERY_STEP:
+    if s.opt.wait_every_step:                             # experiment switch --wait-every-step
         s.add("s_waitcnt lgkmcnt(2)")
     elif not n & 1:
         s.add("s_waitcnt lgkmcnt(1)")
@@ -214,9 +161,9 @@ def emit_gap(s, items):
         if it.startswith(".L") or it.startswith("s_cbranch"):
             if it.endswith(":"):
                 s.label(it[:-1])
-            elif "valu" not in ABL:                      # without the test there is nothing to branch on
+            elif "valu" not in s.abl:                      # without the test there is nothing to branch on
                 s.add(it)
-        elif "valu" not in ABL:
+        elif "valu" not in s.abl:
             s.add(it)
 
 
@@ -228,7 +175,7 @@ def tile(s, var):
     for f in range(16):
         gaps[4 * f + 0].append(exp_unit(cur, 16 + f))
         gaps[4 * f + 1].append(cvt_word(cur, f))          # words 8..15 follow their second exponential by >= one MFMA
-        adds = sum_word(f, cur).split("\\n\\t")
+        adds = sum_word(s.opt, f, cur).split("\\n\\t")
         if len(adds) == 2:                                # one VALU instruction per MFMA gap
             gaps[4 * f + 2].append(adds[0])
             gaps[4 * f + 3].append(adds[1])
@@ -263,9 +210,9 @@ def tile(s, var):
         if kind == "e":            # phase 1) go two to a gap: 23 + 16 + 16 + 8 = the 63 gaps of the phase
             seq.append(exp_unit(nxt, i))
         elif i < 8:
-            seq.extend(pk_arg(nxt, i))
+            seq.extend(pk_arg(s.opt, nxt, i))
         else:
-            seq.append("\\n\\t".join(pk_arg(nxt, i)))
+            seq.append("\\n\\t".join(pk_arg(s.opt, nxt, i)))
     gaps = [[] for _ in range(64)]
     pos = 1                                                # gap 0 stays empty: the last S^T MFMA must have written its tile
     for it in seq:
@@ -332,8 +279,8 @@ def rare_block(s):
     s.add("s_branch .Lr64x_back5_%=")
 
 
-def loop_stmt():
-    s = Stmt()
+def loop_stmt(opt):
+    s = Stmt(opt)
     s.add(f"s_mov_b64 s[{S_KG}:{S_KG + 1}], %[kg]")
     s.add(f"s_mov_b64 s[{S_VG}:{S_VG + 1}], %[vg]")
     s.add(f"s_mov_b32 s{S_TC}, 0")
@@ -360,9 +307,9 @@ def loop_stmt():
     return s
 
 
-def prologue_s0():
+def prologue_s0(opt):
     """S^T(0) into buffer 0 from K slot 0 (un-pipelined), then the lane-local maxima of the four query blocks"""
-    s = Stmt()
+    s = Stmt(opt)
     for f in range(3):
         s.add(f"ds_read_b128 {frag(f)}, %[kaddr] offset:{(f & 1) * 8 * KPIECE + (f >> 1) * 64}")
     for f in range(16):
@@ -382,10 +329,10 @@ def prologue_s0():
     return s
 
 
-def prologue_units():
+def prologue_units(opt):
     """m -> v[28:31]; s * c - m for all of tile 0 and its exp units 0..15 (what phase 2 of a tile does for the next one);
     the fragment ring primed with K(1) fragments 0..2"""
-    s = Stmt()
+    s = Stmt(opt)
     for f in range(3):
         s.add(f"ds_read_b128 {frag(f)}, %[kaddr] offset:{KBYTES + (f & 1) * 8 * KPIECE + (f >> 1) * 64}")
     for q in range(4):
@@ -400,14 +347,14 @@ def prologue_units():
 VARIANTS = [("", ()), ("novalu", ("valu",)), ("nobar", ("bar",)), ("mfmaonly", ("valu", "dma", "read", "wait"))]
 
 
-def emit_loop(w, sfx):
+def emit_loop(opt, w, sfx):
     w(f"// ---- the key-tile loop{sfx}: six tile variants, the rare rescale block, the drain")
     w(f"__device__ __forceinline__ void r64x_loop{sfx}(float& l0, float& l1, float& l2, float& l3, const char* kg, const char* vg, int nt,")
     w("    unsigned kaddr, unsigned vrel, const unsigned (&koff)[4], const unsigned (&voff)[4], float c, unsigned kdst, unsigned vdst,")
     w("    unsigned kstep, unsigned vstep, int klim, int vlim) {")
     w("  float a0, a1, a2, a3, t0, t1, t2, t3, t4;")
     w("  asm volatile(")
-    w(loop_stmt().text())
+    w(loop_stmt(opt).text())
     w('      : [l0] "+v"(l0), [l1] "+v"(l1), [l2] "+v"(l2), [l3] "+v"(l3), [a0] "=&v"(a0), [a1] "=&v"(a1), [a2] "=&v"(a2), [a3] "=&v"(a3),')
     w('        [t0] "=&v"(t0), [t1] "=&v"(t1), [t2] "=&v"(t2), [t3] "=&v"(t3), [t4] "=&v"(t4)')
     w('      : [kg] "s"(kg), [vg] "s"(vg), [nt] "s"(nt), [kaddr] "v"(kaddr), [vrel] "v"(vrel), [koff0] "v"(koff[0]), [koff1] "v"(koff[1]),')
@@ -418,7 +365,7 @@ def emit_loop(w, sfx):
     w("")
 
 
-def emit():
+def emit(opt):
     out, lab = [], []
     lab.append("// GENERATED by dvd_amd/csrc/gen_attn_r64x.py --lab - do not edit.  TIMING ABLATIONS of the r64x loop (lab builds only:")
     lab.append("// they compute garbage).")
@@ -441,7 +388,7 @@ def emit():
     w("")
     w("__device__ __forceinline__ void r64x_prologue_s0(unsigned kaddr, float& a0, float& a1, float& a2, float& a3) {")
     w("  asm volatile(")
-    w(prologue_s0().text())
+    w(prologue_s0(opt).text())
     w('      : [a0] "=&v"(a0), [a1] "=&v"(a1), [a2] "=&v"(a2), [a3] "=&v"(a3)')
     w('      : [kaddr] "v"(kaddr)')
     w('      : "memory");')
@@ -449,31 +396,18 @@ def emit():
     w("")
     w("__device__ __forceinline__ void r64x_prologue_units(unsigned kaddr, float c, float m0, float m1, float m2, float m3) {")
     w("  asm volatile(")
-    w(prologue_units().text())
+    w(prologue_units(opt).text())
     w('      :')
     w('      : [kaddr] "v"(kaddr), [c] "s"(c), [m0] "v"(m0), [m1] "v"(m1), [m2] "v"(m2), [m3] "v"(m3)')
     w('      : "memory");')
     w("}")
     w("")
-    for abl_name, abl in VARIANTS:
-        ABL.clear()
-        ABL.update(abl)
-        emit_loop(out.append if not abl_name else lab.append, "" if not abl_name else "_" + abl_name)
-    ABL.clear()
+    for o, sink, sfx in each_variant(opt, VARIANTS, out, lab):
+        emit_loop(o, sink, sfx)
     w("// clang-format on")
     lab.append("// clang-format on")
     return "\n".join(out) + "\n", "\n".join(lab) + "\n"
 
 
 if __name__ == "__main__":
-    here = os.path.dirname(os.path.abspath(__file__))
-    prod, lab = emit()
-    ppath = os.path.join(here, "attn_r64x_body.inc")
-    lpath = os.path.normpath(os.path.join(here, "..", "..", "benchmarks", "lab", "csrc", "attn_r64x_abl.inc"))
-    arg = sys.argv[1] if len(sys.argv) > 1 else ""
-    if arg == "--check":
-        sys.exit(0 if os.path.exists(ppath) and open(ppath).read() == prod else 1)
-    path, text = (lpath, lab) if arg == "--lab" else (ppath, prod)
-    if not (os.path.exists(path) and open(path).read() == text):      # identical content keeps its mtime (make)
-        open(path, "w").write(text)
-    print(f"wrote {path}: {text.count(chr(10))} lines")
+    main([("attn_r64x", emit)], ("sum-by-dot2", "pk-args", "wait-every-step"))

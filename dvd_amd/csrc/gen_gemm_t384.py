@@ -36,8 +36,7 @@ Register plan (two waves per SIMD: 256 registers per lane, which hipcc splits 12
   SGPR  s[80:85]   DMA source pointers (A, B) and the block counter (clobbers)
 The loop statement declares v[88:127] as clobbers.
 """
-import os
-import sys
+from gen_common import Stmt, each_variant, main
 
 HALF, BOFF, RING = 40960, 24576, 4
 SHIFT = 2 * HALF                   # the read bases reach two slots by immediates; the other two after a shift
@@ -45,9 +44,8 @@ AX, AY, BQ = 88, 100, 112
 S_A, S_B, S_CNT = 80, 82, 84
 SGPR_CLOBBERS = [f"s{i}" for i in range(80, 86)]
 MF = "v_mfma_f32_32x32x16_f16"
-ABL = set()        # timing ablations (lab builds only; garbage results): "dma", "read", "bar"
-# phase-2 MFMA gaps that carry an LDS-DMA piece (T384_PIECES: experiment switch of the generator, not a product option)
-PIECES_AFTER = tuple(int(x) for x in os.environ.get("T384_PIECES", "1,3,5,7,9").split(","))
+# timing ablations (lab builds only; garbage results): the common "read", "wait", "bar"; "dma"; "m16" (below)
+# --pieces (experiment switch of the generator, not a product option): the phase-2 MFMA gaps that carry an LDS-DMA piece
 
 
 def vq(lo):
@@ -81,7 +79,7 @@ def acc_pin(m, n):
 
 
 def mfma(e, m, n, a_quad, b_quad, first, phase):
-    if "m16" in ABL:
+    if "m16" in e.abl:
         for q in (2 * phase, 2 * phase + 1):
             d = acc_quad(m, n, q)
             e.add(f"v_mfma_f32_16x16x32_f16 {d}, {vq(a_quad)}, {vq(b_quad)}, {'0' if first else d}")
@@ -89,21 +87,15 @@ def mfma(e, m, n, a_quad, b_quad, first, phase):
         e.add(f"{MF} {acc(m, n)}, {vq(a_quad)}, {vq(b_quad)}, {'0' if first else acc(m, n)}")
 
 
-class Emit:
+class Emit(Stmt):
     """instruction list + the in-order LDS queue (counted lgkmcnt) + the shift state of the four read bases"""
 
-    def __init__(self):
-        self.lines = []
+    def __init__(self, opt):
+        super().__init__(opt)
         self.issued = 0            # LDS reads issued so far
         self.done = -1             # highest read sequence number known to have returned
         self.holder = {}           # fragment register quad -> sequence number of the read that fills it
         self.shift = {"fa0": 0, "fa1": 0, "fb0": 0, "fb1": 0}
-
-    def add(self, s):
-        self.lines.append(s)
-
-    def label(self, s):
-        self.lines.append(s + ":")
 
     def read(self, quad, base, slot, off):
         """ds_read_b128 of a fragment of the half slab in `slot`: base register (shifted by 2 slots when needed) + immediate"""
@@ -113,22 +105,17 @@ class Emit:
             self.shift[base] = want
         self.holder[quad] = self.issued
         self.issued += 1
-        if "read" not in ABL:
-            self.add(f"ds_read_b128 {vq(quad)}, %[{base}] offset:{(slot & 1) * HALF + off}")
+        self.add(f"ds_read_b128 {vq(quad)}, %[{base}] offset:{(slot & 1) * HALF + off}")
 
     def need(self, quad):
         q = self.holder[quad]
         if q > self.done:
-            if "read" not in ABL:
-                self.add(f"s_waitcnt lgkmcnt({self.issued - q - 1})")
+            self.add(f"s_waitcnt lgkmcnt({self.issued - q - 1})")
             self.done = q
-
-    def text(self):
-        return "\n".join(f'      "{ln}\\n\\t"' for ln in self.lines)
 
 
 def piece(e, i, slot):
-    if "dma" in ABL:
+    if "dma" in e.abl:
         return
     if i < 3:
         e.add(f"s_add_u32 m0, %[pda], {slot * HALF + i * 1024}")
@@ -169,9 +156,9 @@ def iteration(e, slot, first=False, dma=True, vm=5, last=False, barrier=None):
                 e.read(AY + 4 * k, "fa1", slot, 2048 * k)
             else:
                 e.read(BQ + 4 * k, "fb1", slot, 2048 * k)
-    if vm is not None and "dma" not in ABL:
+    if vm is not None and "dma" not in e.abl:
         e.add(f"s_waitcnt vmcnt({vm})")
-    if barrier and "bar" not in ABL:
+    if barrier:
         e.add("s_barrier")
     # ---- phase 2: k-step 1; reads of k-step 0 of the next slot; the pieces of half slab j + 3 -> slot (j - 1) % 4
     rd2 = {0: [("a", 0)], 2: [("b", 0)], 3: [("a", 1)], 4: [("a", 2)], 5: [("b", 1)], 8: [("b", 2)], 11: [("b", 3)]}
@@ -180,17 +167,17 @@ def iteration(e, slot, first=False, dma=True, vm=5, last=False, barrier=None):
         n, m = divmod(i, 3)
         e.need(AY + 4 * m)
         e.need(BQ + 4 * n)
-        mfma(e, m, n, AY + 4 * m, BQ + 4 * n, first and "m16" in ABL, 1)
+        mfma(e, m, n, AY + 4 * m, BQ + 4 * n, first and "m16" in e.abl, 1)
         if not last:
             for kind, k in rd2.get(i, ()):
                 if kind == "a":
                     e.read(AX + 4 * k, "fa0", nslot, 2048 * k)
                 else:
                     e.read(BQ + 4 * k, "fb0", nslot, 2048 * k)
-        if dma and i in PIECES_AFTER:
+        if dma and i in e.opt.pieces:
             piece(e, pc, (slot + RING - 1) % RING)
             pc += 1
-    if dma and "dma" not in ABL:
+    if dma and "dma" not in e.abl:
         e.add(f"s_add_u32 s{S_A}, s{S_A}, 64")
         e.add(f"s_addc_u32 s{S_A + 1}, s{S_A + 1}, 0")
         e.add(f"s_add_u32 s{S_B}, s{S_B}, 64")
@@ -240,17 +227,16 @@ def x_iteration(e, slot, first=False, dma=True, vm=5, last=False, barrier=None):
     nslot = (slot + 1) % RING
     pc = 0
     # (block, gap) of the wave's 5 pieces of half slab j + 3, and the block in front of which the barrier sits: experiment
-    # switches of the generator (T384X_PIECES, T384X_BAR), not product options.  Measured (profiles/r6_gemm_t384x_sched.txt,
+    # switches of the generator (--x-pieces, --x-bar), not product options.  Measured (profiles/r6_gemm_t384x_sched.txt,
     # f16 flavour, four shapes, two rounds): barrier before block 3 + a piece every 2nd gap 1177 / 1145 / 1194 TF/s (c1 / fc / c2);
     # before block 2 + a piece every 4th gap (this default) 1186-1194 / 1162-1174 / 1208-1215; before block 1 within 1 % of it.
-    pieces_at = {tuple(int(v) for v in it.split(".")) for it in os.environ.get("T384X_PIECES", "2.1,2.5,3.1,3.5,4.1").split(",")}
-    bar_at = int(os.environ.get("T384X_BAR", "2"))
+    pieces_at, bar_at = e.opt.x_pieces, e.opt.x_bar
     assert all(b >= bar_at for b, _ in pieces_at) and len(pieces_at) == 5
     for a in range(6):
         if a == bar_at:
-            if vm is not None and "dma" not in ABL:
+            if vm is not None and "dma" not in e.abl:
                 e.add(f"s_waitcnt vmcnt({vm})")
-            if barrier and "bar" not in ABL:
+            if barrier:
                 e.add("s_barrier")
         for n in range(8):
             e.need(AR + 4 * (a & 1))
@@ -266,16 +252,16 @@ def x_iteration(e, slot, first=False, dma=True, vm=5, last=False, barrier=None):
             if dma and (a, n) in pieces_at:
                 piece(e, pc, (slot + RING - 1) % RING)
                 pc += 1
-    if dma and "dma" not in ABL:
+    if dma and "dma" not in e.abl:
         e.add(f"s_add_u32 s{S_A}, s{S_A}, 64")
         e.add(f"s_addc_u32 s{S_A + 1}, s{S_A + 1}, 0")
         e.add(f"s_add_u32 s{S_B}, s{S_B}, 64")
         e.add(f"s_addc_u32 s{S_B + 1}, s{S_B + 1}, 0")
 
 
-def x_loop_stmt(xt=False):
+def x_loop_stmt(opt, xt=False):
     """the structure of loop_stmt (first block | steady block x nloop | final block; K = 128 (2 + nloop)) on x_iteration"""
-    e = Emit()
+    e = Emit(opt)
     e.add(f"s_mov_b64 s[{S_A}:{S_A + 1}], %[asrc]")
     e.add(f"s_mov_b64 s[{S_B}:{S_B + 1}], %[bsrc]")
     e.add(f"s_mov_b32 s{S_CNT}, %[nloop]")
@@ -297,16 +283,15 @@ def x_loop_stmt(xt=False):
     e.done = -1
     x_iteration(e, 0)
     if xt:
-        if "dma" not in ABL:
+        if "dma" not in e.abl:
             e.add(f"s_mov_b64 s[{S_A}:{S_A + 1}], %[anext]")
             e.add(f"s_mov_b64 s[{S_B}:{S_B + 1}], %[bnext]")
         x_iteration(e, 1)
         x_iteration(e, 2)
         x_iteration(e, 3, last=True, barrier=True)
-        if "dma" not in ABL:
+        if "dma" not in e.abl:
             e.add("s_waitcnt vmcnt(10)")
-        if "bar" not in ABL:
-            e.add("s_barrier")
+        e.add("s_barrier")
     else:
         x_iteration(e, 1, dma=False)
         x_iteration(e, 2, dma=False, vm=0)
@@ -316,14 +301,14 @@ def x_loop_stmt(xt=False):
     return e
 
 
-def emit_x_loop(w, sfx, xt=False):
+def emit_x_loop(opt, w, sfx, xt=False):
     name = f"t384x_loop{'_xt' if xt else ''}{sfx}"
     w(f"// ---- the 16x16x32 K loop {name}: acc[4 m + nb] = the 32 x 32 block (m, nb) as four 16 x 16 quads (2 mi + ni), written from 0")
     w(f"__device__ __forceinline__ void {name}(floatx16 (&acc)[12], const char* asrc, const char* bsrc, int nloop, unsigned pda,")
     w("    unsigned pdb, unsigned va0, unsigned va1, unsigned va2, unsigned vb0, unsigned vb1, unsigned fa0, unsigned fb0"
       + (", const char* anext, const char* bnext" if xt else "") + ") {")
     w("  asm volatile(")
-    w(x_loop_stmt(xt).text())
+    w(x_loop_stmt(opt, xt).text())
     w("      : " + ", ".join(f'[c{m}{n}] "=&{acc_pin(m, n)}"(acc[{4 * m + n}])' for m in range(3) for n in range(4)) + ",")
     w('        [fa0] "+v"(fa0), [fb0] "+v"(fb0)')
     w('      : [asrc] "s"(asrc), [bsrc] "s"(bsrc), [nloop] "s"(nloop), [pda] "s"(pda), [pdb] "s"(pdb), [va0] "v"(va0), [va1] "v"(va1),')
@@ -335,7 +320,7 @@ def emit_x_loop(w, sfx, xt=False):
     w("")
 
 
-def loop_stmt(xt=False):
+def loop_stmt(opt, xt=False):
     """first block (half slabs 0-3) | steady block x nloop | final block.  K = 128 (2 + nloop).
     xt = False: the tile's own prologue has put half slabs 0-2 into slots 0-2; the final block issues no pieces after its first
     iteration and its waits shrink with the queue.
@@ -343,7 +328,7 @@ def loop_stmt(xt=False):
     NEXT tile of this workgroup, whose half slabs 0, 1, 2 land in slots 0, 1, 2 while this tile's epilogue runs (LDS-free
     epilogues only); the statement ends with half slab 0 of the next tile landed for every wave (vmcnt(10) + barrier), so the
     next statement can prime its fragments at once."""
-    e = Emit()
+    e = Emit(opt)
     e.add(f"s_mov_b64 s[{S_A}:{S_A + 1}], %[asrc]")
     e.add(f"s_mov_b64 s[{S_B}:{S_B + 1}], %[bsrc]")
     e.add(f"s_mov_b32 s{S_CNT}, %[nloop]")
@@ -365,16 +350,15 @@ def loop_stmt(xt=False):
     e.done = -1
     iteration(e, 0)                               # issues the pieces of the last half slab
     if xt:
-        if "dma" not in ABL:
+        if "dma" not in e.abl:
             e.add(f"s_mov_b64 s[{S_A}:{S_A + 1}], %[anext]")
             e.add(f"s_mov_b64 s[{S_B}:{S_B + 1}], %[bnext]")
         iteration(e, 1)                           # ... of the NEXT tile's half slab 0 -> slot 0
         iteration(e, 2)                           # ... 1 -> slot 1
         iteration(e, 3, last=True, barrier=True)  # ... 2 -> slot 2 (after the barrier: every wave has left slot 2)
-        if "dma" not in ABL:
+        if "dma" not in e.abl:
             e.add("s_waitcnt vmcnt(10)")          # the next tile's half slab 0 has landed (its groups 1 and 2 stay in flight)
-        if "bar" not in ABL:
-            e.add("s_barrier")
+        e.add("s_barrier")
     else:
         iteration(e, 1, dma=False)                # outstanding: the two last groups -> vmcnt(5) still right
         iteration(e, 2, dma=False, vm=0)          # outstanding: the last group
@@ -384,19 +368,19 @@ def loop_stmt(xt=False):
     return e
 
 
-VARIANTS = [("", ()), ("nodma", ("dma",)), ("noread", ("read",)), ("nobar", ("bar",)), ("mfmaonly", ("dma", "read", "bar")),
-            ("m16", ("m16",))]
+VARIANTS = [("", ()), ("nodma", ("dma",)), ("noread", ("read", "wait")), ("nobar", ("bar",)),
+            ("mfmaonly", ("dma", "read", "wait", "bar")), ("m16", ("m16",))]
 
 
-def emit_loop(w, sfx, xt=False):
+def emit_loop(opt, w, sfx, xt=False):
     name = f"t384_loop{'_xt' if xt else ''}{sfx}"
     w(f"// ---- the K loop {name}: prime, first block, steady block, final block; acc[4 m + n] = accumulator (m, n), written from 0")
     w(f"__device__ __forceinline__ void {name}(floatx16 (&acc)[12], const char* asrc, const char* bsrc, int nloop, unsigned pda,")
     w("    unsigned pdb, unsigned va0, unsigned va1, unsigned va2, unsigned vb0, unsigned vb1, unsigned fa0, unsigned fa1, unsigned fb0,")
     w("    unsigned fb1" + (", const char* anext, const char* bnext" if xt else "") + ") {")
     w("  asm volatile(")
-    w(loop_stmt(xt).text())
-    if "m16" in ABL:
+    w(loop_stmt(opt, xt).text())
+    if "m16" in opt.abl:
         w("      : " + ", ".join(f'[c{m}{n}] "=&{acc_pin(m, n)}"(acc[{4 * m + n}])' for m in range(3) for n in range(4)) + ",")
     else:
         w("      : " + ", ".join(f'[c{m}{n}] "=&{"v" if m == 0 else "a"}"(acc[{4 * m + n}])' for m in range(3) for n in range(4)) + ",")
@@ -410,27 +394,19 @@ def emit_loop(w, sfx, xt=False):
     w("")
 
 
-def emit():
+def emit(opt):
     out, lab = [], []
     w = out.append
     w("// GENERATED by gen_gemm_t384.py - do not edit; see that file for the tile, the ring, the register plan and the schedule.")
     w("// clang-format off")
     w(f"#define T384_COMPILER_VGPRS {AX}   // the loop statement clobbers v[{AX}:127]; its 12 accumulators are \"=&a\" outputs")
     w("")
-    for name, abl in VARIANTS:
-        ABL.clear()
-        ABL.update(abl)
-        emit_loop(out.append if not name else lab.append, "" if not name else "_" + name)
-        emit_loop(out.append if not name else lab.append, "" if not name else "_" + name, xt=True)
-    ABL.clear()
-    emit_x_loop(out.append, "")
-    emit_x_loop(out.append, "", xt=True)
-    for name, abl in VARIANTS[1:5]:
-        ABL.clear()
-        ABL.update(abl)
-        emit_x_loop(lab.append, "_" + name)
-        emit_x_loop(lab.append, "_" + name, xt=True)
-    ABL.clear()
+    for o, sink, sfx in each_variant(opt, VARIANTS, out, lab):
+        emit_loop(o, sink, sfx)
+        emit_loop(o, sink, sfx, xt=True)
+    for o, sink, sfx in each_variant(opt, VARIANTS[:5], out, lab):      # the 16x16x32 loop has no "m16" ablation
+        emit_x_loop(o, sink, sfx)
+        emit_x_loop(o, sink, sfx, xt=True)
     w("// clang-format on")
     head = ["// GENERATED by dvd_amd/csrc/gen_gemm_t384.py --lab - do not edit.  TIMING ABLATIONS of the t384 K loop (lab builds only:",
             "// they compute garbage).", "// clang-format off"]
@@ -438,14 +414,4 @@ def emit():
 
 
 if __name__ == "__main__":
-    here = os.path.dirname(os.path.abspath(__file__))
-    prod, lab = emit()
-    ppath = os.path.join(here, "gemm_t384_body.inc")
-    lpath = os.path.normpath(os.path.join(here, "..", "..", "benchmarks", "lab", "csrc", "gemm_t384_abl.inc"))
-    arg = sys.argv[1] if len(sys.argv) > 1 else ""
-    if arg == "--check":
-        sys.exit(0 if os.path.exists(ppath) and open(ppath).read() == prod else 1)
-    path, text = (lpath, lab) if arg == "--lab" else (ppath, prod)
-    if not (os.path.exists(path) and open(path).read() == text):      # identical content keeps its mtime (make)
-        open(path, "w").write(text)
-    print(f"wrote {path}: {text.count(chr(10))} lines")
+    main([("gemm_t384", emit)], ("pieces", "x-pieces", "x-bar"))

@@ -8,6 +8,16 @@ import re
 from dvd_amd import lib
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
+CSRC = os.path.join(ROOT, "dvd_amd", "csrc")
+# the generators of the committed loop bodies (dvd_amd/csrc/*_body.inc) and the experiment switches each of them accepts, with
+# a non-default value that it can emit (gen_common.py: SWITCHES)
+GENERATORS = {
+    "gen_attn_r64m.py": [],
+    "gen_attn_r64x.py": [["--sum-by-dot2"], ["--pk-args"], ["--wait-every-step"]],
+    "gen_attn_h64m.py": [],
+    "gen_attn_h64x.py": [["--l-spread"], ["--sum-by-dot2"], ["--wait-every-step"]],
+    "gen_gemm_t384.py": [["--pieces", "0,2,4,6,8"], ["--x-pieces", "2.1,2.3,2.5,2.7,3.1"], ["--x-bar", "1"]],
+}
 
 
 def declared_symbols():
@@ -78,14 +88,64 @@ def test_header_is_plain_c():
 
 
 def test_generated_attention_body_is_current():
-    """dvd_amd/csrc/attn_r64m_body.inc (the hand-allocated tile loop of the decoder attention kernel) and attn_r64x_body.inc
-    (its 16x16x32-MFMA sibling, lab dispatch only) are GENERATED by gen_attn_r64{m,x}.py and committed: the committed files
-    must be what the committed generators write."""
+    """The hand-allocated loops are GENERATED and committed: dvd_amd/csrc/attn_r64x_body.inc (the decoder attention kernel,
+    flash_attn_r64x_kernel) and attn_h64x_body.inc / attn_h64l_body.inc (head_dim 64, flash_attn_h64x_kernel), attn_r64m_body.inc
+    and attn_h64m_body.inc (their 32x32x16-MFMA siblings, lab dispatch only) and gemm_t384_body.inc (gemm_nt_t384_kernel's K
+    loop).  The committed files must be what the committed generators write."""
+    for name in GENERATORS:
+        assert _gen(name, "--check").returncode == 0, f"run python3 dvd_amd/csrc/{name}"
+
+
+def _gen(name, *args, env=None):
     import subprocess
     import sys
-    for name in ("gen_attn_r64m.py", "gen_attn_r64x.py", "gen_attn_h64m.py", "gen_attn_h64x.py", "gen_gemm_t384.py"):
-        gen = os.path.join(ROOT, "dvd_amd", "csrc", name)
-        assert subprocess.run([sys.executable, gen, "--check"]).returncode == 0, f"run python3 dvd_amd/csrc/{name}"
+    return subprocess.run([sys.executable, os.path.join(CSRC, name), *args], env=env, capture_output=True, text=True)
+
+
+def _committed_bodies():
+    """name -> (content, mtime) of every generated file beside the generators"""
+    return {f: (open(os.path.join(CSRC, f), "rb").read(), os.stat(os.path.join(CSRC, f)).st_mtime_ns)
+            for f in sorted(os.listdir(CSRC)) if f.endswith(".inc")}
+
+
+def test_generators_ignore_the_environment():
+    """The experiment switches were environment variables once; a value left over from an A/B session must not reach a body."""
+    env = dict(os.environ, T384_PIECES="0,2,4,6,8", T384X_PIECES="2.1,2.5,3.1,3.5", T384X_BAR="3", H64X_L_SPREAD="1",
+               R64X_SUM_BY_DOT2="1", R64X_PK_ARGS="1", R64X_WAIT_EVERY_STEP="1")
+    for name in GENERATORS:
+        r = _gen(name, "--check", env=env)
+        assert r.returncode == 0, (name, r.stderr[-300:])
+    for name in list(GENERATORS) + ["gen_common.py"]:
+        assert not re.search(r"\benviron\b|getenv", open(os.path.join(CSRC, name)).read()), name
+
+
+@pytest.mark.parametrize("name,flag", [(n, f) for n, flags in GENERATORS.items() for f in flags], ids=lambda v: v if isinstance(v, str) else v[0])
+def test_generator_experiment_switch_cannot_touch_committed_bodies(name, flag, tmp_path):
+    """An experiment switch is refused with --check and without --out-dir (exit 2 = a usage error, not 1 = `stale`); with
+    --out-dir it writes there, something other than the committed bodies, and leaves those alone."""
+    before = _committed_bodies()
+    assert len(before) == 6
+    for extra in (["--check"], [], ["--lab"], ["--out-dir", CSRC]):
+        r = _gen(name, *flag, *extra)
+        assert r.returncode == 2 and "experiment switch" in r.stderr, (extra, r.returncode, r.stderr[-300:])
+    r = _gen(name, *flag, "--out-dir", str(tmp_path))
+    assert r.returncode == 0, r.stderr[-300:]
+    wrote = {f: (tmp_path / f).read_bytes() for f in os.listdir(tmp_path)}
+    assert wrote and set(wrote) <= set(before), sorted(wrote)
+    assert any(text != before[f][0] for f, text in wrote.items()), "the switch changed nothing"
+    assert _committed_bodies() == before
+
+
+def test_generator_rejects_flags_it_does_not_know():
+    """An unknown flag, an abbreviated one or a switch of another generator is an error - never ignored."""
+    theirs = [f for flags in GENERATORS.values() for f in flags]
+    before = _committed_bodies()
+    for name, mine in GENERATORS.items():
+        for flag in [["--bogus"], ["--l"], ["bogus"]] + [f for f in theirs if f[0] not in [m[0] for m in mine]]:
+            for extra in ([], ["--check"]):
+                r = _gen(name, *flag, *extra)
+                assert r.returncode == 2, (name, flag, extra, r.returncode, r.stderr[-300:])
+    assert _committed_bodies() == before
 
 
 def test_t384_gemm_kernel_resources(tmp_path):
@@ -133,9 +193,10 @@ def test_attention_kernel_register_contract(tmp_path):
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
     if not os.path.exists(hipcc):
         pytest.skip("no hipcc")
-    csrc = os.path.join(ROOT, "dvd_amd", "csrc")
-    for gen in ("gen_attn_r64m.py", "gen_attn_r64x.py", "gen_attn_h64m.py", "gen_attn_h64x.py"):   # the lab build's ablation bodies
-        subprocess.run([sys.executable, os.path.join(csrc, gen), "--lab"], check=True, stdout=subprocess.DEVNULL)
+    csrc = CSRC
+    for gen in GENERATORS:                              # the lab build's ablation bodies
+        if gen.startswith("gen_attn"):
+            subprocess.run([sys.executable, os.path.join(csrc, gen), "--lab"], check=True, stdout=subprocess.DEVNULL)
     sys.path.insert(0, csrc)
     import check_r64m_isa
     out = tmp_path / "attention.s"
