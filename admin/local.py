@@ -51,6 +51,7 @@ _DEFAULTS = {
     "grid_size": 64,         # coordinate grid G (reference: fixed 64)
     "batch_docs": 1,         # documents sampled together per GPU (reference: 1)
     "sampler": "ddim",       # 'ddim' | 'ddpm'
+    "unwarp_mode": "bilinear",   # interpolation of the full-resolution unwarp tail: 'bilinear' (reference) | 'bicubic'
     "num_synthetic_docs": 4,
     "full_res": (1024, 768), # synthetic full-resolution source size (H, W)
     "conditioning_dir": "",   # directory of per-document conditioning .npz files (skips ingest + pre-stage nets)

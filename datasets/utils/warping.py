@@ -6,7 +6,9 @@
 i.e. `F.grid_sample(img, grid.permute(0,2,3,1), mode='bilinear', padding_mode='zeros', align_corners=True)`.
 The modules hold no parameters and no compute of their own: `forward` hands the two device tensors to
 `dvd_grid_sample_bilinear_zeros_ac` (include/dvd_hip.h; LDS-tiled gather kernel, warp.hip) on the current HIP
-stream.  Like every product path there is no CPU route: host tensors are rejected."""
+stream - or, constructed with mode 'bicubic' (the reference forwards `mode` to F.grid_sample), to
+`dvd_grid_sample_bicubic_zeros_ac`.  'nearest' has no kernel and is refused at construction.  Like every product path
+there is no CPU route: host tensors are rejected."""
 from __future__ import annotations
 
 import torch
@@ -21,8 +23,9 @@ class SpatialTransformer2(nn.Module):
 
     def __init__(self, size, mode="bilinear"):
         super().__init__()
-        if mode != "bilinear":
-            raise NotImplementedError(f"mode {mode!r}: the sampling path warps bilinearly (gaussian_diffusion.py:20,218)")
+        if mode not in ("bilinear", "bicubic"):
+            raise NotImplementedError(f"mode {mode!r}: the warps are 'bilinear' (the sampling path, gaussian_diffusion.py:20,218) "
+                                      "and 'bicubic'")
         self.size, self.mode = tuple(size), mode      # `size` is unused by the reference's forward as well
 
     def forward(self, src, flow):
@@ -32,7 +35,7 @@ class SpatialTransformer2(nn.Module):
             raise ValueError(f"batch sizes differ: src {src.shape[0]}, flow {flow.shape[0]}")   # F.grid_sample's rule
         if flow.device != src.device:
             raise ValueError(f"src on {src.device}, flow on {flow.device}")
-        return ops.grid_sample(src.to(torch.float32).contiguous(), flow.to(torch.float32).contiguous())
+        return ops.grid_sample(src.to(torch.float32).contiguous(), flow.to(torch.float32).contiguous(), mode=self.mode)
 
 
 class register_model2(nn.Module):

@@ -839,6 +839,395 @@ __global__ void __launch_bounds__(256) unwarp_u8_band_kernel(const float* __rest
 }
 #endif  // DVD_LAB
 
+// ---------------------------------------------------------------------------------------
+// Bicubic warps: F.grid_sample(mode='bicubic', padding_mode='zeros', align_corners=True) and the u8 tail in that mode.
+//
+// ix = unnorm(gx, win), fx = floor(ix), t = ix - fx (exact in f32); taps are columns fx-1 .. fx+2 and rows fy-1 .. fy+2,
+// weighted per axis by the cubic-convolution kernel with A = -0.75: [c2(t+1), c1(t), c1(1-t), c2(2-t)],
+// c1(x) = ((A+2)x - (A+3))x^2 + 1, c2(x) = ((Ax - 5A)x + 8A)x - 4A.  A tap outside the plane contributes 0 (zeros padding
+// is per tap; the coordinate is not clipped).
+//
+// One pixel's taps are held as a WINDOW: 4 consecutive columns from cb = clamp(fx-1, 0, win-4) and 4 consecutive rows from
+// rb = clamp(fy-1, 0, hin-4), with the four weights of an axis shifted onto the window's slots (a slot no tap lands on, and
+// a slot beyond a plane narrower than 4, gets weight 0).  Away from the border the window IS the taps; at the border the
+// in-range taps keep their weights and the out-of-range ones vanish - zeros padding as weights, never as a branch round a
+// load - and a tap row is always 4 adjacent elements: one 16-byte read of an f32 plane, 12 adjacent bytes of an RGB image.
+// Every bicubic kernel (general, LDS-staged, the direct gather of a tile too large to stage, the u8 tail and the ragged u8
+// tail) builds its taps with make_ctaps and sums them with bicubic_sum, so a pixel has the same bits on every route.
+// ---------------------------------------------------------------------------------------
+struct CTaps {
+  int cb, rb;                  // first column / row of the window, clamped into the plane
+  float wx[4], wy[4];          // weights of the window's columns / rows
+};
+
+// The outer weights in factored form, c2(1+t) = A t (1-t)^2 and c2(2-t) = A (1-t) t^2: no cancellation (absolute error
+// <= 1.5 * 2^-24); the inner ones by Horner's rule (<= 5 * 2^-24, tests/test_bicubic_cpu.py derives both).
+__device__ __forceinline__ float cubic_inner(float x) { return fmaf(__fmul_rn(fmaf(1.25f, x, -2.25f), x), x, 1.f); }
+__device__ __forceinline__ float cubic_outer(float x, float y) { return __fmul_rn(__fmul_rn(__fmul_rn(-0.75f, x), y), y); }
+
+__device__ __forceinline__ void cubic_axis(float i, int size, int& base, float (&w)[4]) {
+  float f = floorf(i);
+  const float t = i - f, s = 1.f - t;
+  const float c0 = cubic_outer(t, s), c1 = cubic_inner(t), c2 = cubic_inner(s), c3 = cubic_outer(s, t);
+  // keep the int conversion safe for wild / non-finite coordinates
+  f = fminf(fmaxf(f, -3.f), (float)(size + 2));
+  if (!(i == i)) f = -3.f;
+  const int first = (int)f - 1;                                   // column of tap 0
+  base = min(max(first, 0), max(size - 4, 0));
+  const int sh = base - first;                                    // slot m holds tap m + sh
+  const bool nonfinite = !(fabsf(i) < __builtin_inff());
+#pragma unroll
+  for (int m = 0; m < 4; ++m) {
+    const int j = m + sh;
+    float v = (j == 0) ? c0 : ((j == 1) ? c1 : ((j == 2) ? c2 : ((j == 3) ? c3 : 0.f)));
+    if (base + m >= size) v = 0.f;                                // planes narrower than 4: the slot is no column at all
+    w[m] = nonfinite ? __builtin_nanf("") : v;                    // non-finite coordinate: NaN out, as F.grid_sample
+  }
+}
+
+__device__ __forceinline__ CTaps make_ctaps(float gx, float gy, int hin, int win) {
+  CTaps t;
+  cubic_axis(unnorm(gx, win), win, t.cb, t.wx);
+  cubic_axis(unnorm(gy, hin), hin, t.rb, t.wy);
+  return t;
+}
+
+// The 16-tap sum, separable: each window row is mul + 3 fma along x, the four row sums mul + 3 fma along y.
+__device__ __forceinline__ float bicubic_sum(const float (&v)[4][4], const float (&wx)[4], const float (&wy)[4]) {
+  float r[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+    r[i] = fmaf(v[i][3], wx[3], fmaf(v[i][2], wx[2], fmaf(v[i][1], wx[1], __fmul_rn(v[i][0], wx[0]))));
+  return fmaf(r[3], wy[3], fmaf(r[2], wy[2], fmaf(r[1], wy[1], __fmul_rn(r[0], wy[0]))));
+}
+
+// General kernel: any shape.  One thread per output pixel, every tap a scalar load at a clamped address.
+__global__ void __launch_bounds__(256) grid_sample_bicubic_nchw_kernel(const float* __restrict__ src,
+                                                                       const float* __restrict__ grid,
+                                                                       float* __restrict__ out, int c, int hin, int win,
+                                                                       int h, int w, int src_batch_div) {
+  const int n = blockIdx.z, y = blockIdx.y;
+  const int x = blockIdx.x * blockDim.x + threadIdx.x;
+  if (x >= w) return;
+  const size_t hw = (size_t)h * w;
+  const float* g = grid + (size_t)n * 2 * hw + (size_t)y * w + x;
+  const CTaps t = make_ctaps(g[0], g[hw], hin, win);
+  size_t ro[4];
+  int co[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    ro[i] = (size_t)min(t.rb + i, hin - 1) * win;
+    co[i] = min(t.cb + i, win - 1);
+  }
+  const size_t plane = (size_t)hin * win;
+  const float* s = src + (size_t)(n / src_batch_div) * c * plane;
+  float* o = out + (size_t)n * c * hw + (size_t)y * w + x;
+  for (int ch = 0; ch < c; ++ch) {
+    const float* p = s + (size_t)ch * plane;
+    float v[4][4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int m = 0; m < 4; ++m) v[i][m] = p[ro[i] + co[m]];
+    o[(size_t)ch * hw] = bicubic_sum(v, t.wx, t.wy);
+  }
+}
+
+// LDS-tiled kernel (win % 4 == 0, w % 4 == 0, planes < 4 GiB): the plan of grid_sample_lds_kernel - 32 x 32 output tiles
+// in XCD bands, 4 consecutive x per thread, 16-byte grid loads and output stores, LCG planes staged together - with the
+// footprint box reduced over the pixels' 4 x 4 windows.  A unit-scale tile touches 35 rows x 35 columns, at most 40 floats
+// wide once its origin is aligned down to 16 bytes: 1400 floats.  LCAP_C = 3072 floats per plane (a tile magnified 1.45 x
+// in each direction still stages): 3 * 3072 * 4 B = 36 KiB of LDS, which would allow 4 workgroups per CU; the kernel's
+// 157 VGPRs (four pixels' windows and weights beside nine float4 of staging) allow 3 workgroups (12 waves) per CU, so the
+// registers, not the LDS, set the occupancy - a smaller LCAP would buy nothing.  Holding it to 128 VGPRs spills (tried:
+// 24 VGPRs to scratch).  A tile whose box is larger gathers its window rows directly (16-byte loads).
+constexpr int LCAP_C = 3072;
+struct __attribute__((packed, aligned(4))) PackedF4 { float a, b, c, d; };
+
+__global__ void __launch_bounds__(256) grid_sample_bicubic_lds_kernel(
+    const float* __restrict__ src, const float* __restrict__ grid, float* __restrict__ out, int c, int hin, int win, int h,
+    int w, int src_batch_div, int ntx, int nty, unsigned tiles_total, unsigned tiles_per_xcd) {
+  constexpr int LCAP = LCAP_C;
+  __shared__ __attribute__((aligned(16))) float box[LCG * LCAP];
+  __shared__ int red[4][4];
+  // ---- tile of this workgroup (XCD bands) ----
+  const unsigned seq = blockIdx.x >> 3, xcd = blockIdx.x & 7u;
+  const unsigned tile = xcd * tiles_per_xcd + seq;
+  if (seq >= tiles_per_xcd || tile >= tiles_total) return;                  // workgroup-uniform
+  const unsigned per_img = (unsigned)ntx * (unsigned)nty;
+  const int n = (int)(tile / per_img);
+  const unsigned rem = tile - (unsigned)n * per_img;
+  const int ty = (int)(rem / (unsigned)ntx), tx = (int)(rem - (unsigned)ty * (unsigned)ntx);
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int x = tx * LTW + 4 * (tid % (LTW / 4)), y = ty * LTH + (tid / (LTW / 4));   // 4 consecutive pixels of one row
+  const size_t hw = (size_t)h * w;
+  const size_t plane = (size_t)hin * win;
+  const float* g = grid + (size_t)n * 2 * hw;                               // uniform
+  // a dead thread (beyond the right / bottom edge; w % 4 == 0) is clamped onto live pixels for the loads
+  const bool live = x < w && y < h;
+  const uint32_t poff = ((uint32_t)min(y, h - 1) * (uint32_t)w + (uint32_t)min(x, w - 4)) * 4u;
+  const float4 gx4 = load_f4(g, poff), gy4 = load_f4(g + hw, poff);
+  const float gxs[4] = {gx4.x, gx4.y, gx4.z, gx4.w}, gys[4] = {gy4.x, gy4.y, gy4.z, gy4.w};
+  CTaps t[4];
+  int xmin = win, xmax = 0, ymin = hin, ymax = 0;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    t[k] = make_ctaps(gxs[k], gys[k], hin, win);
+    xmin = min(xmin, t[k].cb); xmax = max(xmax, t[k].cb + 3);               // win >= 4: the window lies inside the row
+    ymin = min(ymin, t[k].rb); ymax = max(ymax, min(t[k].rb + 3, hin - 1));
+  }
+  xmin = wave_min(xmin); xmax = wave_max(xmax); ymin = wave_min(ymin); ymax = wave_max(ymax);
+  if (lane == 0) { red[wv][0] = xmin; red[wv][1] = xmax; red[wv][2] = ymin; red[wv][3] = ymax; }
+  __syncthreads();
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    xmin = min(xmin, red[i][0]); xmax = max(xmax, red[i][1]);
+    ymin = min(ymin, red[i][2]); ymax = max(ymax, red[i][3]);
+  }
+  xmin = __builtin_amdgcn_readfirstlane(xmin); xmax = __builtin_amdgcn_readfirstlane(xmax);
+  ymin = __builtin_amdgcn_readfirstlane(ymin); ymax = __builtin_amdgcn_readfirstlane(ymax);
+  const int x0a = xmin & ~3;                           // 16-byte aligned box origin (win % 4 == 0)
+  const int bw4 = ((xmax - x0a) >> 2) + 1;             // float4 per box row (x0a + 4 bw4 <= win)
+  const int bh = ymax - ymin + 1;
+  const int bw = bw4 * 4;                              // LDS row pitch (floats): the box is stored compactly
+  const int nvec = bh * bw4;
+  const bool staged = nvec * 4 <= LCAP && bw4 <= 64;   // workgroup-uniform
+  const float* s = src + (size_t)(n / src_batch_div) * c * plane;
+  float* o = out + (size_t)n * c * hw;
+
+  if (staged) {
+    // thread i moves float4 number i, i + 256, ... of each plane's [bh][bw4] image (row = i / bw4 by an exact reciprocal
+    // multiply: i < 1024, bw4 <= 64)
+    constexpr int ITER = (LCAP / 4 + 255) / 256;
+    const uint32_t inv = (65536u + (uint32_t)bw4 - 1u) / (uint32_t)bw4;      // uniform
+    uint32_t voff[ITER];
+    bool vok[ITER];
+#pragma unroll
+    for (int it = 0; it < ITER; ++it) {
+      const uint32_t idx = (uint32_t)tid + 256u * it;
+      const uint32_t row = (idx * inv) >> 16, c4 = idx - row * (uint32_t)bw4;
+      vok[it] = (int)idx < nvec;
+      voff[it] = vok[it] ? (row * (uint32_t)win + 4u * c4) * 4u : 0u;
+    }
+    const float* s0 = s + (size_t)ymin * win + x0a;                           // uniform
+    for (int ch0 = 0; ch0 < c; ch0 += LCG) {
+      float4 v[LCG][ITER];
+#pragma unroll
+      for (int j = 0; j < LCG; ++j) {
+        const float* pc = s0 + (size_t)min(ch0 + j, c - 1) * plane;           // uniform
+#pragma unroll
+        for (int it = 0; it < ITER; ++it) v[j][it] = load_f4(pc, voff[it]);
+      }
+      if (ch0) __syncthreads();                        // the previous channel group's taps have been read
+#pragma unroll
+      for (int j = 0; j < LCG; ++j)
+#pragma unroll
+        for (int it = 0; it < ITER; ++it)
+          if (vok[it]) *reinterpret_cast<float4*>(&box[j * LCAP + (tid + 256 * it) * 4]) = v[j][it];
+      __syncthreads();
+#pragma unroll
+      for (int j = 0; j < LCG; ++j) {
+        if (ch0 + j >= c) break;
+        float r[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          float tv[4][4];
+#pragma unroll
+          for (int i = 0; i < 4; ++i) {
+            const float* b = &box[j * LCAP + (min(t[k].rb + i, hin - 1) - ymin) * bw + (t[k].cb - x0a)];
+#pragma unroll
+            for (int m = 0; m < 4; ++m) tv[i][m] = b[m];
+          }
+          r[k] = bicubic_sum(tv, t[k].wx, t[k].wy);
+        }
+        if (live)
+          *reinterpret_cast<float4*>(reinterpret_cast<char*>(o + (size_t)(ch0 + j) * hw) + poff) = make_float4(r[0], r[1], r[2], r[3]);
+      }
+    }
+  } else {
+    // ---- footprint too large for LDS: direct gather for this tile, a window row per 16-byte load ----
+    for (int ch = 0; ch < c; ++ch) {
+      const float* pc = s + (size_t)ch * plane;                               // uniform
+      float r[4];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        float tv[4][4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const uint32_t off = ((uint32_t)min(t[k].rb + i, hin - 1) * (uint32_t)win + (uint32_t)t[k].cb) * 4u;
+          const PackedF4 q = *reinterpret_cast<const PackedF4*>(reinterpret_cast<const char*>(pc) + off);
+          tv[i][0] = q.a; tv[i][1] = q.b; tv[i][2] = q.c; tv[i][3] = q.d;
+        }
+        r[k] = bicubic_sum(tv, t[k].wx, t[k].wy);
+      }
+      if (live) store_f4_nt(o + (size_t)ch * hw, poff, make_float4(r[0], r[1], r[2], r[3]));
+    }
+  }
+}
+
+// The bicubic u8 tail of ONE document's 32 x 32 output tile (256 threads x 4 consecutive x); shared by
+// unwarp_u8_bicubic_kernel (one size per launch, one document per grid z) and unwarp_u8_bicubic_ragged_kernel (a flat grid
+// over all documents' tiles), so both give the same bytes.  The grid is flow_grid_at's - the bits of dvd_unwarp_grid; the
+// source is HWC u8, so a window row is 12 adjacent bytes.  The tile's byte footprint - rows ymin .. ymax, the bytes of
+// columns xmin .. xmax of each - is staged in LDS as aligned dwords (any w, any alignment of src: a dword that is not
+// wholly inside the image is put together from its bytes that are) and a window row is read back as 4 dwords + 3
+// v_alignbyte.  A unit-scale tile is 35 rows x 30 dwords = 4.2 KB; UCAP = 2048 dwords (8 KiB, no limit on occupancy).  A
+// larger box gathers its bytes directly.  The output is clamped to 0 .. 255 before the truncation: bicubic overshoots.
+constexpr int UCAP = 2048;
+
+__device__ __forceinline__ uint32_t bicubic_u8(float a) { return (uint32_t)(int)fminf(fmaxf(a, 0.f), 255.f); }
+
+__device__ __forceinline__ void unwarp_u8_bicubic_tile(const float* __restrict__ flow, const uint8_t* __restrict__ src,
+                                                       uint8_t* __restrict__ out, const UpParams& p, unsigned tx, unsigned ty) {
+  // + 4: a window row is read as 4 dwords, of which up to 2 lie beyond what the staging wrote - the next row's words or
+  // this pad.  Such a word is either dropped by v_alignbyte (the 4th dword when the window starts on a dword) or holds
+  // only bytes of slots whose weight is 0 (images narrower than 4 pixels); a byte converted to float is always finite, so
+  // weight 0 makes it contribute exactly 0 whatever the word holds.
+  __shared__ uint32_t img[UCAP + 4];
+  __shared__ int red[4][4];
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int x = (int)tx * 32 + 4 * (tid & 7), y = (int)ty * 32 + (tid >> 3);
+  CTaps t[4];
+  int xmin = p.w, xmax = 0, ymin = p.h, ymax = 0;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    float gx, gy;
+    flow_grid_at(flow, p, min(y, p.h - 1), min(x + k, p.w - 1), gx, gy);    // a pixel beyond the edge: a live one's taps
+    t[k] = make_ctaps(gx, gy, p.h, p.w);
+    xmin = min(xmin, t[k].cb); xmax = max(xmax, min(t[k].cb + 3, p.w - 1));
+    ymin = min(ymin, t[k].rb); ymax = max(ymax, min(t[k].rb + 3, p.h - 1));
+  }
+  xmin = wave_min(xmin); xmax = wave_max(xmax); ymin = wave_min(ymin); ymax = wave_max(ymax);
+  if (lane == 0) { red[wv][0] = xmin; red[wv][1] = xmax; red[wv][2] = ymin; red[wv][3] = ymax; }
+  __syncthreads();
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    xmin = min(xmin, red[i][0]); xmax = max(xmax, red[i][1]);
+    ymin = min(ymin, red[i][2]); ymax = max(ymax, red[i][3]);
+  }
+  xmin = __builtin_amdgcn_readfirstlane(xmin); xmax = __builtin_amdgcn_readfirstlane(xmax);
+  ymin = __builtin_amdgcn_readfirstlane(ymin); ymax = __builtin_amdgcn_readfirstlane(ymax);
+  const int rowbytes = (xmax - xmin + 1) * 3;
+  const int nd = (rowbytes + 6) >> 2;                  // dwords per staged row: 3 bytes of lead at most + the row's bytes
+  const int bh = ymax - ymin + 1;
+  const bool staged = nd <= 64 && bh * nd <= UCAP;     // workgroup-uniform
+  const size_t pitch = (size_t)p.w * 3;
+  uint32_t ob[12];
+  if (staged) {
+    // "virtual" byte offsets count from src - mis, the 4-byte aligned address at or below src
+    const size_t mis = (size_t)((uintptr_t)src & 3u), vend = mis + (size_t)p.h * pitch;
+    const uint8_t* sa = src - mis;
+    const size_t v0 = mis + (size_t)ymin * pitch + (size_t)xmin * 3;        // the box's first byte
+    const int shift = nd <= 32 ? 5 : 6;                // lanes per staged row: 32 or 64
+    const int kk = tid & ((1 << shift) - 1);
+    for (int r = tid >> shift; r < bh; r += 256 >> shift) {
+      const size_t vr = v0 + (size_t)r * pitch;        // the row's first byte; its dwords start at vr & ~3
+      const size_t q = (vr & ~(size_t)3) + 4u * (size_t)kk;
+      if (kk < nd && q < vr + (size_t)rowbytes) {
+        uint32_t d = 0;
+        if (q >= mis && q + 4 <= vend) {
+          d = *reinterpret_cast<const uint32_t*>(sa + q);
+        } else {                                       // the image's first / last dword: only the bytes inside it
+#pragma unroll
+          for (int b = 0; b < 4; ++b)
+            if (q + b >= mis && q + b < vend) d |= (uint32_t)sa[q + b] << (8 * b);
+        }
+        img[r * nd + kk] = d;
+      }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      uint32_t d[4][3];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int rr = min(t[k].rb + i, p.h - 1) - ymin;
+        const uint32_t lead = (uint32_t)((v0 + (size_t)rr * pitch) & 3u);
+        const uint32_t b = lead + (uint32_t)(t[k].cb - xmin) * 3u;          // byte position of the window in the staged row
+        const uint32_t* q = &img[rr * nd + (int)(b >> 2)];
+        const uint32_t q0 = q[0], q1 = q[1], q2 = q[2], q3 = q[3], sh = b & 3u;
+        d[i][0] = __builtin_amdgcn_alignbyte(q1, q0, sh);
+        d[i][1] = __builtin_amdgcn_alignbyte(q2, q1, sh);
+        d[i][2] = __builtin_amdgcn_alignbyte(q3, q2, sh);
+      }
+#pragma unroll
+      for (int ch = 0; ch < 3; ++ch) {
+        float tv[4][4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+          for (int m = 0; m < 4; ++m) tv[i][m] = (float)((d[i][(3 * m + ch) >> 2] >> (8 * ((3 * m + ch) & 3))) & 255u);
+        ob[k * 3 + ch] = bicubic_u8(bicubic_sum(tv, t[k].wx, t[k].wy));
+      }
+    }
+  } else {
+    // ---- footprint too large for LDS: every tap byte a load at a clamped address ----
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const uint8_t* q[4][4];
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int m = 0; m < 4; ++m)
+          q[i][m] = src + (size_t)min(t[k].rb + i, p.h - 1) * pitch + (size_t)min(t[k].cb + m, p.w - 1) * 3;
+#pragma unroll
+      for (int ch = 0; ch < 3; ++ch) {
+        float tv[4][4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+          for (int m = 0; m < 4; ++m) tv[i][m] = (float)q[i][m][ch];
+        ob[k * 3 + ch] = bicubic_u8(bicubic_sum(tv, t[k].wx, t[k].wy));
+      }
+    }
+  }
+  if (y >= p.h || x >= p.w) return;
+  uint8_t* o = out + ((size_t)y * p.w + x) * 3;
+  if (x + 3 < p.w && ((uintptr_t)o & 3u) == 0) {
+    PackedU3 v;
+    v.a = ob[0] | (ob[1] << 8) | (ob[2] << 16) | (ob[3] << 24);
+    v.b = ob[4] | (ob[5] << 8) | (ob[6] << 16) | (ob[7] << 24);
+    v.c = ob[8] | (ob[9] << 8) | (ob[10] << 16) | (ob[11] << 24);
+    *reinterpret_cast<PackedU3*>(o) = v;
+  } else {
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+      if (x + k < p.w) {
+        o[k * 3 + 0] = (uint8_t)ob[k * 3 + 0]; o[k * 3 + 1] = (uint8_t)ob[k * 3 + 1]; o[k * 3 + 2] = (uint8_t)ob[k * 3 + 2];
+      }
+  }
+}
+
+__global__ void __launch_bounds__(256) unwarp_u8_bicubic_kernel(const float* __restrict__ flow,
+                                                                const uint8_t* __restrict__ src, uint8_t* __restrict__ out,
+                                                                UpParams p) {
+  flow += (size_t)blockIdx.z * 2 * p.g * p.g;        // one document per grid z (batched launch)
+  src += (size_t)blockIdx.z * 3 * p.h * p.w;
+  out += (size_t)blockIdx.z * 3 * p.h * p.w;
+  unwarp_u8_bicubic_tile(flow, src, out, p, blockIdx.x, blockIdx.y);
+}
+
+// Documents of different sizes: a flat 1-D grid over the 32 x 32 tiles of all documents, as unwarp_u8_ragged_kernel.
+__global__ void __launch_bounds__(256) unwarp_u8_bicubic_ragged_kernel(const float* __restrict__ flow, int g, float scale,
+                                                                       RaggedTab tab, RaggedUp up) {
+  const unsigned tile = blockIdx.x;
+  const int d = ragged_doc_of(tab, tile);
+  UpParams p;
+  p.g = g;
+  p.h = tab.h[d];
+  p.w = tab.w[d];
+  p.sy = up.sy[d];
+  p.sx = up.sx[d];
+  p.sby = up.sby[d];
+  p.sbx = up.sbx[d];
+  p.scale = scale;
+  p.small = (p.h + p.w <= 128) ? 1 : 0;
+  const unsigned local = tile - (d ? tab.tile_end[d - 1] : 0u);
+  const unsigned ntx = ((unsigned)p.w + 31u) >> 5;
+  const unsigned ty = local / ntx, tx = local - ty * ntx;
+  unwarp_u8_bicubic_tile(flow + (size_t)d * 2 * g * g, tab.src[d], tab.out[d], p, tx, ty);
+}
+
 static UpParams make_up(int g, int h, int w, float scale) {
   UpParams p;
   p.g = g;
@@ -1015,16 +1404,21 @@ extern "C" int dvd_unwarp_u8(const float* flow, int g, const uint8_t* src_hwc, u
   return dvd_unwarp_u8_batch(flow, g, src_hwc, out_hwc, 1, h, w, scale, stream);
 }
 
-extern "C" int dvd_unwarp_u8_ragged(const float* flow, int g, const dvd_ragged_image* docs, int n, float scale,
-                                    void* stream) {
-  DVD_REQUIRE(flow && docs, "unwarp_u8_ragged: null pointer");
-  DVD_REQUIRE(n >= 0, "unwarp_u8_ragged: bad batch %d", n);
-  DVD_REQUIRE(g >= 2, "unwarp_u8_ragged: bad grid g=%d", g);
+// The ragged u8 tails (bilinear: 256-column x 4-row blocks, the block function chosen per document by u8_rows_shape;
+// bicubic: 32 x 32 tiles, one block function): every document is checked before the first launch, then up to kRaggedCap
+// documents and fewer than 2^31 blocks go into one launch of `kern` over a flat grid of tw x th blocks.
+typedef void (*ragged_u8_kernel_t)(const float*, int, float, RaggedTab, RaggedUp);
+
+static int launch_u8_ragged(const char* what, ragged_u8_kernel_t kern, int tw, int th, bool rows_rule, const float* flow, int g,
+                            const dvd_ragged_image* docs, int n, float scale, void* stream) {
+  DVD_REQUIRE(flow && docs, "%s: null pointer", what);
+  DVD_REQUIRE(n >= 0, "%s: bad batch %d", what, n);
+  DVD_REQUIRE(g >= 2, "%s: bad grid g=%d", what, g);
   for (int d = 0; d < n; ++d) {       // every document is checked before the first launch
-    DVD_REQUIRE(docs[d].src && docs[d].out, "unwarp_u8_ragged: null pointer in document %d", d);
-    DVD_REQUIRE(docs[d].h >= 1 && docs[d].w >= 1 && docs[d].h <= 65535, "unwarp_u8_ragged: bad shape h=%d w=%d of document %d",
+    DVD_REQUIRE(docs[d].src && docs[d].out, "%s: null pointer in document %d", what, d);
+    DVD_REQUIRE(docs[d].h >= 1 && docs[d].w >= 1 && docs[d].h <= 65535, "%s: bad shape h=%d w=%d of document %d", what,
                 docs[d].h, docs[d].w, d);
-    DVD_REQUIRE((size_t)cdiv(docs[d].w, 256) * cdiv(docs[d].h, 4) < (1ull << 31), "unwarp_u8_ragged: document %d too large", d);
+    DVD_REQUIRE((size_t)cdiv(docs[d].w, tw) * cdiv(docs[d].h, th) < (1ull << 31), "%s: document %d too large", what, d);
   }
   for (int d0 = 0; d0 < n;) {
     // one launch: up to kRaggedCap documents and fewer than 2^31 blocks
@@ -1034,24 +1428,71 @@ extern "C" int dvd_unwarp_u8_ragged(const float* flow, int g, const dvd_ragged_i
     int m = 0;
     for (; m < kRaggedCap && d0 + m < n; ++m) {
       const dvd_ragged_image& im = docs[d0 + m];
-      const size_t t = (size_t)cdiv(im.w, 256) * cdiv(im.h, 4);
+      const size_t t = (size_t)cdiv(im.w, tw) * cdiv(im.h, th);
       if (tiles + t >= (1ull << 31)) break;
       tiles += t;
       const UpParams p = make_up(g, im.h, im.w, scale);
       tab.src[m] = im.src; tab.out[m] = im.out; tab.h[m] = im.h; tab.w[m] = im.w; tab.tile_end[m] = (unsigned)tiles;
       up.sy[m] = p.sy; up.sx[m] = p.sx; up.sby[m] = p.sby; up.sbx[m] = p.sbx;
-      up.fast[m] = u8_rows_shape(im.h, im.w) ? 1 : 0;
+      up.fast[m] = (rows_rule && u8_rows_shape(im.h, im.w)) ? 1 : 0;
     }
     for (int k = m; k < kRaggedCap; ++k) {    // unused entries: defined values in the kernel argument
       tab.src[k] = nullptr; tab.out[k] = nullptr; tab.h[k] = tab.w[k] = 0; tab.tile_end[k] = (unsigned)tiles;
       up.sy[k] = up.sx[k] = up.sby[k] = up.sbx[k] = 0.f; up.fast[k] = 0;
     }
     tab.n = m;
-    unwarp_u8_ragged_kernel<<<(unsigned)tiles, 256, 0, (hipStream_t)stream>>>(flow + (size_t)d0 * 2 * g * g, g, scale, tab, up);
-    if (int e = check_launch("unwarp_u8_ragged")) return e;
+    kern<<<(unsigned)tiles, 256, 0, (hipStream_t)stream>>>(flow + (size_t)d0 * 2 * g * g, g, scale, tab, up);
+    if (int e = check_launch(what)) return e;
     d0 += m;
   }
   return DVD_OK;
+}
+
+extern "C" int dvd_unwarp_u8_ragged(const float* flow, int g, const dvd_ragged_image* docs, int n, float scale,
+                                    void* stream) {
+  return launch_u8_ragged("unwarp_u8_ragged", unwarp_u8_ragged_kernel, 256, 4, true, flow, g, docs, n, scale, stream);
+}
+
+// ---- bicubic: the drop-in grid_sample and the u8 tail (batched / ragged); kernels chosen by shape only ----
+extern "C" int dvd_grid_sample_bicubic_zeros_ac(const float* src, const float* grid, float* out, int n, int c, int hin,
+                                                int win, int h, int w, int src_batch_div, void* stream) {
+  DVD_REQUIRE(src && grid && out, "grid_sample_bicubic: null pointer");
+  DVD_REQUIRE(n >= 0 && c > 0 && hin > 0 && win > 0 && h > 0 && w > 0 && src_batch_div > 0,
+              "grid_sample_bicubic: bad shape n=%d c=%d in=%dx%d out=%dx%d", n, c, hin, win, h, w);
+  if (n == 0) return DVD_OK;
+  DVD_REQUIRE(h <= 65535 && n <= 65535, "grid_sample_bicubic: h or n exceeds the 65535 grid limit");
+  const bool planes32 = (size_t)hin * win * 4 < (1ull << 32) && (size_t)h * w * 4 < (1ull << 32);
+  if (win >= 4 && win % 4 == 0 && w % 4 == 0 && ((uintptr_t)src % 16) == 0 && ((uintptr_t)grid % 16) == 0 &&
+      ((uintptr_t)out % 16) == 0 && planes32) {
+    const int ntx = cdiv(w, LTW), nty = cdiv(h, LTH);
+    const size_t total = (size_t)ntx * nty * n;
+    DVD_REQUIRE(total < (1ull << 31) - 8, "grid_sample_bicubic: too many tiles");
+    const unsigned per_xcd = (unsigned)((total + 7) / 8);
+    grid_sample_bicubic_lds_kernel<<<per_xcd * 8u, 256, 0, (hipStream_t)stream>>>(src, grid, out, c, hin, win, h, w, src_batch_div,
+                                                                                  ntx, nty, (unsigned)total, per_xcd);
+    return check_launch("grid_sample_bicubic(lds)");
+  }
+  const int bx = w >= 256 ? 256 : (w > 64 ? 128 : 64);
+  dim3 grd(cdiv(w, bx), h, n);
+  grid_sample_bicubic_nchw_kernel<<<grd, bx, 0, (hipStream_t)stream>>>(src, grid, out, c, hin, win, h, w, src_batch_div);
+  return check_launch("grid_sample_bicubic");
+}
+
+extern "C" int dvd_unwarp_u8_bicubic_batch(const float* flow, int g, const uint8_t* src_hwc, uint8_t* out_hwc, int n, int h,
+                                           int w, float scale, void* stream) {
+  if (int e = unwarp_args(flow, src_hwc, out_hwc, g, h, w)) return e;
+  DVD_REQUIRE(n >= 0 && n <= 65535, "unwarp: bad batch %d", n);
+  DVD_REQUIRE((size_t)cdiv(w, 32) < (1ull << 31), "unwarp: w too large");
+  if (n == 0) return DVD_OK;
+  dim3 grd(cdiv(w, 32), cdiv(h, 32), n);
+  unwarp_u8_bicubic_kernel<<<grd, 256, 0, (hipStream_t)stream>>>(flow, src_hwc, out_hwc, make_up(g, h, w, scale));
+  return check_launch("unwarp_u8_bicubic");
+}
+
+extern "C" int dvd_unwarp_u8_bicubic_ragged(const float* flow, int g, const dvd_ragged_image* docs, int n, float scale,
+                                            void* stream) {
+  return launch_u8_ragged("unwarp_u8_bicubic_ragged", unwarp_u8_bicubic_ragged_kernel, 32, 32, false, flow, g, docs, n, scale,
+                          stream);
 }
 
 #ifdef DVD_LAB

@@ -149,11 +149,14 @@ def run_evaluation_docunet(settings, logger, val_loader, diffusion, model, pretr
     `val_loader` yields the reference's dicts or this package's documents (`documents_of`); `env.batch_docs` documents are
     batched per pass (the reference: 1): ingest + the three pre-stage nets for documents that arrive as images
     (:162-216), the sampler (:247-265), then the tail (:301-306 + visualization_utils.py:75-77) as ONE fused u8 launch per
-    batch (documents of one size or of different sizes alike), and - if env.visualize - `visualize_dewarping` writes the PNG where the reference writes it.
+    batch (documents of one size or of different sizes alike; env.unwarp_mode 'bilinear' | 'bicubic' is its interpolation), and - if env.visualize - `visualize_dewarping` writes the PNG where the reference writes it.
     The pre-stage models may all be None when every document carries ready conditioning tensors.
     Returns [(path, uint8 [H,W,3] device tensor)] (the reference returns None)."""
     from utils_flow.visualization_utils import visualize_dewarping
     env = settings.env
+    unwarp_mode = getattr(env, "unwarp_mode", "bilinear")       # the interpolation of the full-resolution tail
+    if unwarp_mode not in ("bilinear", "bicubic"):
+        raise ValueError(f"env.unwarp_mode must be 'bilinear' or 'bicubic', got {unwarp_mode!r}")
     device = next(model.parameters()).device
     nets = (pretrained_dewarp_model, pretrained_seg_model, pretrained_line_seg_model)
     prestage_models = None if all(m is None for m in nets) else nets
@@ -188,18 +191,26 @@ def run_evaluation_docunet(settings, logger, val_loader, diffusion, model, pretr
         times.append((time.time() - t0) / nb)
         # :301-306 + viz :75-77 - one launch for the batch when its documents are byte images
         if all("src_u8" in d for d in batch) and len({tuple(d["src_u8"].shape) for d in batch}) == 1:
-            outs = ops.unwarp_u8_batch(flow.contiguous(), stack("src_u8"))
+            outs = ops.unwarp_u8_batch(flow.contiguous(), stack("src_u8"), mode=unwarp_mode)
         else:
             # byte images of different sizes: still one launch (the ragged tail); a float source that is not a byte image
-            # takes the fused f32 tail on its own, truncated like numpy's astype(uint8)
+            # takes the fused f32 tail on its own, truncated like numpy's astype(uint8) (bicubic: the grid and the f32
+            # drop-in kernel, clamped to 0..255 first - bicubic overshoots)
             outs = [None] * nb
             u8 = [j for j, d in enumerate(batch) if "src_u8" in d]
             if u8:
                 fl = flow.contiguous() if len(u8) == nb else flow[u8].contiguous()
-                for j, out in zip(u8, ops.unwarp_u8_ragged(fl, [dev_t(batch[j]["src_u8"]).contiguous() for j in u8])):
+                for j, out in zip(u8, ops.unwarp_u8_ragged(fl, [dev_t(batch[j]["src_u8"]).contiguous() for j in u8],
+                                                             mode=unwarp_mode)):
                     outs[j] = out
             for j, d in enumerate(batch):
-                if outs[j] is None:
+                if outs[j] is None and unwarp_mode == "bicubic":
+                    vis = d["source_vis"].to(device).float()[None].contiguous()
+                    grid = ops.unwarp_grid(flow[j:j + 1].contiguous(), vis.shape[-2], vis.shape[-1])
+                    f32 = ops.grid_sample(vis, grid, mode="bicubic")[0]
+                    # NaN (a non-finite grid value) -> 0, as the u8 kernels give; then np.clip(a, 0, 255).astype(uint8)
+                    outs[j] = th.nan_to_num(f32, nan=0.0).clamp(0, 255).to(th.uint8).permute(1, 2, 0).contiguous()
+                elif outs[j] is None:
                     outs[j] = ops.unwarp_f32(flow[j:j + 1].contiguous(),
                                              d["source_vis"].to(device).float()[None].contiguous()).to(th.uint8)
         for j, d in enumerate(batch):

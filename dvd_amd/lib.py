@@ -96,6 +96,10 @@ SIGNATURES = {
     "dvd_unwarp_u8_batch": [c_void, C.c_int, c_void, c_void, C.c_int, C.c_int, C.c_int, C.c_float, c_void],
     "dvd_unwarp_grid": [c_void, C.c_int, c_void, C.c_int, C.c_int, C.c_float, c_void],
     "dvd_unwarp_u8_ragged": [c_void, C.c_int, C.POINTER(RaggedImage), C.c_int, C.c_float, c_void],
+    "dvd_grid_sample_bicubic_zeros_ac": [c_void, c_void, c_void, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                         C.c_int, C.c_int, c_void],
+    "dvd_unwarp_u8_bicubic_batch": [c_void, C.c_int, c_void, c_void, C.c_int, C.c_int, C.c_int, C.c_float, c_void],
+    "dvd_unwarp_u8_bicubic_ragged": [c_void, C.c_int, C.POINTER(RaggedImage), C.c_int, C.c_float, c_void],
     "dvd_sched_step": [C.POINTER(SchedCoef), c_void, c_void, c_void, c_void, c_void, C.c_int, C.c_int, c_void],
     "dvd_sched_step_clip": [C.POINTER(SchedCoef), c_void, c_void, c_void, c_void, c_void, C.c_int, C.c_int, c_void],
     "dvd_hyp_mean_clamp": [c_void, c_void, C.c_int, C.c_int, C.c_int, c_void],

@@ -24,15 +24,27 @@ def _chk(t: torch.Tensor, dtype, name):
         raise lib.DvdError(f"{name}: expected contiguous {dtype}, got {t.dtype} contiguous={t.is_contiguous()}")
 
 
-def grid_sample(src: torch.Tensor, grid_nchw: torch.Tensor, src_batch_div: int = 1) -> torch.Tensor:
+_WARP_MODES = ("bilinear", "bicubic")
+
+
+def _warp_mode(mode, name):
+    """The interpolation of a warp: checked before anything is allocated or launched."""
+    if mode not in _WARP_MODES:
+        raise ValueError(f"{name}: mode must be 'bilinear' or 'bicubic', got {mode!r}")
+    return mode == "bicubic"
+
+
+def grid_sample(src: torch.Tensor, grid_nchw: torch.Tensor, src_batch_div: int = 1, mode: str = "bilinear") -> torch.Tensor:
+    """F.grid_sample(src, grid, mode, padding_mode='zeros', align_corners=True); mode 'bilinear' | 'bicubic'."""
+    cubic = _warp_mode(mode, "grid_sample")
     _chk(src, torch.float32, "src")
     _chk(grid_nchw, torch.float32, "grid")
     n, two, h, w = grid_nchw.shape
     ns, c, hin, win = src.shape
     assert two == 2 and ns * src_batch_div == n
     out = torch.empty((n, c, h, w), dtype=torch.float32, device=src.device)
-    lib.call("dvd_grid_sample_bilinear_zeros_ac", ptr(src), ptr(grid_nchw), ptr(out), n, c, hin, win, h, w,
-             src_batch_div, stream_ptr())
+    lib.call("dvd_grid_sample_bicubic_zeros_ac" if cubic else "dvd_grid_sample_bilinear_zeros_ac", ptr(src), ptr(grid_nchw),
+             ptr(out), n, c, hin, win, h, w, src_batch_div, stream_ptr())
     return out
 
 
@@ -54,25 +66,32 @@ def unwarp_f32(flow: torch.Tensor, src_chw: torch.Tensor, scale: float = 0.987) 
     return out
 
 
-def unwarp_u8(flow: torch.Tensor, src_hwc: torch.Tensor, scale: float = 0.987) -> torch.Tensor:
-    """flow [1,2,G,G]; src [H,W,3] uint8 -> [H,W,3] uint8 (truncated like numpy astype)."""
+def unwarp_u8(flow: torch.Tensor, src_hwc: torch.Tensor, scale: float = 0.987, mode: str = "bilinear") -> torch.Tensor:
+    """flow [1,2,G,G]; src [H,W,3] uint8 -> [H,W,3] uint8 (truncated like numpy astype; mode='bicubic': clamped to 0..255
+    first, np.clip(a, 0, 255).astype(uint8))."""
+    cubic = _warp_mode(mode, "unwarp_u8")
     _chk(flow, torch.float32, "flow")
     _chk(src_hwc, torch.uint8, "src")
     h, w = src_hwc.shape[:2]
     out = torch.empty_like(src_hwc)
-    lib.call("dvd_unwarp_u8", ptr(flow), flow.shape[-1], ptr(src_hwc), ptr(out), h, w, C.c_float(scale), stream_ptr())
+    if cubic:
+        lib.call("dvd_unwarp_u8_bicubic_batch", ptr(flow), flow.shape[-1], ptr(src_hwc), ptr(out), 1, h, w, C.c_float(scale),
+                 stream_ptr())
+    else:
+        lib.call("dvd_unwarp_u8", ptr(flow), flow.shape[-1], ptr(src_hwc), ptr(out), h, w, C.c_float(scale), stream_ptr())
     return out
 
 
-def unwarp_u8_batch(flow: torch.Tensor, src_nhwc: torch.Tensor, scale: float = 0.987) -> torch.Tensor:
+def unwarp_u8_batch(flow: torch.Tensor, src_nhwc: torch.Tensor, scale: float = 0.987, mode: str = "bilinear") -> torch.Tensor:
     """flow [B,2,G,G]; src [B,H,W,3] uint8 -> [B,H,W,3] uint8: the batch's documents in ONE launch."""
+    cubic = _warp_mode(mode, "unwarp_u8_batch")
     _chk(flow, torch.float32, "flow")
     _chk(src_nhwc, torch.uint8, "src")
     b, h, w, three = src_nhwc.shape
     assert three == 3 and flow.shape[0] == b and flow.shape[1] == 2
     out = torch.empty_like(src_nhwc)
-    lib.call("dvd_unwarp_u8_batch", ptr(flow), flow.shape[-1], ptr(src_nhwc), ptr(out), b, h, w, C.c_float(scale),
-             stream_ptr())
+    lib.call("dvd_unwarp_u8_bicubic_batch" if cubic else "dvd_unwarp_u8_batch", ptr(flow), flow.shape[-1], ptr(src_nhwc),
+             ptr(out), b, h, w, C.c_float(scale), stream_ptr())
     return out
 
 
@@ -94,10 +113,11 @@ def _ragged_table(srcs, outs):
     return tab
 
 
-def unwarp_u8_ragged(flow: torch.Tensor, srcs, scale: float = 0.987):
+def unwarp_u8_ragged(flow: torch.Tensor, srcs, scale: float = 0.987, mode: str = "bilinear"):
     """flow [n,2,G,G]; srcs: n [h_d,w_d,3] uint8 tensors of ANY sizes -> n uint8 tensors, each the bytes of
-    unwarp_u8(flow[d:d+1], srcs[d]): the batch's documents in ONE launch (per lib.RAGGED_CAP documents).  The outputs are
-    views of one allocation."""
+    unwarp_u8(flow[d:d+1], srcs[d], mode=mode): the batch's documents in ONE launch (per lib.RAGGED_CAP documents).  The
+    outputs are views of one allocation."""
+    cubic = _warp_mode(mode, "unwarp_u8_ragged")
     _chk(flow, torch.float32, "flow")
     srcs = list(srcs)
     assert flow.dim() == 4 and flow.shape[0] == len(srcs) and flow.shape[1] == 2
@@ -107,8 +127,8 @@ def unwarp_u8_ragged(flow: torch.Tensor, srcs, scale: float = 0.987):
     if not srcs:
         return []
     outs = [o.view(s.shape) for o, s in zip(_carve([s.numel() for s in srcs], flow.device), srcs)]
-    lib.call("dvd_unwarp_u8_ragged", ptr(flow), flow.shape[-1], _ragged_table(srcs, outs), len(srcs), C.c_float(scale),
-             stream_ptr())
+    lib.call("dvd_unwarp_u8_bicubic_ragged" if cubic else "dvd_unwarp_u8_ragged", ptr(flow), flow.shape[-1],
+             _ragged_table(srcs, outs), len(srcs), C.c_float(scale), stream_ptr())
     return outs
 
 

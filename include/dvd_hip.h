@@ -83,6 +83,29 @@ int dvd_unwarp_u8_ragged(const float* flow, int g, const dvd_ragged_image* docs,
 /* Materialise the full-resolution sampling grid only ([2,H,W] f32), i.e. evaluation.py:301-306. */
 int dvd_unwarp_grid(const float* flow, int g, float* grid_out, int h, int w, float scale, void* stream);
 
+/* The same warps with mode='bicubic': F.grid_sample(src, grid, mode='bicubic', padding_mode='zeros',
+ * align_corners=True).  Each entry point takes the parameters of its bilinear sibling above.
+ *   ix = (gx + 1) * ((Win - 1) / 2) in f32 (the bilinear warps' unnormalisation), fx = floor(ix), tx = ix - fx; y alike.
+ *   Taps: columns fx-1 .. fx+2, rows fy-1 .. fy+2.  A tap outside [0,Win) x [0,Hin) contributes 0: zeros padding is per
+ *   tap, the coordinate is not clipped.
+ *   Weights per axis, A = -0.75: w = [c2(t+1), c1(t), c1(1-t), c2(2-t)] with c1(x) = ((A+2)x - (A+3))x^2 + 1 and
+ *   c2(x) = ((Ax - 5A)x + 8A)x - 4A;  out = sum_i sum_j wy[i] wx[j] v[i][j], accumulated in f32 by ONE device function on
+ *   every kernel route, so a pixel has the same bits whichever kernel its shape selects.
+ *   A non-finite grid value gives NaN in the f32 output and 0 in the u8 output; no grid value makes a kernel read outside
+ *   src.
+ *   u8 output = (uint8_t)(int)fminf(fmaxf(a, 0), 255): clamped, then truncated - np.clip(a, 0, 255).astype(np.uint8).
+ *   Bicubic overshoots (about -56 .. 297 on random bytes), so unlike the bilinear tail the clamp is part of the result.
+ * dvd_unwarp_u8_bicubic_batch: the grid of each pixel is dvd_unwarp_grid's, bit for bit; out equals the clamp of
+ * dvd_grid_sample_bicubic_zeros_ac on the same image as f32 planes, byte for byte.  dvd_unwarp_u8_bicubic_ragged:
+ * docs[d].out == dvd_unwarp_u8_bicubic_batch(flow + d*2*G*G, g, docs[d].src, docs[d].out, 1, h_d, w_d, scale) byte for
+ * byte; at most DVD_RAGGED_CAP documents per launch, as dvd_unwarp_u8_ragged. */
+int dvd_grid_sample_bicubic_zeros_ac(const float* src, const float* grid, float* out,
+                                     int n, int c, int hin, int win, int h, int w,
+                                     int src_batch_div, void* stream);
+int dvd_unwarp_u8_bicubic_batch(const float* flow, int g, const uint8_t* src_hwc, uint8_t* out_hwc,
+                                int n, int h, int w, float scale, void* stream);
+int dvd_unwarp_u8_bicubic_ragged(const float* flow, int g, const dvd_ragged_image* docs, int n, float scale, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Scheduler step (idf/gaussian_diffusion.py:434-438,445-491 ddim_sample; :270-292 posterior
  * mean for the DDPM variant).  One fused elementwise kernel over [n_elem] floats:
