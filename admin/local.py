@@ -52,6 +52,10 @@ _DEFAULTS = {
     "batch_docs": 1,         # documents sampled together per GPU (reference: 1)
     "sampler": "ddim",       # 'ddim' | 'ddpm'
     "unwarp_mode": "bilinear",   # interpolation of the full-resolution unwarp tail: 'bilinear' (reference) | 'bicubic'
+    # directory of ground-truth scans `<stem>.png`: when set, every dewarped page is scored against its scan with MS-SSIM
+    # (ops.ms_ssim_u8; "" = no scoring, nothing else changes); metric_preset: 'docunet' | 'wang' 
+    "gt_dir": "",
+    "metric_preset": "docunet",
     "num_synthetic_docs": 4,
     "full_res": (1024, 768), # synthetic full-resolution source size (H, W)
     "conditioning_dir": "",   # directory of per-document conditioning .npz files (skips ingest + pre-stage nets)

@@ -8,6 +8,7 @@ or as dicts of ready conditioning tensors (synthetic or loaded from .npz), i.e. 
 from __future__ import annotations
 
 import os
+import re
 import time
 
 import numpy as np
@@ -143,6 +144,39 @@ def _source_u8(d, device):
     return as_u8.permute(1, 2, 0).contiguous()
 
 
+def gt_candidates(path):
+    """File names under env.gt_dir that may hold the ground-truth scan of document `path`, in the order they are tried: the
+    document's own stem, then the stem's leading integer (DocUNet: '12_1 copy.png' -> '12_1 copy.png', '12.png')."""
+    stem = os.path.splitext(os.path.basename(str(path)))[0]
+    names = [stem + ".png"]
+    lead = re.match(r"\d+", stem)
+    if lead and lead.group(0) != stem:
+        names.append(lead.group(0) + ".png")
+    return names
+
+
+def find_gt(gt_dir, path):
+    """The ground-truth file of document `path` under gt_dir, or None."""
+    for name in gt_candidates(path):
+        full = os.path.join(gt_dir, name)
+        if os.path.isfile(full):
+            return full
+    return None
+
+
+def _score_against_gt(settings, logger, path, out, device):
+    """MS-SSIM of one dewarped page (uint8 [H,W,3] on the device) against its ground-truth scan, if there is one."""
+    from PIL import Image
+    gt_file = find_gt(settings.env.gt_dir, path)
+    if gt_file is None:
+        logger.info(f"{path} ms_ssim skipped: no ground truth in {settings.env.gt_dir}")
+        return
+    gt = th.from_numpy(np.ascontiguousarray(np.asarray(Image.open(gt_file).convert("RGB")))).to(device)
+    value = ops.ms_ssim_u8(out.contiguous(), gt, preset=getattr(settings.env, "metric_preset", "docunet"))
+    logger.info(f"{path} ms_ssim {value:.6f}")
+    settings.ms_ssim.append((path, value))
+
+
 def run_evaluation_docunet(settings, logger, val_loader, diffusion, model, pretrained_dewarp_model,
                            pretrained_line_seg_model=None, pretrained_seg_model=None):
     """Document loop with the reference's positional signature (evaluation.py:142-327; call site val_TDiff.py:103-104).
@@ -151,6 +185,9 @@ def run_evaluation_docunet(settings, logger, val_loader, diffusion, model, pretr
     (:162-216), the sampler (:247-265), then the tail (:301-306 + visualization_utils.py:75-77) as ONE fused u8 launch per
     batch (documents of one size or of different sizes alike; env.unwarp_mode 'bilinear' | 'bicubic' is its interpolation), and - if env.visualize - `visualize_dewarping` writes the PNG where the reference writes it.
     The pre-stage models may all be None when every document carries ready conditioning tensors.
+    With env.gt_dir set, every dewarped page is scored against `<gt_dir>/<stem>.png` (`gt_candidates`) with MS-SSIM
+    (ops.ms_ssim_u8, env.metric_preset): logged per document and as a mean, written to ms_ssim.txt beside the pictures and
+    left in settings.ms_ssim as [(path, value)]; a document without a ground truth is logged and skipped.
     Returns [(path, uint8 [H,W,3] device tensor)] (the reference returns None)."""
     from utils_flow.visualization_utils import visualize_dewarping
     env = settings.env
@@ -163,6 +200,10 @@ def run_evaluation_docunet(settings, logger, val_loader, diffusion, model, pretr
     os.makedirs(f"vis_hp/{env.eval_dataset_name}/{settings.name}", exist_ok=True)
     G, B = env.grid_size, env.batch_docs
     times, results, batch = [], [], []
+    gt_dir = getattr(env, "gt_dir", "")
+    if gt_dir:
+        ops._ssim_preset(getattr(env, "metric_preset", "docunet"), "env.metric_preset")
+        settings.ms_ssim = []
 
     def flush():
         if not batch:
@@ -219,6 +260,8 @@ def run_evaluation_docunet(settings, logger, val_loader, diffusion, model, pretr
             if env.visualize:
                 name = d["path"] if os.path.splitext(d["path"])[1] else d["path"] + ".png"
                 visualize_dewarping(settings, None, d, len(results) - 1, None, [name], warped_u8=out)
+            if gt_dir:
+                _score_against_gt(settings, logger, d["path"], out, device)
         batch.clear()
 
     for item in val_loader:
@@ -230,4 +273,13 @@ def run_evaluation_docunet(settings, logger, val_loader, diffusion, model, pretr
     if times:
         print(len(times))
         print("Elapsed time:{:.2f} avg_second ".format(sum(times) / len(times)))
+    if gt_dir:
+        with open(f"vis_hp/{env.eval_dataset_name}/{settings.name}/ms_ssim.txt", "w") as f:
+            for path, value in settings.ms_ssim:
+                f.write(f"{path} {value:.6f}\n")
+        if settings.ms_ssim:
+            mean = sum(v for _, v in settings.ms_ssim) / len(settings.ms_ssim)
+            logger.info(f"mean ms_ssim {mean:.6f} over {len(settings.ms_ssim)} of {len(results)} documents")
+        else:
+            logger.info(f"mean ms_ssim: no document of {len(results)} has a ground truth in {gt_dir}")
     return results

@@ -367,3 +367,103 @@ def resize_bilinear_nhwc(x, c, hin, win, hout, wout):
     out = torch.empty(hout * wout, c, dtype=torch.float32, device=x.device)
     lib.call("dvd_resize_bilinear_nhwc", ptr(x), ptr(out), c, hin, win, hout, wout, stream_ptr())
     return out
+
+
+# ---- MS-SSIM against a ground-truth scan (dvd_amd/csrc/metrics.hip; definition: DESIGN.md 4.3) -----------------------------
+MSSSIM_WEIGHTS = (0.0448, 0.2856, 0.3001, 0.2363, 0.1333)
+MSSSIM_MIN_SIDE = 176          # the fifth scale must still hold one full 11 x 11 window
+MSSSIM_AREA = 598400           # working size of the DocUNet benchmark protocol, in pixels
+_SSIM_PRESETS = {"docunet": lib.MSSSIM_DOCUNET, "wang": lib.MSSSIM_WANG}
+
+
+def _ssim_preset(preset, name):
+    """The metric's preset: checked before anything is allocated or launched."""
+    if preset not in _SSIM_PRESETS:
+        raise ValueError(f"{name}: preset must be 'docunet' or 'wang', got {preset!r}")
+    return _SSIM_PRESETS[preset]
+
+
+def _size_query(name, *args):
+    """A byte count from the library (a negative value is a DVD_E_* status)."""
+    nbytes = getattr(lib.raw(), name)(*args)
+    if nbytes < 0:
+        raise lib.DvdError(f"{name} failed ({nbytes}): {lib.raw().dvd_last_error().decode()}")
+    return nbytes
+
+
+def resize_gray_u8(img_nhwc_u8: torch.Tensor, out_h: int, out_w: int) -> torch.Tensor:
+    """[N,H,W,3] uint8 RGB -> [N,out_h,out_w] f32 gray (integers 0..255): anti-aliased triangle resize, one rounding to
+    u8, round(0.2989 R + 0.5870 G + 0.1140 B) - the metric's preparation in one launch for the N images."""
+    if img_nhwc_u8.dim() != 4 or img_nhwc_u8.shape[0] < 1 or img_nhwc_u8.shape[3] != 3:
+        raise ValueError(f"resize_gray_u8: expected [N,H,W,3] with N >= 1, got {tuple(img_nhwc_u8.shape)}")
+    n, h, w, _ = img_nhwc_u8.shape
+    if min(h, w, out_h, out_w) < 1:
+        raise ValueError(f"resize_gray_u8: bad shape {h}x{w} -> {out_h}x{out_w}")
+    _chk(img_nhwc_u8, torch.uint8, "img")
+    out = torch.empty((n, out_h, out_w), dtype=torch.float32, device=img_nhwc_u8.device)
+    scratch = torch.empty(_size_query("dvd_resize_gray_scratch_bytes", h, w, out_h, out_w), dtype=torch.uint8,
+                          device=img_nhwc_u8.device)
+    lib.call("dvd_resize_gray_u8", ptr(img_nhwc_u8), n, h, w, ptr(out), out_h, out_w, ptr(scratch), stream_ptr())
+    return out
+
+
+def ssim_scales(x: torch.Tensor, y: torch.Tensor, preset: str = "docunet") -> torch.Tensor:
+    """Gray planes x, y [N,H,W] f32 (0..255) of one size -> [N,5,2] f32: per scale (mean ssim, mean cs)."""
+    flag = _ssim_preset(preset, "ssim_scales")
+    if x.dim() != 3 or x.shape[0] < 1 or tuple(x.shape) != tuple(y.shape):
+        raise ValueError(f"ssim_scales: expected two [N,H,W] planes of one shape, got {tuple(x.shape)} and {tuple(y.shape)}")
+    n, h, w = x.shape
+    if min(h, w) < MSSSIM_MIN_SIDE:
+        raise ValueError(f"ssim_scales: each side must be >= {MSSSIM_MIN_SIDE} (five scales of an 11x11 window), got {h}x{w}")
+    _chk(x, torch.float32, "x")
+    _chk(y, torch.float32, "y")
+    out = torch.empty((n, 5, 2), dtype=torch.float32, device=x.device)
+    work = torch.empty(_size_query("dvd_msssim_workspace_bytes", h, w, n), dtype=torch.uint8, device=x.device)
+    lib.call("dvd_msssim_scales", ptr(x), ptr(y), n, h, w, flag, ptr(work), ptr(out), stream_ptr())
+    return out
+
+
+def msssim_combine(scales, preset: str = "docunet") -> float:
+    """The ten numbers of one document ([5][2]: per scale (ssim, cs)) -> MS-SSIM, in Python floats."""
+    _ssim_preset(preset, "msssim_combine")
+    s = [[float(v) for v in row] for row in scales]
+    if preset == "wang":
+        terms = [s[0][1], s[1][1], s[2][1], s[3][1], s[4][0]]
+        if min(terms) < 0.0:                      # a negative mean has no real fractional power (numpy gives nan too)
+            return float("nan")
+        val = 1.0
+        for t, wk in zip(terms, MSSSIM_WEIGHTS):
+            val *= t ** wk
+        return val
+    return sum(wk * s[k][0] for k, wk in enumerate(MSSSIM_WEIGHTS))
+
+
+def ms_ssim(x: torch.Tensor, y: torch.Tensor, preset: str = "docunet") -> np.ndarray:
+    """MS-SSIM of N pairs of gray planes [N,H,W] -> [N] float64 (the per-scale numbers are combined on the host)."""
+    scales = ssim_scales(x, y, preset).cpu().tolist()
+    return np.array([msssim_combine(s, preset) for s in scales], dtype=np.float64)
+
+
+def msssim_target_size(h: int, w: int, area: int = MSSSIM_AREA):
+    """(rows, columns) the ground truth [h,w] is resized to: (round(h s), round(w s)), s = sqrt(area / (h w))."""
+    s = (area / (h * w)) ** 0.5
+    return int(round(h * s)), int(round(w * s))
+
+
+def ms_ssim_u8(pred_hwc_u8: torch.Tensor, gt_hwc_u8: torch.Tensor, preset: str = "docunet", area: int = MSSSIM_AREA) -> float:
+    """The whole protocol for one pair of uint8 RGB images [H,W,3] of any two sizes: the ground truth is resized to `area`
+    pixels, the prediction to the ground truth's resized size, both go to gray, then MS-SSIM."""
+    _ssim_preset(preset, "ms_ssim_u8")
+    for name, t in (("pred", pred_hwc_u8), ("gt", gt_hwc_u8)):
+        if t.dim() != 3 or t.shape[2] != 3 or min(t.shape[:2]) < 1:
+            raise ValueError(f"ms_ssim_u8: {name}: expected [H,W,3], got {tuple(t.shape)}")
+    if area < 1:
+        raise ValueError(f"ms_ssim_u8: area must be positive, got {area}")
+    th_, tw_ = msssim_target_size(gt_hwc_u8.shape[0], gt_hwc_u8.shape[1], area)
+    if min(th_, tw_) < MSSSIM_MIN_SIDE:
+        raise ValueError(f"ms_ssim_u8: the working size {th_}x{tw_} has a side below {MSSSIM_MIN_SIDE}")
+    _chk(pred_hwc_u8, torch.uint8, "pred")
+    _chk(gt_hwc_u8, torch.uint8, "gt")
+    x = resize_gray_u8(pred_hwc_u8[None], th_, tw_)
+    y = resize_gray_u8(gt_hwc_u8[None], th_, tw_)
+    return float(ms_ssim(x, y, preset)[0])

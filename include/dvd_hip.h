@@ -442,6 +442,44 @@ int dvd_engine_debug_stop(void* handle, int stage);
  * operand, f32-MFMA A[:, :2].B[:2, :]}.  No reference counterpart (test infrastructure). */
 int dvd_selftest_mfma(const void* a16, const void* b16, const void* vt16, float* out3072, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Image-quality metric of the evaluation tail: MS-SSIM of a dewarped page against its flat ground-truth scan.  The
+ * reference leaves it to offline MATLAB (matlab_code/run_docunet.m, whose evalUnwarp is not in its tree); the definition
+ * is this project's own (float64 statement: tests/msssim_model.py) and parity with MATLAB's imresize /
+ * rgb2gray / ssim / impyramid is UNPINNED.  No kernel uses an atomic: the same inputs give the same bits on every launch,
+ * and document d of a batch gets the bits it gets alone.
+ * ---------------------------------------------------------------------------------------- */
+#define DVD_SSIM_REPLICATE 0 /* window centred, indices clamped: the map is h x w */
+#define DVD_SSIM_VALID 1     /* full windows only: the map is (h-10) x (w-10) */
+#define DVD_MSSSIM_DOCUNET 0 /* replicate border, [1,4,6,4,1]/16 reduce */
+#define DVD_MSSSIM_WANG 1    /* valid border, 2-tap box reduce */
+/* Fused preparation: src [n,h,w,3] u8 RGB -> out [n,out_h,out_w] f32 gray (integer values 0..255).  Separable anti-aliased
+ * triangle resize (per axis r = out/in, centre u = (o+0.5)/r - 0.5, taps j = ceil(u - 1/s) .. floor(u + 1/s) with
+ * s = min(r,1), weight tri((u-j) s), tap indices clamped, weights normalised to sum 1; f64 taps and sums), rounded half
+ * to even to u8 once, then gray = round(0.2989 R + 0.5870 G + 0.1140 B).  The tap tables are built on the device in
+ * `scratch` (dvd_resize_gray_scratch_bytes; a negative DVD_E_* value for a bad shape).  Every side 1..32768. */
+long dvd_resize_gray_scratch_bytes(int h, int w, int out_h, int out_w);
+int dvd_resize_gray_u8(const uint8_t* src_nhwc, int n, int h, int w, float* out, int out_h, int out_w,
+                       void* scratch, void* stream);
+/* One scale on gray planes x, y [n,h,w] f32 (values 0..255, each side 11..32768): the 11-tap Gaussian (sigma 1.5) moments
+ * mu_x, mu_y, E[xx], E[yy], E[xy] of both planes less 127.5, cs = (2 s_xy + C2) / (s_xx + s_yy + C2) and
+ * ssim = cs (2 mu_x mu_y + C1) / (mu_x^2 + mu_y^2 + C1), C1 = 6.5025, C2 = 58.5225.  partials [n, tiles, 2] f64 receives
+ * (sum ssim, sum cs) of every 32 x 32 tile of the map, tiles = ceil(map_h / 32) * ceil(map_w / 32), row-major. */
+int dvd_ssim_scale(const float* x, const float* y, int n, int h, int w, int border, double* partials, void* stream);
+/* out[d, scale, 0..1] = (sum ssim, sum cs) of document d's tiles, added in a fixed order in f64, / count (the map's
+ * pixels); out is [n,5,2] f32, scale 0..4. */
+int dvd_ssim_finalize(const double* partials, int n, int tiles, long count, float* out_n52, int scale, void* stream);
+/* Both planes [n,h,w] reduced by 2 to [n,ceil(h/2),ceil(w/2)] in one launch.  taps 2: out[i] = (x[2i] + x[min(2i+1,
+ * n-1)]) / 2 per axis; taps 5: [1,4,6,4,1]/16 centred on 2i, indices clamped. */
+int dvd_reduce2_pair(const float* x, const float* y, float* x_out, float* y_out, int n, int h, int w, int taps,
+                     void* stream);
+/* The five scales of n pairs of planes [n,h,w] (each side 176..32768, so that the fifth scale holds one full window):
+ * out [n,5,2] f32 = per scale (mean ssim, mean cs).  workspace: dvd_msssim_workspace_bytes(h, w, n) bytes (tile partials
+ * and the planes of scales 2..5; a negative DVD_E_* value for a bad shape or batch). */
+long dvd_msssim_workspace_bytes(int h, int w, int n);
+int dvd_msssim_scales(const float* x, const float* y, int n, int h, int w, int preset, void* workspace,
+                      float* out_n52, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
