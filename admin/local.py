@@ -56,6 +56,9 @@ _DEFAULTS = {
     # (ops.ms_ssim_u8; "" = no scoring, nothing else changes); metric_preset: 'docunet' | 'wang' 
     "gt_dir": "",
     "metric_preset": "docunet",
+    # who writes dewarped_pred/warped_<stem>.png: 'pil' (the reference: copy the page to the host, Image.save) | 'hip'
+    # (ops.png_encode on the device, only the compressed file crosses to the host; the same pixels, other bytes - DESIGN.md 4.4)
+    "png_encoder": "pil",
     "num_synthetic_docs": 4,
     "full_res": (1024, 768), # synthetic full-resolution source size (H, W)
     "conditioning_dir": "",   # directory of per-document conditioning .npz files (skips ingest + pre-stage nets)

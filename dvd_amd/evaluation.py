@@ -183,7 +183,8 @@ def run_evaluation_docunet(settings, logger, val_loader, diffusion, model, pretr
     `val_loader` yields the reference's dicts or this package's documents (`documents_of`); `env.batch_docs` documents are
     batched per pass (the reference: 1): ingest + the three pre-stage nets for documents that arrive as images
     (:162-216), the sampler (:247-265), then the tail (:301-306 + visualization_utils.py:75-77) as ONE fused u8 launch per
-    batch (documents of one size or of different sizes alike; env.unwarp_mode 'bilinear' | 'bicubic' is its interpolation), and - if env.visualize - `visualize_dewarping` writes the PNG where the reference writes it.
+    batch (documents of one size or of different sizes alike; env.unwarp_mode 'bilinear' | 'bicubic' is its interpolation), and - if env.visualize - `visualize_dewarping` writes the PNG where the reference writes it
+    (env.png_encoder 'pil' | 'hip': PIL on a host copy, or the HIP encoder on the device).
     The pre-stage models may all be None when every document carries ready conditioning tensors.
     With env.gt_dir set, every dewarped page is scored against `<gt_dir>/<stem>.png` (`gt_candidates`) with MS-SSIM
     (ops.ms_ssim_u8, env.metric_preset): logged per document and as a mean, written to ms_ssim.txt beside the pictures and
@@ -194,6 +195,9 @@ def run_evaluation_docunet(settings, logger, val_loader, diffusion, model, pretr
     unwarp_mode = getattr(env, "unwarp_mode", "bilinear")       # the interpolation of the full-resolution tail
     if unwarp_mode not in ("bilinear", "bicubic"):
         raise ValueError(f"env.unwarp_mode must be 'bilinear' or 'bicubic', got {unwarp_mode!r}")
+    png_encoder = getattr(env, "png_encoder", "pil")            # who writes the PNG: visualize_dewarping reads it
+    if png_encoder not in ("pil", "hip"):
+        raise ValueError(f"env.png_encoder must be 'pil' or 'hip', got {png_encoder!r}")
     device = next(model.parameters()).device
     nets = (pretrained_dewarp_model, pretrained_seg_model, pretrained_line_seg_model)
     prestage_models = None if all(m is None for m in nets) else nets

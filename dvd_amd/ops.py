@@ -467,3 +467,48 @@ def ms_ssim_u8(pred_hwc_u8: torch.Tensor, gt_hwc_u8: torch.Tensor, preset: str =
     x = resize_gray_u8(pred_hwc_u8[None], th_, tw_)
     y = resize_gray_u8(gt_hwc_u8[None], th_, tw_)
     return float(ms_ssim(x, y, preset)[0])
+
+
+# ---- PNG of a dewarped page, encoded on the device (dvd_amd/csrc/png.hip; format: DESIGN.md 4.4) ------------------------------
+def _png_input(img, name):
+    """The encoder's input: checked before anything is allocated or launched."""
+    if not torch.is_tensor(img) or img.dim() != 3 or img.shape[2] != 3 or min(img.shape[:2]) < 1:
+        raise ValueError(f"{name}: expected a [H,W,3] tensor, got {tuple(img.shape) if torch.is_tensor(img) else type(img)}")
+    if img.dtype != torch.uint8 or not img.is_contiguous():
+        raise ValueError(f"{name}: expected contiguous uint8, got {img.dtype} contiguous={img.is_contiguous()}")
+    h, w = int(img.shape[0]), int(img.shape[1])
+    if h * (3 * w + 1) >= 2 ** 31:
+        raise ValueError(f"{name}: image {h}x{w} too large (h * (3w + 1) must be below 2^31)")
+    return h, w
+
+
+def png_bound(h: int, w: int) -> int:
+    """Worst-case bytes of the PNG file of an h x w RGB image (dvd_png_bound)."""
+    return _size_query("dvd_png_bound", h, w)
+
+
+def png_encode(img_hwc_u8: torch.Tensor, scratch: torch.Tensor = None) -> torch.Tensor:
+    """[H,W,3] uint8 on the device -> the complete PNG file as uint8 [nbytes] on the device: four launches, then ONE read-back
+    (the file's length) to trim the worst-case buffer.  The bytes depend on (H, W, pixels) only.  scratch (optional): a
+    uint8 device buffer of at least dvd_png_scratch_bytes(H, W) bytes to reuse between calls; its contents do not matter."""
+    h, w = _png_input(img_hwc_u8, "png_encode")
+    _chk(img_hwc_u8, torch.uint8, "img")
+    dev = img_hwc_u8.device
+    need = _size_query("dvd_png_scratch_bytes", h, w)
+    if scratch is None:
+        scratch = torch.empty(need, dtype=torch.uint8, device=dev)
+    elif scratch.dtype != torch.uint8 or not scratch.is_contiguous() or scratch.numel() < need or scratch.device != dev:
+        raise ValueError(f"png_encode: scratch must be a contiguous uint8 buffer of >= {need} bytes on {dev}")
+    cap = png_bound(h, w)
+    out = torch.empty(cap, dtype=torch.uint8, device=dev)
+    nbytes = torch.zeros(1, dtype=torch.int64, device=dev)
+    lib.call("dvd_png_encode_rgb8", ptr(img_hwc_u8), h, w, ptr(out), cap, ptr(nbytes), ptr(scratch), stream_ptr())
+    return out[:int(nbytes.item())]
+
+
+def png_encode_to_file(img_hwc_u8: torch.Tensor, path: str) -> int:
+    """Encode on the device and write `path`: only the compressed bytes cross to the host.  Returns the file's bytes."""
+    data = png_encode(img_hwc_u8).cpu().numpy()
+    with open(path, "wb") as f:
+        f.write(data.tobytes())
+    return int(data.size)

@@ -480,6 +480,31 @@ long dvd_msssim_workspace_bytes(int h, int w, int n);
 int dvd_msssim_scales(const float* x, const float* y, int n, int h, int w, int preset, void* workspace,
                       float* out_n52, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Lossless PNG of a dewarped page, encoded where the unwarp tail leaves it (the reference: Image.fromarray(...).save on
+ * the host, utils_flow/visualization_utils.py:77-78).  The file is a pure function of (h, w, pixels) - DESIGN.md 4.4:
+ *   signature, IHDR (w, h, depth 8, colour type 2, 0, 0, 0), one IDAT per segment, IEND.
+ *   Filtered stream: h rows of 1 + 3w bytes; per row the filter None / Sub / Up / Average / Paeth with the least sum of
+ *   |residual as a signed byte|, the lowest number on a tie.
+ *   The stream is cut into segments of DVD_PNG_SEGMENT bytes (not tied to rows).  Each is compressed on its own: greedy LZ77
+ *   (length 3..258, matches never reach before the segment's first byte or past its last), ONE fixed-Huffman block
+ *   (BFINAL = 0), then an empty stored block (00 00 FF FF after padding to a byte), so the segments' bytes concatenate.
+ *   The zlib stream is 78 01, the segments, the final empty fixed block 03 00 and the big-endian Adler-32 of the filtered
+ *   stream (per-segment partials folded exactly mod 65521).  IDAT s holds segment s; the first also the two header bytes,
+ *   the last also 03 00 and the Adler-32.  Each IDAT's CRC-32 covers that chunk only.
+ * ---------------------------------------------------------------------------------------- */
+#define DVD_PNG_SEGMENT 32768
+/* Worst-case file bytes and scratch bytes for an h x w image; host-only.  A negative DVD_E_* value for a bad shape
+ * (h < 1, w < 1 or h * (3w + 1) >= 2^31). */
+long dvd_png_bound(int h, int w);
+long dvd_png_scratch_bytes(int h, int w);
+/* img_hwc [h,w,3] u8 -> the complete file in out[0 .. *out_len), *out_len (a DEVICE uint64) <= dvd_png_bound(h, w).
+ * cap = bytes writable at out: cap < dvd_png_bound(h, w) is DVD_E_ARG, checked before anything is launched, so no kernel
+ * can write past out + cap.  scratch: dvd_png_scratch_bytes(h, w) device bytes, 16-byte aligned; its previous contents
+ * do not matter.  Four launches on `stream`, no synchronisation, no read-back. */
+int dvd_png_encode_rgb8(const uint8_t* img_hwc, int h, int w, uint8_t* out, long cap, unsigned long long* out_len,
+                        void* scratch, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

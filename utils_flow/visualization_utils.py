@@ -9,7 +9,11 @@ Called as the reference calls it (evaluation.py:311-312)
 `sample` is the grid `((interp(flow) + base)*2 - 1)*0.987` [1,2,H,W] and the warp is `reg_model_bilin([source_vis, sample])`
 on the drop-in HIP kernel (32 B/px).  `dvd_amd.evaluation.run_evaluation_docunet` instead passes `warped_u8=`: the bytes its
 fused tail kernel (`dvd_unwarp_u8[_batch]`, 6 B/px: up-sampling, base grid, affine, gather and truncation in one launch) already
-produced from the COARSE flow - bit-identical to the long way (tests/test_gpu_ops.py::test_unwarp_golden, golden G5)."""
+produced from the COARSE flow - bit-identical to the long way (tests/test_gpu_ops.py::test_unwarp_golden, golden G5).
+
+`settings.env.png_encoder` chooses who writes the PNG: 'pil' (default, the reference's Image.save on a host copy of the page) or
+'hip' (`dvd_amd.ops.png_encode_to_file`: filtered and compressed where the page lies, only the file crosses to the host - the
+same pixels in a file of other bytes)."""
 from __future__ import annotations
 
 import os
@@ -20,6 +24,7 @@ from PIL import Image
 from datasets.utils.warping import register_model2
 
 reg_model_bilin = register_model2((512, 512), "bilinear")
+PNG_ENCODERS = ("pil", "hip")
 
 
 def _stem(data_path):
@@ -28,16 +33,33 @@ def _stem(data_path):
 
 
 def visualize_dewarping(settings, sample, data, i, source_vis, data_path, ref_flow=None, *, warped_u8=None):
-    """Returns the uint8 [H,W,3] image it wrote (the reference returns None)."""
+    """Returns the uint8 [H,W,3] image it wrote (the reference returns None): a NumPy array with png_encoder 'pil', the
+    DEVICE tensor with 'hip' (the page is never copied to the host there)."""
+    encoder = getattr(settings.env, "png_encoder", "pil")
+    if encoder not in PNG_ENCODERS:
+        raise ValueError(f"env.png_encoder must be 'pil' or 'hip', got {encoder!r}")
     out_dir = f"vis_hp/{settings.env.eval_dataset_name}/{settings.name}"
     os.makedirs(f"{out_dir}/pred_flow", exist_ok=True)
     os.makedirs(f"{out_dir}/dewarped_pred", exist_ok=True)
-    if warped_u8 is None:
+    if encoder == "hip":
+        import torch
+        from dvd_amd import ops
+        if warped_u8 is None:                        # the reference's call form: truncated to uint8 on the device
+            warped = reg_model_bilin([source_vis.to(sample.device).float(), sample])
+            warped_u8 = warped[0].permute(1, 2, 0).detach().to(torch.uint8)
+        elif not torch.is_tensor(warped_u8):
+            warped_u8 = torch.from_numpy(np.asarray(warped_u8))
+        if not warped_u8.is_cuda:
+            warped_u8 = warped_u8.to(sample.device if sample is not None else "cuda")
+        warped_u8 = warped_u8.detach().contiguous()
+        ops.png_encode_to_file(warped_u8, f"{out_dir}/dewarped_pred/warped_{_stem(data_path)}.png")
+    elif warped_u8 is None:
         warped = reg_model_bilin([source_vis.to(sample.device).float(), sample])
         warped_u8 = warped[0].permute(1, 2, 0).detach().cpu().numpy().astype(np.uint8)
     else:
         warped_u8 = warped_u8.detach().cpu().numpy() if hasattr(warped_u8, "detach") else np.asarray(warped_u8)
-    Image.fromarray(warped_u8).save(f"{out_dir}/dewarped_pred/warped_{_stem(data_path)}.png")
+    if encoder == "pil":
+        Image.fromarray(warped_u8).save(f"{out_dir}/dewarped_pred/warped_{_stem(data_path)}.png")
     if ref_flow is not None:
         os.makedirs(f"{out_dir}/pred_flow_ref", exist_ok=True)
         os.makedirs(f"{out_dir}/dewarped_pred_ref", exist_ok=True)
