@@ -59,6 +59,12 @@ _DEFAULTS = {
     # who writes dewarped_pred/warped_<stem>.png: 'pil' (the reference: copy the page to the host, Image.save) | 'hip'
     # (ops.png_encode on the device, only the compressed file crosses to the host; the same pixels, other bytes - DESIGN.md 4.4)
     "png_encoder": "pil",
+    # the container of dewarped_pred/warped_<stem>: 'png' (the reference; png_encoder chooses who writes it) | 'jpeg'
+    # (warped_<stem>.jpg: baseline JFIF encoded on the device by ops.jpeg_encode, only the file crosses to the host; png_encoder
+    # is not consulted - DESIGN.md 4.5)
+    "page_format": "png",
+    "jpeg_quality": 90,         # 1..100, PIL's `quality` scale (the Annex K tables scaled by the usual rule)
+    "jpeg_subsampling": "420",  # '420' | '444'
     "num_synthetic_docs": 4,
     "full_res": (1024, 768), # synthetic full-resolution source size (H, W)
     "conditioning_dir": "",   # directory of per-document conditioning .npz files (skips ingest + pre-stage nets)

@@ -184,13 +184,14 @@ def run_evaluation_docunet(settings, logger, val_loader, diffusion, model, pretr
     batched per pass (the reference: 1): ingest + the three pre-stage nets for documents that arrive as images
     (:162-216), the sampler (:247-265), then the tail (:301-306 + visualization_utils.py:75-77) as ONE fused u8 launch per
     batch (documents of one size or of different sizes alike; env.unwarp_mode 'bilinear' | 'bicubic' is its interpolation), and - if env.visualize - `visualize_dewarping` writes the PNG where the reference writes it
-    (env.png_encoder 'pil' | 'hip': PIL on a host copy, or the HIP encoder on the device).
+    (env.png_encoder 'pil' | 'hip': PIL on a host copy, or the HIP encoder on the device; env.page_format 'jpeg' writes
+    warped_<stem>.jpg with the HIP JPEG encoder instead, at env.jpeg_quality and env.jpeg_subsampling).
     The pre-stage models may all be None when every document carries ready conditioning tensors.
     With env.gt_dir set, every dewarped page is scored against `<gt_dir>/<stem>.png` (`gt_candidates`) with MS-SSIM
     (ops.ms_ssim_u8, env.metric_preset): logged per document and as a mean, written to ms_ssim.txt beside the pictures and
     left in settings.ms_ssim as [(path, value)]; a document without a ground truth is logged and skipped.
     Returns [(path, uint8 [H,W,3] device tensor)] (the reference returns None)."""
-    from utils_flow.visualization_utils import visualize_dewarping
+    from utils_flow.visualization_utils import page_settings, visualize_dewarping
     env = settings.env
     unwarp_mode = getattr(env, "unwarp_mode", "bilinear")       # the interpolation of the full-resolution tail
     if unwarp_mode not in ("bilinear", "bicubic"):
@@ -198,6 +199,7 @@ def run_evaluation_docunet(settings, logger, val_loader, diffusion, model, pretr
     png_encoder = getattr(env, "png_encoder", "pil")            # who writes the PNG: visualize_dewarping reads it
     if png_encoder not in ("pil", "hip"):
         raise ValueError(f"env.png_encoder must be 'pil' or 'hip', got {png_encoder!r}")
+    page_settings(env)                                          # env.page_format, env.jpeg_quality, env.jpeg_subsampling
     device = next(model.parameters()).device
     nets = (pretrained_dewarp_model, pretrained_seg_model, pretrained_line_seg_model)
     prestage_models = None if all(m is None for m in nets) else nets

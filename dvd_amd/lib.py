@@ -85,12 +85,14 @@ MSSSIM_DOCUNET, MSSSIM_WANG = 0, 1         # DVD_MSSSIM_*: presets of dvd_msssim
 
 PNG_SEGMENT = 32768   # DVD_PNG_SEGMENT: filtered-stream bytes per IDAT chunk of the PNG encoder
 
+JPEG_420, JPEG_444 = 0, 1                  # DVD_JPEG_*: chroma subsampling of the JPEG encoder
+
 RAGGED_CAP = 64   # DVD_RAGGED_CAP: documents per launch of the ragged entry points (larger batches are cut by the library)
 
 NON_STATUS = {"dvd_last_error", "dvd_version", "dvd_engine_workspace_bytes", "dvd_engine_tensor_count",
               "dvd_flash_attn_kernel_name", "dvd_gemm_kernel_name", "dvd_convnet_workspace_bytes", "dvd_convnet_weight_floats",
               "dvd_ingest_scratch_bytes", "dvd_ingest_ragged_scratch_bytes", "dvd_resize_gray_scratch_bytes",
-              "dvd_msssim_workspace_bytes", "dvd_png_bound", "dvd_png_scratch_bytes"}
+              "dvd_msssim_workspace_bytes", "dvd_png_bound", "dvd_png_scratch_bytes", "dvd_jpeg_bound", "dvd_jpeg_scratch_bytes"}
 
 # name -> argtypes; kept in one table so tests can check every symbol of include/dvd_hip.h
 SIGNATURES = {
@@ -158,6 +160,9 @@ SIGNATURES = {
     "dvd_png_bound": [C.c_int, C.c_int],
     "dvd_png_scratch_bytes": [C.c_int, C.c_int],
     "dvd_png_encode_rgb8": [c_void, C.c_int, C.c_int, c_void, C.c_long, c_void, c_void, c_void],
+    "dvd_jpeg_bound": [C.c_int, C.c_int, C.c_int],
+    "dvd_jpeg_scratch_bytes": [C.c_int, C.c_int, C.c_int],
+    "dvd_jpeg_encode_rgb8": [c_void, C.c_int, C.c_int, C.c_int, C.c_int, c_void, C.c_long, c_void, c_void, c_void],
     "dvd_dither_f16": [c_void, c_void, c_void, C.c_long, C.c_uint, C.c_uint, c_void],
     "dvd_engine_create": [C.c_int, C.c_int, C.c_int, C.POINTER(c_void)],
     "dvd_engine_destroy": [c_void],
@@ -179,7 +184,8 @@ SIGNATURES = {
 # entries of SIGNATURES that return something other than a status
 RESTYPES = {"dvd_gemm_kernel_name": C.c_char_p, "dvd_ingest_ragged_scratch_bytes": C.c_long,
             "dvd_resize_gray_scratch_bytes": C.c_long, "dvd_msssim_workspace_bytes": C.c_long,
-            "dvd_png_bound": C.c_long, "dvd_png_scratch_bytes": C.c_long}
+            "dvd_png_bound": C.c_long, "dvd_png_scratch_bytes": C.c_long,
+            "dvd_jpeg_bound": C.c_long, "dvd_jpeg_scratch_bytes": C.c_long}
 
 # entry points that exist only in the lab build (benchmarks/lab/dvd_hip_lab.h; loaded through use_library)
 LAB_SIGNATURES = {"dvd_gemm_debug_stamps": [c_void], "dvd_attn_debug_stamps": [c_void]}

@@ -512,3 +512,62 @@ def png_encode_to_file(img_hwc_u8: torch.Tensor, path: str) -> int:
     with open(path, "wb") as f:
         f.write(data.tobytes())
     return int(data.size)
+
+
+# ---- JPEG of a dewarped page, encoded on the device (dvd_amd/csrc/jpeg.hip; format: DESIGN.md 4.5) ----------------------------
+JPEG_SUBSAMPLINGS = {"420": lib.JPEG_420, "444": lib.JPEG_444}
+
+
+def jpeg_settings(quality, subsampling, name="jpeg_encode"):
+    """(quality, the library's subsampling flag), or ValueError: quality an integer 1..100, subsampling '420' | '444'."""
+    if isinstance(quality, bool) or not isinstance(quality, (int, np.integer)) or not 1 <= quality <= 100:
+        raise ValueError(f"{name}: quality must be an integer 1..100, got {quality!r}")
+    if subsampling not in JPEG_SUBSAMPLINGS:
+        raise ValueError(f"{name}: subsampling must be '420' or '444', got {subsampling!r}")
+    return int(quality), JPEG_SUBSAMPLINGS[subsampling]
+
+
+def _jpeg_input(img, name):
+    """The encoder's input: checked before anything is allocated or launched."""
+    if not torch.is_tensor(img) or img.dim() != 3 or img.shape[2] != 3 or min(img.shape[:2]) < 1:
+        raise ValueError(f"{name}: expected a [H,W,3] tensor, got {tuple(img.shape) if torch.is_tensor(img) else type(img)}")
+    if img.dtype != torch.uint8 or not img.is_contiguous():
+        raise ValueError(f"{name}: expected contiguous uint8, got {img.dtype} contiguous={img.is_contiguous()}")
+    h, w = int(img.shape[0]), int(img.shape[1])
+    if max(h, w) > 65535 or 3 * (-(-h // 16) * 16) * (-(-w // 16) * 16) >= 2 ** 31:
+        raise ValueError(f"{name}: image {h}x{w} too large (h, w <= 65535 and the padded planes below 2^31 bytes)")
+    return h, w
+
+
+def jpeg_bound(h: int, w: int, subsampling: str = "420") -> int:
+    """Worst-case bytes of the JPEG file of an h x w RGB image (dvd_jpeg_bound)."""
+    return _size_query("dvd_jpeg_bound", h, w, jpeg_settings(90, subsampling, "jpeg_bound")[1])
+
+
+def jpeg_encode(img_hwc_u8: torch.Tensor, quality: int = 90, subsampling: str = "420", scratch: torch.Tensor = None) -> torch.Tensor:
+    """[H,W,3] uint8 on the device -> the complete baseline JPEG file as uint8 [nbytes] on the device: four launches, then ONE
+    read-back (the file's length) to trim the worst-case buffer.  The bytes depend on (H, W, pixels, quality, subsampling) only.
+    The tensor's first byte may lie at any address.  scratch (optional): a uint8 device buffer of at least
+    dvd_jpeg_scratch_bytes(H, W, subsampling) bytes to reuse between calls; its contents do not matter."""
+    h, w = _jpeg_input(img_hwc_u8, "jpeg_encode")
+    quality, flag = jpeg_settings(quality, subsampling)
+    _chk(img_hwc_u8, torch.uint8, "img")
+    dev = img_hwc_u8.device
+    need = _size_query("dvd_jpeg_scratch_bytes", h, w, flag)
+    if scratch is None:
+        scratch = torch.empty(need, dtype=torch.uint8, device=dev)
+    elif scratch.dtype != torch.uint8 or not scratch.is_contiguous() or scratch.numel() < need or scratch.device != dev:
+        raise ValueError(f"jpeg_encode: scratch must be a contiguous uint8 buffer of >= {need} bytes on {dev}")
+    cap = _size_query("dvd_jpeg_bound", h, w, flag)
+    out = torch.empty(cap, dtype=torch.uint8, device=dev)
+    nbytes = torch.zeros(1, dtype=torch.int64, device=dev)
+    lib.call("dvd_jpeg_encode_rgb8", ptr(img_hwc_u8), h, w, quality, flag, ptr(out), cap, ptr(nbytes), ptr(scratch), stream_ptr())
+    return out[:int(nbytes.item())]
+
+
+def jpeg_encode_to_file(img_hwc_u8: torch.Tensor, path: str, quality: int = 90, subsampling: str = "420") -> int:
+    """Encode on the device and write `path`: only the compressed bytes cross to the host.  Returns the file's bytes."""
+    data = jpeg_encode(img_hwc_u8, quality, subsampling).cpu().numpy()
+    with open(path, "wb") as f:
+        f.write(data.tobytes())
+    return int(data.size)

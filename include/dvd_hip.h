@@ -505,6 +505,31 @@ long dvd_png_scratch_bytes(int h, int w);
 int dvd_png_encode_rgb8(const uint8_t* img_hwc, int h, int w, uint8_t* out, long cap, unsigned long long* out_len,
                         void* scratch, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Baseline JPEG of a dewarped page, encoded where the unwarp tail leaves it.  The file is a pure function of (h, w, pixels,
+ * quality, subsampling), integer arithmetic throughout - DESIGN.md 4.5:
+ *   SOI, APP0 (JFIF 1.01), DQT (the Annex K.1 tables scaled by the usual quality rule), SOF0 (8 bit, Y Cb Cr), DHT (the four
+ *   Annex K.3 tables), DRI, SOS, the entropy-coded data, EOI.
+ *   One restart interval per MCU row (MCU 16 x 16 pixels in 4:2:0, 8 x 8 in 4:4:4): every interval starts with DC predictors
+ *   0, ends padded with 1-bits to a byte and is followed by RSTm, m = interval mod 8 (the last by EOI).
+ *   Pixels past the image repeat its last row / column.  RGB -> YCbCr in 16-bit fixed point, 4:2:0 chroma = the 2 x 2 average
+ *   (a + b + c + d + 2) >> 2, DCT by the integer matrix round(2^13 C(u)/2 cos((2x+1) u pi/16)) (rows keep 2 fraction bits, the
+ *   coefficient 3), quantisation by division rounded half away from zero.
+ * ---------------------------------------------------------------------------------------- */
+#define DVD_JPEG_420 0
+#define DVD_JPEG_444 1
+/* Worst-case file bytes and scratch bytes for an h x w image; host-only.  A negative DVD_E_* value for a bad shape (h or w
+ * outside 1..65535, or 3 * h * w at 16-pixel granularity >= 2^31) or an unknown subsampling. */
+long dvd_jpeg_bound(int h, int w, int subsampling);
+long dvd_jpeg_scratch_bytes(int h, int w, int subsampling);
+/* img_hwc [h,w,3] u8 (any byte alignment) -> the complete file in out[0 .. *out_len), *out_len (a DEVICE uint64) <=
+ * dvd_jpeg_bound(h, w, subsampling).  quality 1..100.  cap = bytes writable at out: cap below the bound is DVD_E_ARG,
+ * checked like every other argument before anything is launched, so no kernel can write past out + cap.  scratch:
+ * dvd_jpeg_scratch_bytes(h, w, subsampling) device bytes, 16-byte aligned; its previous contents do not matter.  Four
+ * launches on `stream`, no synchronisation, no read-back. */
+int dvd_jpeg_encode_rgb8(const uint8_t* img_hwc, int h, int w, int quality, int subsampling, uint8_t* out, long cap,
+                         unsigned long long* out_len, void* scratch, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -13,7 +13,11 @@ produced from the COARSE flow - bit-identical to the long way (tests/test_gpu_op
 
 `settings.env.png_encoder` chooses who writes the PNG: 'pil' (default, the reference's Image.save on a host copy of the page) or
 'hip' (`dvd_amd.ops.png_encode_to_file`: filtered and compressed where the page lies, only the file crosses to the host - the
-same pixels in a file of other bytes)."""
+same pixels in a file of other bytes).
+
+`settings.env.page_format = 'jpeg'` (default 'png': all of the above, unchanged) writes `warped_<stem>.jpg` instead: baseline
+JFIF at `env.jpeg_quality` (1..100, default 90) and `env.jpeg_subsampling` ('420' default | '444'), encoded on the device by
+`dvd_amd.ops.jpeg_encode_to_file`; `png_encoder` is not consulted."""
 from __future__ import annotations
 
 import os
@@ -25,6 +29,22 @@ from datasets.utils.warping import register_model2
 
 reg_model_bilin = register_model2((512, 512), "bilinear")
 PNG_ENCODERS = ("pil", "hip")
+PAGE_FORMATS = ("png", "jpeg")
+JPEG_SUBSAMPLINGS = ("420", "444")
+
+
+def page_settings(env):
+    """(page_format, jpeg_quality, jpeg_subsampling) of `env`, each checked: ValueError names the setting."""
+    fmt = getattr(env, "page_format", "png")
+    quality = getattr(env, "jpeg_quality", 90)
+    subsampling = getattr(env, "jpeg_subsampling", "420")
+    if fmt not in PAGE_FORMATS:
+        raise ValueError(f"env.page_format must be 'png' or 'jpeg', got {fmt!r}")
+    if isinstance(quality, bool) or not isinstance(quality, (int, np.integer)) or not 1 <= quality <= 100:
+        raise ValueError(f"env.jpeg_quality must be an integer 1..100, got {quality!r}")
+    if subsampling not in JPEG_SUBSAMPLINGS:
+        raise ValueError(f"env.jpeg_subsampling must be '420' or '444', got {subsampling!r}")
+    return fmt, int(quality), subsampling
 
 
 def _stem(data_path):
@@ -34,14 +54,17 @@ def _stem(data_path):
 
 def visualize_dewarping(settings, sample, data, i, source_vis, data_path, ref_flow=None, *, warped_u8=None):
     """Returns the uint8 [H,W,3] image it wrote (the reference returns None): a NumPy array with png_encoder 'pil', the
-    DEVICE tensor with 'hip' (the page is never copied to the host there)."""
+    DEVICE tensor with 'hip' and with page_format 'jpeg' (the page is never copied to the host there)."""
     encoder = getattr(settings.env, "png_encoder", "pil")
     if encoder not in PNG_ENCODERS:
         raise ValueError(f"env.png_encoder must be 'pil' or 'hip', got {encoder!r}")
+    page_format, quality, subsampling = page_settings(settings.env)
+    if page_format == "jpeg":
+        encoder = "jpeg"                             # the device route below; png_encoder is not consulted
     out_dir = f"vis_hp/{settings.env.eval_dataset_name}/{settings.name}"
     os.makedirs(f"{out_dir}/pred_flow", exist_ok=True)
     os.makedirs(f"{out_dir}/dewarped_pred", exist_ok=True)
-    if encoder == "hip":
+    if encoder in ("hip", "jpeg"):
         import torch
         from dvd_amd import ops
         if warped_u8 is None:                        # the reference's call form: truncated to uint8 on the device
@@ -52,7 +75,10 @@ def visualize_dewarping(settings, sample, data, i, source_vis, data_path, ref_fl
         if not warped_u8.is_cuda:
             warped_u8 = warped_u8.to(sample.device if sample is not None else "cuda")
         warped_u8 = warped_u8.detach().contiguous()
-        ops.png_encode_to_file(warped_u8, f"{out_dir}/dewarped_pred/warped_{_stem(data_path)}.png")
+        if encoder == "jpeg":
+            ops.jpeg_encode_to_file(warped_u8, f"{out_dir}/dewarped_pred/warped_{_stem(data_path)}.jpg", quality, subsampling)
+        else:
+            ops.png_encode_to_file(warped_u8, f"{out_dir}/dewarped_pred/warped_{_stem(data_path)}.png")
     elif warped_u8 is None:
         warped = reg_model_bilin([source_vis.to(sample.device).float(), sample])
         warped_u8 = warped[0].permute(1, 2, 0).detach().cpu().numpy().astype(np.uint8)
