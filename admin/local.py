@@ -65,6 +65,10 @@ _DEFAULTS = {
     "page_format": "png",
     "jpeg_quality": 90,         # 1..100, PIL's `quality` scale (the Annex K tables scaled by the usual rule)
     "jpeg_subsampling": "420",  # '420' | '444'
+    # who decodes the input photograph of the image-directory path: 'pil' (the loader decodes on the CPU, the pixels cross to
+    # the device) | 'hip' (a .jpg/.jpeg FILE crosses and ops.jpeg_decode makes the same bytes there; a file the device decoder
+    # does not cover, and every other format, is decoded by PIL with one log line naming the reason - DESIGN.md 4.6)
+    "image_decoder": "pil",
     "num_synthetic_docs": 4,
     "full_res": (1024, 768), # synthetic full-resolution source size (H, W)
     "conditioning_dir": "",   # directory of per-document conditioning .npz files (skips ingest + pre-stage nets)

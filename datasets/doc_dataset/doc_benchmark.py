@@ -10,7 +10,15 @@ carries
     path              str                                        - as the reference (the file's full path)
 
 and NOT `source_image`: `run_evaluation_docunet` computes it from `source_image_ori` on the device when a loader item
-lacks it, and takes it as given when an item has it (a loader built on the reference's own cv2 dataset)."""
+lacks it, and takes it as given when an item has it (a loader built on the reference's own cv2 dataset).
+
+With `decode='hip'` (env.image_decoder) a `.jpg` / `.jpeg` item is not decoded here at all: it carries
+
+    file_bytes        [n] uint8   the file as it is on disk
+    path              str
+
+and `dvd_amd.evaluation.decode_documents` makes the same RGB bytes on the device (ops.decode_image: the HIP JPEG decoder,
+or PIL for a file it does not cover).  Other extensions behave as with 'pil'."""
 from __future__ import annotations
 
 import os
@@ -18,13 +26,17 @@ import os
 import numpy as np
 from torch.utils.data import Dataset
 
+_JPEG_EXTS = (".jpg", ".jpeg")
 _IMAGE_EXTS = (".jpg", ".jpeg", ".png", ".bmp", ".tif", ".tiff", ".webp")
 
 
 class Doc_benchmark(Dataset):
-    def __init__(self, data_root, input_transform) -> None:
+    def __init__(self, data_root, input_transform, decode="pil") -> None:
+        if decode not in ("pil", "hip"):
+            raise ValueError(f"Doc_benchmark: decode must be 'pil' or 'hip', got {decode!r}")
         self.data_root = data_root
         self.input_transform = input_transform
+        self.decode = decode
         self.init_img_parms()
 
     def init_img_parms(self):
@@ -42,5 +54,8 @@ class Doc_benchmark(Dataset):
 
     def __getitem__(self, idx):
         sample_path = os.path.join(self.data_root, self.data_paths[idx])
+        if self.decode == "hip" and sample_path.lower().endswith(_JPEG_EXTS):
+            import torch
+            return {"file_bytes": torch.from_numpy(np.fromfile(sample_path, dtype=np.uint8)), "path": sample_path}
         img_ori = self.load_rgb_u8(sample_path)
         return {"source_image_ori": self.input_transform(img_ori), "path": sample_path}

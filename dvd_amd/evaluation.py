@@ -4,7 +4,8 @@ the HIP engine.
 
 Documents arrive either as decoded images (dict key "image_u8": [H,W,3] uint8 RGB) - then the ingest kernel
 (doc_benchmark.py:75-97) and the pre-stage conditioning nets (evaluation.py:162-216, dvd_amd/prestage.py) run first -
-or as dicts of ready conditioning tensors (synthetic or loaded from .npz), i.e. exactly the tensors those nets produce."""
+as JPEG files (key "file_bytes", env.image_decoder = 'hip': decoded on the device first, `decode_documents`), or as dicts
+of ready conditioning tensors (synthetic or loaded from .npz), i.e. exactly the tensors those nets produce."""
 from __future__ import annotations
 
 import os
@@ -65,6 +66,15 @@ def npz_documents(settings, indices, files):
         yield d
 
 
+def decode_documents(batch, device, log=None):
+    """Documents that arrive as FILES (`file_bytes`: the 1-D uint8 tensor a Doc_benchmark(decode='hip') item carries) get
+    `image_u8` [H,W,3] uint8 on the device - the bytes PIL's decode of the file gives, EXIF orientation applied - and
+    `decode_route` ('hip' | 'pil': ops.decode_image).  Other documents pass through untouched."""
+    for d in batch:
+        if "file_bytes" in d and "image_u8" not in d and "y512" not in d:
+            d["image_u8"], d["decode_route"] = ops.decode_image(d.pop("file_bytes"), device, log=log)
+
+
 def prepare_conditioning(batch, device, grid, prestage_models, use_init_flow=False):
     """Documents given as decoded images: ingest (cv2.resize to 512^2, / 255; doc_benchmark.py:84-88) and the pre-stage
     nets (evaluation.py:162-216) fill in y512 / mask_cat / mask_y512 / line_msk / src_u8 as DEVICE tensors.  Documents
@@ -72,6 +82,7 @@ def prepare_conditioning(batch, device, grid, prestage_models, use_init_flow=Fal
     env.conditioning_dir) pass through untouched and need no pre-stage nets.  use_init_flow: every document also gets
     `init_flow` [2,G,G] from GeoTr (evaluation.py:172-178), in the same pre-stage pass when that runs."""
     from . import prestage
+    decode_documents(batch, device)
     need_ingest = [d for d in batch if "image_u8" in d and "y512" not in d]
     imgs = [(d["image_u8"] if th.is_tensor(d["image_u8"]) else th.from_numpy(d["image_u8"])).to(device).contiguous()
             for d in need_ingest]
@@ -112,7 +123,10 @@ def documents_of(item):
       * the reference's (doc_benchmark.py:91-97 through `DataLoader(batch_size=b)`): `source_image` [b,3,512,512] f32 in 0..1
         (may be absent: computed on the GPU, see datasets/doc_dataset/doc_benchmark.py), `source_image_ori` [b,3,H,W]
         (0..255, float or uint8), `path` list of b file names;
-      * this package's document dicts (`image_u8` [H,W,3] or ready conditioning tensors + `src_u8`, `path` = a stem)."""
+      * this package's document dicts (`image_u8` [H,W,3] or ready conditioning tensors + `src_u8`, `path` = a stem);
+      * a Doc_benchmark(decode='hip') item: `file_bytes` [b,n] (or [n]) uint8, the JPEG file itself, and `path`."""
+    if "file_bytes" in item and "path" in item and not isinstance(item["path"], str):   # through DataLoader(batch_size=b)
+        return [{"path": path, "file_bytes": item["file_bytes"][j]} for j, path in enumerate(item["path"])]
     if "source_image_ori" not in item and "source_image" not in item:
         return [item]
     ori = item.get("source_image_ori", item.get("source_image"))
@@ -186,6 +200,8 @@ def run_evaluation_docunet(settings, logger, val_loader, diffusion, model, pretr
     batch (documents of one size or of different sizes alike; env.unwarp_mode 'bilinear' | 'bicubic' is its interpolation), and - if env.visualize - `visualize_dewarping` writes the PNG where the reference writes it
     (env.png_encoder 'pil' | 'hip': PIL on a host copy, or the HIP encoder on the device; env.page_format 'jpeg' writes
     warped_<stem>.jpg with the HIP JPEG encoder instead, at env.jpeg_quality and env.jpeg_subsampling).
+    env.image_decoder 'pil' | 'hip' says who decodes the input photograph: the loader (PIL), or - for items that carry the JPEG
+    file as `file_bytes` - the HIP decoder on the device (`decode_documents`; the same bytes either way).
     The pre-stage models may all be None when every document carries ready conditioning tensors.
     With env.gt_dir set, every dewarped page is scored against `<gt_dir>/<stem>.png` (`gt_candidates`) with MS-SSIM
     (ops.ms_ssim_u8, env.metric_preset): logged per document and as a mean, written to ms_ssim.txt beside the pictures and
@@ -200,6 +216,9 @@ def run_evaluation_docunet(settings, logger, val_loader, diffusion, model, pretr
     if png_encoder not in ("pil", "hip"):
         raise ValueError(f"env.png_encoder must be 'pil' or 'hip', got {png_encoder!r}")
     page_settings(env)                                          # env.page_format, env.jpeg_quality, env.jpeg_subsampling
+    image_decoder = getattr(env, "image_decoder", "pil")        # who decodes the input photograph: the loader reads it
+    if image_decoder not in ("pil", "hip"):
+        raise ValueError(f"env.image_decoder must be 'pil' or 'hip', got {image_decoder!r}")
     device = next(model.parameters()).device
     nets = (pretrained_dewarp_model, pretrained_seg_model, pretrained_line_seg_model)
     prestage_models = None if all(m is None for m in nets) else nets

@@ -87,6 +87,20 @@ PNG_SEGMENT = 32768   # DVD_PNG_SEGMENT: filtered-stream bytes per IDAT chunk of
 
 JPEG_420, JPEG_444 = 0, 1                  # DVD_JPEG_*: chroma subsampling of the JPEG encoder
 
+
+class JpegDecInfo(C.Structure):
+    """dvd_jpegdec_info: what dvd_jpegdec_probe reads from a JPEG file's header."""
+    _fields_ = [("h", C.c_int), ("w", C.c_int), ("out_h", C.c_int), ("out_w", C.c_int), ("components", C.c_int),
+                ("hs", C.c_int), ("vs", C.c_int), ("orientation", C.c_int), ("restart_interval", C.c_int),
+                ("scan_offset", C.c_long), ("scan_bytes", C.c_long), ("blocks", C.c_long), ("scratch_bytes", C.c_long)]
+
+
+# DVD_E_JPEG_*: why the JPEG decoder hands a file back (a refusal on the host, or NOSYNC / DATA after the entropy decoder ran)
+JPEG_DECODE_CODES = {-20: "HEADER", -21: "PROGRESSIVE", -22: "EXTENDED", -23: "LOSSLESS", -24: "ARITHMETIC", -25: "PRECISION",
+                     -26: "COMPONENTS", -27: "ADOBE", -28: "SAMPLING", -29: "SCANS", -30: "QUANT16", -31: "TABLE", -32: "SIZE",
+                     -33: "ORIENTATION", -34: "NOSYNC", -35: "DATA"}
+JPEGDEC_SUBSEQ = 128   # DVD_JPEGDEC_SUBSEQ: bytes of the scan per lane of the entropy decoder
+
 RAGGED_CAP = 64   # DVD_RAGGED_CAP: documents per launch of the ragged entry points (larger batches are cut by the library)
 
 NON_STATUS = {"dvd_last_error", "dvd_version", "dvd_engine_workspace_bytes", "dvd_engine_tensor_count",
@@ -163,6 +177,8 @@ SIGNATURES = {
     "dvd_jpeg_bound": [C.c_int, C.c_int, C.c_int],
     "dvd_jpeg_scratch_bytes": [C.c_int, C.c_int, C.c_int],
     "dvd_jpeg_encode_rgb8": [c_void, C.c_int, C.c_int, C.c_int, C.c_int, c_void, C.c_long, c_void, c_void, c_void],
+    "dvd_jpegdec_probe": [c_void, C.c_long, C.POINTER(JpegDecInfo)],
+    "dvd_jpeg_decode_rgb8": [c_void, c_void, C.c_long, c_void, C.c_long, C.c_int, C.POINTER(C.c_int), c_void, c_void],
     "dvd_dither_f16": [c_void, c_void, c_void, C.c_long, C.c_uint, C.c_uint, c_void],
     "dvd_engine_create": [C.c_int, C.c_int, C.c_int, C.POINTER(c_void)],
     "dvd_engine_destroy": [c_void],

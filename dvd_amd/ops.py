@@ -9,6 +9,7 @@ HIP library.  These wrappers mirror the reference callables they replace:
 from __future__ import annotations
 
 import ctypes as C
+import os
 
 import numpy as np
 import torch
@@ -571,3 +572,130 @@ def jpeg_encode_to_file(img_hwc_u8: torch.Tensor, path: str, quality: int = 90, 
     with open(path, "wb") as f:
         f.write(data.tobytes())
     return int(data.size)
+
+
+# ---- JPEG decoder for the input photograph (dvd_amd/csrc/jpegdec.hip; definition: DESIGN.md 4.6) ------------------------------
+class JpegUnsupported(ValueError):
+    """The device decoder hands the file back: a refusal of the host-side header check (progressive, 4 components, ...), or
+    NOSYNC / DATA after the entropy decoder ran.  `code` is the name of the library's DVD_E_JPEG_* code.  A normal outcome:
+    decode_image falls back to PIL."""
+
+    def __init__(self, code: str, message: str):
+        super().__init__(f"{code}: {message}")
+        self.code = code
+
+
+def _jpeg_file(data, name):
+    """The file as (host uint8 array, the caller's device tensor or None)."""
+    if torch.is_tensor(data):
+        if data.dtype != torch.uint8 or data.dim() != 1 or not data.is_contiguous():
+            raise ValueError(f"{name}: expected a contiguous 1-D uint8 tensor, got {data.dtype} {tuple(data.shape)}")
+        host = data.cpu().numpy()
+        dev = data if data.is_cuda else None
+    elif isinstance(data, (bytes, bytearray, memoryview)):
+        host, dev = np.frombuffer(bytearray(data), dtype=np.uint8), None   # a writable copy: torch.from_numpy takes it
+    elif isinstance(data, np.ndarray) and data.dtype == np.uint8 and data.ndim == 1:
+        host, dev = np.ascontiguousarray(data), None
+    else:
+        raise ValueError(f"{name}: expected bytes or a 1-D uint8 tensor, got {type(data)}")
+    if host.size < 1:
+        raise ValueError(f"{name}: an empty file")
+    return host, dev
+
+
+def _jpeg_status(name, rc):
+    if rc == 0:
+        return
+    message = lib.raw().dvd_last_error().decode()
+    if rc in lib.JPEG_DECODE_CODES:
+        raise JpegUnsupported(lib.JPEG_DECODE_CODES[rc], message)
+    raise lib.DvdError(f"{name} failed ({rc}): {message}")
+
+
+def _jpeg_probe(host, name):
+    info = lib.JpegDecInfo()
+    _jpeg_status(name, lib.raw().dvd_jpegdec_probe(C.c_void_p(host.ctypes.data), host.size, C.byref(info)))
+    return info
+
+
+def jpeg_probe(data) -> dict:
+    """What the decoder reads from the header of a JPEG file (bytes or a 1-D uint8 tensor), on the host: h, w, out_h, out_w
+    (after the EXIF orientation), components, hs, vs, orientation, restart_interval, scan_offset, scan_bytes, blocks,
+    scratch_bytes.  Raises JpegUnsupported for a file the device decoder refuses."""
+    info = _jpeg_probe(_jpeg_file(data, "jpeg_probe")[0], "jpeg_probe")
+    return {k: int(getattr(info, k)) for k, _ in lib.JpegDecInfo._fields_}
+
+
+def jpeg_decode(data, device=None, max_iters: int = None, scratch: torch.Tensor = None, out: torch.Tensor = None,
+                return_iters: bool = False):
+    """A baseline JPEG file (bytes or a 1-D uint8 tensor, on the host or already on the device) -> [H,W,3] uint8 RGB on the
+    device with the EXIF orientation applied: the bytes ImageOps.exif_transpose(Image.open(f)).convert("RGB") gives.  Only
+    the file crosses to the device.  max_iters caps the entropy decoder's fixpoint iterations (None: the library's 1024).
+    scratch (optional): a uint8 device buffer of at least jpeg_probe(data)['scratch_bytes'] bytes to reuse between calls.
+    out (optional): a contiguous uint8 device tensor of >= 3 H W elements, at any byte address, to decode into.
+    return_iters: also return how many iterations ran.  Raises JpegUnsupported (a ValueError) for a file the decoder
+    refuses, for 'NOSYNC' (max_iters reached) and for 'DATA' (the scan does not hold the header's blocks).  The call
+    synchronises its stream (dvd_hip.h: every 16 iterations and once after the count pass)."""
+    host, dev_file = _jpeg_file(data, "jpeg_decode")
+    if max_iters is not None and (isinstance(max_iters, bool) or not isinstance(max_iters, (int, np.integer)) or max_iters < 1):
+        raise ValueError(f"jpeg_decode: max_iters must be a positive integer or None, got {max_iters!r}")
+    info = _jpeg_probe(host, "jpeg_decode")
+    if dev_file is None:
+        dev_file = torch.from_numpy(host).to(torch.device("cuda") if device is None else device)
+    elif device is not None and torch.device(device) != dev_file.device:
+        dev_file = dev_file.to(device)
+    dev = dev_file.device
+    _chk(dev_file, torch.uint8, "file")
+    need, numel = int(info.scratch_bytes), 3 * info.h * info.w
+    if scratch is None:
+        scratch = torch.empty(need, dtype=torch.uint8, device=dev)
+    elif scratch.dtype != torch.uint8 or not scratch.is_contiguous() or scratch.numel() < need or scratch.device != dev:
+        raise ValueError(f"jpeg_decode: scratch must be a contiguous uint8 buffer of >= {need} bytes on {dev}")
+    if out is None:
+        out = torch.empty(numel, dtype=torch.uint8, device=dev)
+    elif out.dtype != torch.uint8 or not out.is_contiguous() or out.numel() < numel or out.device != dev:
+        raise ValueError(f"jpeg_decode: out must be a contiguous uint8 tensor of >= {numel} elements on {dev}")
+    iters = C.c_int(0)
+    with torch.cuda.device(dev):
+        rc = lib.raw().dvd_jpeg_decode_rgb8(C.c_void_p(host.ctypes.data), ptr(dev_file), host.size, ptr(out), out.numel(),
+                                            0 if max_iters is None else int(max_iters), C.byref(iters), ptr(scratch), stream_ptr())
+    _jpeg_status("dvd_jpeg_decode_rgb8", rc)
+    img = out.view(-1)[:numel].view(info.out_h, info.out_w, 3)
+    return (img, int(iters.value)) if return_iters else img
+
+
+def jpeg_decode_from_file(path: str, device=None, max_iters: int = None) -> torch.Tensor:
+    """Read `path` and decode it on the device (jpeg_decode)."""
+    with open(path, "rb") as f:
+        return jpeg_decode(f.read(), device=device, max_iters=max_iters)
+
+
+def pil_decode_rgb8(path_or_bytes) -> np.ndarray:
+    """The host decoder every route falls back to: PIL, EXIF orientation applied, RGB, [H,W,3] uint8."""
+    import io
+    from PIL import Image, ImageOps
+    src = path_or_bytes if isinstance(path_or_bytes, (str, os.PathLike)) else io.BytesIO(bytes(path_or_bytes))
+    im = ImageOps.exif_transpose(Image.open(src))
+    return np.array(im.convert("RGB"), dtype=np.uint8)       # a writable, contiguous copy
+
+
+def decode_image(path_or_bytes, device=None, max_iters: int = None, log=None):
+    """An image file (a path, bytes or a 1-D uint8 tensor) -> ([H,W,3] uint8 RGB on the device, the route that ran): 'hip'
+    = the device decoder, 'pil' = PIL on the host plus an upload of the pixels, for every file the device decoder hands back
+    (JpegUnsupported) - with ONE line to `log` (default: dvd_amd.logger.info) that names the reason.  The pixels are the
+    same on both routes."""
+    if isinstance(path_or_bytes, (str, os.PathLike)):
+        with open(path_or_bytes, "rb") as f:
+            data, what = f.read(), str(path_or_bytes)
+    else:
+        data = path_or_bytes.cpu().numpy().tobytes() if torch.is_tensor(path_or_bytes) else bytes(path_or_bytes)
+        what = f"<{len(data)} bytes>"
+    try:
+        return jpeg_decode(data, device=device, max_iters=max_iters), "hip"
+    except JpegUnsupported as e:
+        if log is None:
+            from . import logger
+            log = logger.info
+        log(f"{what}: decoded by PIL, not on the device: {e}")
+    pixels = torch.from_numpy(pil_decode_rgb8(data))
+    return pixels.to(torch.device("cuda") if device is None else device), "pil"

@@ -530,6 +530,57 @@ long dvd_jpeg_scratch_bytes(int h, int w, int subsampling);
 int dvd_jpeg_encode_rgb8(const uint8_t* img_hwc, int h, int w, int quality, int subsampling, uint8_t* out, long cap,
                          unsigned long long* out_len, void* scratch, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Baseline JPEG decoder for the input photograph: the FILE goes to the device, the [H,W,3] u8 RGB page (EXIF orientation
+ * applied) is made there - DESIGN.md 4.6.  The pixels are libjpeg's for such a file, integer arithmetic throughout
+ * (accurate integer IDCT, triangle chroma upsampling, 16-bit fixed-point colour), i.e. byte for byte what
+ * ImageOps.exif_transpose(Image.open(f)).convert("RGB") returns.
+ * Accepted: SOF0, 8-bit samples and tables, Huffman, ONE scan of all components, 3 components as 4:4:4 / 4:2:2 / 4:2:0 or
+ * 1 component at 1x1, with or without DRI.  Everything else is REFUSED on the host with one of the codes below before
+ * anything is launched; a refusal is a normal outcome (the caller decodes on the CPU).
+ * ---------------------------------------------------------------------------------------- */
+#define DVD_E_JPEG_HEADER (-20)       /* no SOI, a truncated or malformed header, no SOF / SOS */
+#define DVD_E_JPEG_PROGRESSIVE (-21)  /* SOF2 */
+#define DVD_E_JPEG_EXTENDED (-22)     /* SOF1 */
+#define DVD_E_JPEG_LOSSLESS (-23)     /* SOF3, 5..7: lossless, hierarchical */
+#define DVD_E_JPEG_ARITHMETIC (-24)   /* SOF9..15, DAC */
+#define DVD_E_JPEG_PRECISION (-25)    /* samples of other than 8 bits */
+#define DVD_E_JPEG_COMPONENTS (-26)   /* not 1 or 3 components, or ids 'R','G','B' without JFIF / Adobe (an RGB file) */
+#define DVD_E_JPEG_ADOBE (-27)        /* an Adobe APP14 segment with transform 0 (RGB) */
+#define DVD_E_JPEG_SAMPLING (-28)     /* sampling other than 4:4:4, 4:2:2, 4:2:0 / gray 1x1 */
+#define DVD_E_JPEG_SCANS (-29)        /* more than one SOS */
+#define DVD_E_JPEG_QUANT16 (-30)      /* a 16-bit quantisation table */
+#define DVD_E_JPEG_TABLE (-31)        /* a quantisation or Huffman table the scan names is missing (or has id > 1 / > 3) */
+#define DVD_E_JPEG_SIZE (-32)         /* 3 h w >= 2^31 */
+#define DVD_E_JPEG_ORIENTATION (-33)  /* no EXIF orientation but an XMP packet that names one */
+#define DVD_E_JPEG_NOSYNC (-34)       /* the entropy decoder's fixpoint took more than max_iters iterations */
+#define DVD_E_JPEG_DATA (-35)         /* the scan does not hold the blocks the header implies */
+#define DVD_JPEGDEC_SUBSEQ 128        /* bytes of the scan per lane of the entropy decoder */
+typedef struct dvd_jpegdec_info {
+  int h, w;                /* as in SOF0 */
+  int out_h, out_w;        /* after the EXIF orientation: swapped for orientations 5..8 */
+  int components;          /* 1 or 3 */
+  int hs, vs;              /* luma sampling factors: 1x1, 2x1 or 2x2 */
+  int orientation;         /* 1..8 */
+  int restart_interval;    /* MCUs, 0 = none */
+  long scan_offset;        /* first byte of the entropy-coded data in the file */
+  long scan_bytes;         /* its bytes, stuffing and RSTn markers included */
+  long blocks;             /* 8 x 8 blocks of the scan */
+  long scratch_bytes;      /* device bytes dvd_jpeg_decode_rgb8 needs */
+} dvd_jpegdec_info;
+/* Host only: parses the n bytes of the file at file_host; 0 and *info, or the refusal code (dvd_last_error says why). */
+int dvd_jpegdec_probe(const uint8_t* file_host, long n, dvd_jpegdec_info* info);
+/* file_host / file_dev: the same n bytes on the host (parsed there) and on the device (the kernels read the scan there).
+ * out_hwc [out_h,out_w,3] u8, any byte alignment; cap = bytes writable at it: cap < 3 h w is DVD_E_ARG.  Every bad
+ * argument and every refusal is decided before anything is launched.  scratch: info.scratch_bytes device bytes, 16-byte
+ * aligned; its contents do not matter.  max_iters >= 1 (0 = the default, 1024) caps the fixpoint iterations; *iters_out
+ * (host, may be null) receives how many ran.  SYNCHRONISES `stream` after every 16 iterations (a 4-byte read-back: the
+ * last iteration that changed a state) and once after the count pass (a 4-byte read-back: the blocks found); from there
+ * on - coefficients, DC sums, IDCT, upsampling + colour + orientation - the launches are asynchronous.  Returns 0, a
+ * refusal code, DVD_E_JPEG_NOSYNC or DVD_E_JPEG_DATA (out_hwc is untouched then), DVD_E_ARG or DVD_E_LAUNCH. */
+int dvd_jpeg_decode_rgb8(const uint8_t* file_host, const uint8_t* file_dev, long n, uint8_t* out_hwc, long cap,
+                         int max_iters, int* iters_out, void* scratch, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
