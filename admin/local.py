@@ -59,6 +59,9 @@ _DEFAULTS = {
     # who writes dewarped_pred/warped_<stem>.png: 'pil' (the reference: copy the page to the host, Image.save) | 'hip'
     # (ops.png_encode on the device, only the compressed file crosses to the host; the same pixels, other bytes - DESIGN.md 4.4)
     "png_encoder": "pil",
+    # the deflate blocks of the 'hip' PNG encoder: 'fixed' (one fixed-Huffman block per segment) | 'dynamic' (per segment the
+    # smaller of a dynamic-Huffman and the fixed block: the same pixels in a file about a third smaller - DESIGN.md 4.4)
+    "png_huffman": "fixed",
     # the container of dewarped_pred/warped_<stem>: 'png' (the reference; png_encoder chooses who writes it) | 'jpeg'
     # (warped_<stem>.jpg: baseline JFIF encoded on the device by ops.jpeg_encode, only the file crosses to the host; png_encoder
     # is not consulted - DESIGN.md 4.5)

@@ -4,6 +4,8 @@
 //   png_filter_kernel     one row per workgroup: the five filters' costs, the winner's bytes -> the filtered stream
 //   png_compress_kernel   one wave per DVD_PNG_SEGMENT bytes of that stream: LZ77 + one fixed-Huffman block -> the segment's slot,
 //                         its length and Adler-32 partials
+//   png_compress_dyn_kernel  DVD_PNG_HUFFMAN_DYNAMIC: the same token loop into 16-bit tokens, their histograms, the two
+//                         length-limited codes, then the smaller of the dynamic and the fixed block written by all lanes
 //   png_layout_kernel     exclusive scan of the chunk sizes, signature, IHDR, IEND, the Adler-32, the file's length
 //   png_gather_kernel     one workgroup per segment: its IDAT chunk (length, type, data, CRC-32) into the contiguous file
 #include "common.h"
@@ -69,6 +71,11 @@ struct WaveOps {
   }
   static __device__ __forceinline__ void store32(uint32_t* p, uint32_t v) { if (threadIdx.x == 0) *p = v; }
   static __device__ __forceinline__ void store16(uint16_t* p, uint16_t v) { *p = v; }   // all lanes: one address, one value
+  static __device__ __forceinline__ void store_tok(uint16_t* p, uint16_t v) { if (threadIdx.x == 0) *p = v; }
+  static __device__ __forceinline__ int lane() { return threadIdx.x; }
+  static __device__ __forceinline__ int lanes() { return kWave; }
+  // an LDS integer atomic: integer sums do not depend on the order of the additions, so the histogram is the tokens' alone
+  static __device__ __forceinline__ void count(uint32_t* p) { atomicAdd(p, 1u); }
 };
 
 // LDS: the segment (kSeg bytes) and the hash table (8 KB), both written by this kernel before they are read.
@@ -97,6 +104,105 @@ __global__ void __launch_bounds__(kWave) png_compress_kernel(const uint8_t* __re
   }
   const int len = compress_segment<WaveOps>(seg, n, table, (uint32_t*)(slots + s * kSlot), s == 0, s == nseg - 1);
   if (lane == 0) meta[s] = SegMeta{(uint32_t)len, (uint32_t)(a % kAdlerMod), (uint32_t)(b % kAdlerMod), 0u};
+}
+
+// ---------------------------------------------------------------- segment compressor, dynamic Huffman ----------------------
+// The tokens go to global scratch (2 bytes per stream byte, one 64 KiB run per segment, written by lane 0 as the token loop
+// produces them and read back by all lanes, from L2), not to LDS: segment + table + tokens would be 104 KB, one workgroup per
+// CU; this way the kernel keeps the fixed route's 40 KB and four workgroups per CU.  Once the token loop has ended, the
+// segment's bytes are dead and the DynState (histograms, codes, staging dwords) takes their place in LDS.
+//   1. token loop (wave-uniform, as in png_compress_kernel), entries to tok[]
+//   2. histograms: the lanes stride over the entries, LDS integer atomics
+//   3. lane 0: plan_block - the code lengths, the header, both block types priced, the code tables of the smaller one
+//   4. the block's header through the serial bit writer (lane 0 stores), continued by
+//   5. the parallel emitter: 64 entries per step, one per lane; a lane looks up its token's bits, an inclusive scan over the
+//      wave gives its bit offset, it ORs its (at most 3) dwords into the LDS staging area - two lanes that share a dword are
+//      combined there -, then the lanes store the step's complete dwords to the slot and the last partial dword is carried
+//   6. end of block, the stored block and 03 00 through the serial bit writer again.
+__global__ void __launch_bounds__(kWave) png_compress_dyn_kernel(const uint8_t* __restrict__ filt, long stream, int nseg,
+                                                                  uint8_t* __restrict__ slots, uint16_t* tokens,
+                                                                  SegMeta* __restrict__ meta) {
+  __shared__ __attribute__((aligned(16))) uint8_t seg[kSeg];
+  __shared__ uint16_t table[kHashSize];
+  static_assert(sizeof(DynState) <= kSeg && alignof(DynState) <= 16, "the DynState takes the segment's place");
+  const int lane = threadIdx.x;
+  const long s = blockIdx.x;
+  const long base = s * kSeg;
+  const int n = (int)(stream - base < kSeg ? stream - base : kSeg);
+  const uint4* src = (const uint4*)(filt + base);
+  for (int k = lane; k * 16 < n; k += kWave) ((uint4*)seg)[k] = src[k];
+  for (int k = lane; k < kHashSize; k += kWave) table[k] = (uint16_t)kEmpty;
+  __syncthreads();
+  unsigned long long a = 0, b = 0;
+  for (int k = lane; k < n; k += kWave) {
+    a += seg[k];
+    b += (unsigned long long)(n - k) * seg[k];
+  }
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) {
+    a += __shfl_down(a, d, 64);
+    b += __shfl_down(b, d, 64);
+  }
+  if (lane == 0) meta[s] = SegMeta{0u, (uint32_t)(a % kAdlerMod), (uint32_t)(b % kAdlerMod), 0u};
+  uint16_t* tok = tokens + s * kSeg;           // at most n <= kSeg entries
+  TokenSink<WaveOps> sink{tok, 0};
+  tokenise<WaveOps>(seg, n, table, sink);
+  const int m = sink.count;
+  __syncthreads();                             // seg is dead from here; lane 0's entries are visible to the wave
+  DynState& st = *reinterpret_cast<DynState*>(seg);
+  for (int k = lane; k < 288; k += kWave) st.ll_freq[k] = k == 256 ? 1u : 0u;   // one end of block
+  if (lane < 32) st.d_freq[lane] = 0;
+  for (int k = lane; k < kStageWords; k += kWave) st.stage[k] = 0;
+  __syncthreads();
+  count_tokens<WaveOps>(tok, m, st);
+  __syncthreads();
+  if (lane == 0) plan_block(st);
+  __syncthreads();
+  BitWriter<WaveOps> bw{0, 0, (uint32_t*)(slots + s * kSlot), 0};
+  put_block_header(bw, st, s == 0);
+  int words = bw.words, cnt = bw.cnt;          // wave-uniform: dwords stored, bits pending in stage[0]
+  if (lane == 0) st.stage[0] = (uint32_t)bw.buf;
+  __syncthreads();
+  for (int i0 = 0; i0 < m; i0 += kWave) {
+    const int i = i0 + lane;
+    uint64_t bits = 0;
+    int nb = 0;
+    if (i < m) {
+      const uint32_t e = tok[i];
+      if (!(e & kDistFlag)) bits = token_bits(st, e, e >= 256 ? (uint32_t)tok[i + 1] : 0u, nb);   // a head's distance word: i + 1 < m
+    }
+    int incl = nb;
+#pragma unroll
+    for (int d = 1; d < kWave; d <<= 1) {
+      const int t = __shfl_up(incl, d, 64);
+      if (lane >= d) incl += t;
+    }
+    const int end = cnt + __shfl(incl, kWave - 1, 64);
+    if (nb) {
+      const int off = cnt + incl - nb;         // <= 31 + 63 * 48: dwords 0 .. 97 of the staging area
+      const int w = off >> 5, sh = off & 31;
+      const uint64_t lo = bits << sh;
+      const uint32_t hi = sh ? (uint32_t)(bits >> (64 - sh)) : 0u;
+      atomicOr(&st.stage[w], (uint32_t)lo);    // LDS; OR does not depend on the order
+      if ((uint32_t)(lo >> 32)) atomicOr(&st.stage[w + 1], (uint32_t)(lo >> 32));
+      if (hi) atomicOr(&st.stage[w + 2], hi);
+    }
+    __syncthreads();
+    const int full = end >> 5;                 // <= 96 complete dwords
+    const uint32_t carry = st.stage[full];
+    for (int k = lane; k < full; k += kWave) bw.out[words + k] = st.stage[k];
+    __syncthreads();
+    for (int k = lane; k <= full; k += kWave) st.stage[k] = k == 0 ? carry : 0u;
+    __syncthreads();
+    words += full;
+    cnt = end & 31;
+  }
+  bw.words = words;
+  bw.cnt = cnt;
+  bw.buf = WaveOps::uniform(st.stage[0]);
+  bw.put(WaveOps::uniform(st.ll_code[256]), (int)WaveOps::uniform(st.ll_len[256]));   // end of block
+  const int len = finish_segment(bw, s == nseg - 1);
+  if (lane == 0) meta[s].len = (uint32_t)len;
 }
 
 // ---------------------------------------------------------------- layout ----------------------------------------------------
@@ -195,7 +301,7 @@ __global__ void __launch_bounds__(256) png_gather_kernel(const uint8_t* __restri
 
 static size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
-struct Layout { size_t filt, slots, meta, offs, adler, total; };
+struct Layout { size_t filt, slots, meta, offs, adler, total, tokens, total_dyn; };
 
 static Layout layout_of(long stream) {
   const size_t ns = (size_t)segments(stream);
@@ -205,7 +311,9 @@ static Layout layout_of(long stream) {
   l.meta = l.slots + ns * (size_t)kSlot;
   l.offs = l.meta + align_up(ns * sizeof(SegMeta), 256);
   l.adler = l.offs + align_up(ns * sizeof(unsigned long long), 256);
-  l.total = l.adler + 256;
+  l.total = l.adler + 256;                     // the fixed route's scratch ends here
+  l.tokens = l.total;                          // the dynamic route's: 2 bytes per stream byte of a full segment
+  l.total_dyn = l.tokens + ns * (size_t)kSeg * sizeof(uint16_t);
   return l;
 }
 
@@ -233,16 +341,35 @@ extern "C" long dvd_png_scratch_bytes(int h, int w) {
   return (long)png::layout_of(png::stream_bytes(h, w)).total;
 }
 
-extern "C" int dvd_png_encode_rgb8(const uint8_t* img_hwc, int h, int w, uint8_t* out, long cap, unsigned long long* out_len,
-                                   void* scratch, void* stream) {
-  DVD_REQUIRE(img_hwc && out && out_len && scratch, "png_encode_rgb8: null pointer");
-  DVD_REQUIRE(h >= 1 && w >= 1, "png_encode_rgb8: bad shape %dx%d (h >= 1, w >= 1)", h, w);
-  DVD_REQUIRE(png::shape_ok(h, w), "png_encode_rgb8: image %dx%d too large (h * (3 w + 1) must be below 2^31)", h, w);
+extern "C" long dvd_png_scratch_bytes_huff(int h, int w, int huffman) {
+  if (huffman != DVD_PNG_HUFFMAN_FIXED && huffman != DVD_PNG_HUFFMAN_DYNAMIC) {
+    set_error("png_scratch_bytes_huff: huffman %d is neither DVD_PNG_HUFFMAN_FIXED nor DVD_PNG_HUFFMAN_DYNAMIC", huffman);
+    return DVD_E_ARG;
+  }
+  if (!png::shape_ok(h, w)) {
+    set_error("png_scratch_bytes_huff: bad shape %dx%d (h >= 1, w >= 1, h * (3 w + 1) < 2^31)", h, w);
+    return DVD_E_ARG;
+  }
+  const png::Layout l = png::layout_of(png::stream_bytes(h, w));
+  return (long)(huffman == DVD_PNG_HUFFMAN_DYNAMIC ? l.total_dyn : l.total);
+}
+
+// every check comes before the first launch
+static int png_encode_args(const char* name, const uint8_t* img_hwc, int h, int w, uint8_t* out, long cap,
+                           unsigned long long* out_len, void* scratch) {
+  DVD_REQUIRE(img_hwc && out && out_len && scratch, "%s: null pointer", name);
+  DVD_REQUIRE(h >= 1 && w >= 1, "%s: bad shape %dx%d (h >= 1, w >= 1)", name, h, w);
+  DVD_REQUIRE(png::shape_ok(h, w), "%s: image %dx%d too large (h * (3 w + 1) must be below 2^31)", name, h, w);
+  const long bound = png::file_bound(png::stream_bytes(h, w));
+  // no kernel can write past the caller's buffer
+  DVD_REQUIRE(cap >= bound, "%s: cap %ld below dvd_png_bound(%d, %d) = %ld", name, cap, h, w, bound);
+  DVD_REQUIRE(((uintptr_t)scratch & 15) == 0, "%s: scratch must be 16-byte aligned", name);
+  return DVD_OK;
+}
+
+static int png_encode_launch(const char* name, const uint8_t* img_hwc, int h, int w, uint8_t* out, unsigned long long* out_len,
+                             void* scratch, int huffman, void* stream) {
   const long bytes = png::stream_bytes(h, w);
-  // before anything is launched: no kernel can write past the caller's buffer
-  DVD_REQUIRE(cap >= png::file_bound(bytes), "png_encode_rgb8: cap %ld below dvd_png_bound(%d, %d) = %ld", cap, h, w,
-              png::file_bound(bytes));
-  DVD_REQUIRE(((uintptr_t)scratch & 15) == 0, "png_encode_rgb8: scratch must be 16-byte aligned");
   hipStream_t st = (hipStream_t)stream;
   const int nseg = (int)png::segments(bytes);
   const png::Layout l = png::layout_of(bytes);
@@ -253,8 +380,27 @@ extern "C" int dvd_png_encode_rgb8(const uint8_t* img_hwc, int h, int w, uint8_t
   unsigned long long* offs = (unsigned long long*)(base + l.offs);
   uint32_t* adler = (uint32_t*)(base + l.adler);
   png::png_filter_kernel<<<h, 256, 0, st>>>(img_hwc, w, filt);
-  png::png_compress_kernel<<<nseg, kWave, 0, st>>>(filt, bytes, nseg, slots, meta);
+  if (huffman == DVD_PNG_HUFFMAN_DYNAMIC)
+    png::png_compress_dyn_kernel<<<nseg, kWave, 0, st>>>(filt, bytes, nseg, slots, (uint16_t*)(base + l.tokens), meta);
+  else
+    png::png_compress_kernel<<<nseg, kWave, 0, st>>>(filt, bytes, nseg, slots, meta);
   png::png_layout_kernel<<<1, 256, 0, st>>>(meta, nseg, bytes, h, w, offs, adler, out, out_len);
   png::png_gather_kernel<<<nseg, 256, 0, st>>>(slots, meta, offs, adler, nseg, out);
-  return check_launch("png_encode_rgb8");
+  return check_launch(name);
+}
+
+extern "C" int dvd_png_encode_rgb8(const uint8_t* img_hwc, int h, int w, uint8_t* out, long cap, unsigned long long* out_len,
+                                   void* scratch, void* stream) {
+  const int rc = png_encode_args("png_encode_rgb8", img_hwc, h, w, out, cap, out_len, scratch);
+  if (rc != DVD_OK) return rc;
+  return png_encode_launch("png_encode_rgb8", img_hwc, h, w, out, out_len, scratch, DVD_PNG_HUFFMAN_FIXED, stream);
+}
+
+extern "C" int dvd_png_encode_rgb8_huff(const uint8_t* img_hwc, int h, int w, uint8_t* out, long cap,
+                                        unsigned long long* out_len, void* scratch, int huffman, void* stream) {
+  DVD_REQUIRE(huffman == DVD_PNG_HUFFMAN_FIXED || huffman == DVD_PNG_HUFFMAN_DYNAMIC,
+              "png_encode_rgb8_huff: huffman %d is neither DVD_PNG_HUFFMAN_FIXED nor DVD_PNG_HUFFMAN_DYNAMIC", huffman);
+  const int rc = png_encode_args("png_encode_rgb8_huff", img_hwc, h, w, out, cap, out_len, scratch);
+  if (rc != DVD_OK) return rc;
+  return png_encode_launch("png_encode_rgb8_huff", img_hwc, h, w, out, out_len, scratch, huffman, stream);
 }

@@ -2,8 +2,11 @@
 // segment compressor, bit writer, Adler-32 folding, chunk layout and CRC-32 tree, with the lanes of a wave and the threads of
 // a workgroup as plain loops.  Plain C++ (no HIP), so it can be built with -fsanitize=address,undefined and run anywhere:
 //     g++ -O1 -g -fsanitize=address,undefined png_host_check.cpp -o png_host_check
-//     png_host_check H W in.rgb out.png        in.rgb = H*W*3 raw bytes
-// It is not part of libdvd_hip.so; tests/test_png_cpu.py builds and runs it and decodes what it writes.
+//     png_host_check H W in.rgb out.png            in.rgb = H*W*3 raw bytes; DVD_PNG_HUFFMAN_FIXED
+//     png_host_check H W in.rgb out.png dynamic    DVD_PNG_HUFFMAN_DYNAMIC: png_compress_dyn_kernel's steps, its 64 lanes a loop
+//     png_host_check --code-lengths LIMIT f0 f1 ...    the lengths build_code_lengths gives the histogram f0 f1 ...
+// It is not part of libdvd_hip.so; tests/test_png_cpu.py and tests/test_png_dyn_cpu.py build and run it and decode what it
+// writes.
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -23,17 +26,86 @@ struct HostOps {
   }
   static void store32(uint32_t* p, uint32_t v) { *p = v; }
   static void store16(uint16_t* p, uint16_t v) { *p = v; }
+  static void store_tok(uint16_t* p, uint16_t v) { *p = v; }
+  static int lane() { return 0; }
+  static int lanes() { return 1; }
+  static void count(uint32_t* p) { ++*p; }
 };
+
+// png_compress_dyn_kernel's steps after the segment is staged.  tok: exactly n entries; st on the heap with the staging
+// dwords as its last member, so that a staging index past them is the sanitizer's to find.
+static int compress_segment_dynamic(const uint8_t* seg, int n, uint16_t* table, uint16_t* tok, DynState& st, uint32_t* out,
+                                    bool first, bool last) {
+  const int kLanes = 64;
+  TokenSink<HostOps> sink{tok, 0};
+  tokenise<HostOps>(seg, n, table, sink);
+  const int m = sink.count;
+  memset(&st, 0, sizeof(st));
+  st.ll_freq[256] = 1;
+  count_tokens<HostOps>(tok, m, st);
+  plan_block(st);
+  BitWriter<HostOps> bw{0, 0, out, 0};
+  put_block_header(bw, st, first);
+  int words = bw.words, cnt = bw.cnt;
+  st.stage[0] = (uint32_t)bw.buf;
+  for (int i0 = 0; i0 < m; i0 += kLanes) {
+    int off = cnt;
+    for (int lane = 0; lane < kLanes && i0 + lane < m; ++lane) {
+      const uint32_t e = tok[i0 + lane];
+      if (e & kDistFlag) continue;
+      int nb = 0;
+      const uint64_t bits = token_bits(st, e, e >= 256 ? (uint32_t)tok[i0 + lane + 1] : 0u, nb);
+      if (nb) {
+        const int w = off >> 5, sh = off & 31;
+        const uint64_t lo = bits << sh;
+        const uint32_t hi = sh ? (uint32_t)(bits >> (64 - sh)) : 0u;
+        st.stage[w] |= (uint32_t)lo;
+        if ((uint32_t)(lo >> 32)) st.stage[w + 1] |= (uint32_t)(lo >> 32);
+        if (hi) st.stage[w + 2] |= hi;
+      }
+      off += nb;
+    }
+    const int full = off >> 5;
+    const uint32_t carry = st.stage[full];
+    for (int k = 0; k < full; ++k) out[words + k] = st.stage[k];
+    for (int k = 0; k <= full; ++k) st.stage[k] = k == 0 ? carry : 0u;
+    words += full;
+    cnt = off & 31;
+  }
+  bw.words = words;
+  bw.cnt = cnt;
+  bw.buf = st.stage[0];
+  bw.put(st.ll_code[256], st.ll_len[256]);
+  return finish_segment(bw, last);
+}
+
+static int code_lengths_mode(int argc, char** argv) {
+  const int limit = atoi(argv[2]), n = argc - 3;
+  if (limit < 1 || limit > 15 || n < 1 || n > 288 || n > (1 << limit)) return 2;
+  std::vector<uint32_t> freq((size_t)n), work(2 * 288);
+  std::vector<uint8_t> len((size_t)n);
+  for (int s = 0; s < n; ++s) {
+    const long v = atol(argv[3 + s]);
+    if (v < 0 || v >= (1L << 23)) return 2;
+    freq[s] = (uint32_t)v;
+  }
+  build_code_lengths(freq.data(), n, limit, len.data(), work.data());
+  for (int s = 0; s < n; ++s) printf(s ? " %d" : "%d", (int)len[s]);
+  printf("\n");
+  return 0;
+}
 
 static void put_be32(uint8_t* p, uint32_t v) {
   p[0] = (uint8_t)(v >> 24); p[1] = (uint8_t)(v >> 16); p[2] = (uint8_t)(v >> 8); p[3] = (uint8_t)v;
 }
 
 int main(int argc, char** argv) {
-  if (argc != 5) {
-    fprintf(stderr, "usage: %s H W in.rgb out.png\n", argv[0]);
+  if (argc >= 4 && !strcmp(argv[1], "--code-lengths")) return code_lengths_mode(argc, argv);
+  if (argc != 5 && !(argc == 6 && !strcmp(argv[5], "dynamic"))) {
+    fprintf(stderr, "usage: %s H W in.rgb out.png [dynamic] | %s --code-lengths LIMIT f0 f1 ...\n", argv[0], argv[0]);
     return 2;
   }
+  const bool dynamic = argc == 6;
   const int h = atoi(argv[1]), w = atoi(argv[2]);
   if (h < 1 || w < 1 || 3L * w + 1 > ((1L << 31) - 1) / h) return 2;
   const long rb = 3L * w, stream = stream_bytes(h, w);
@@ -71,7 +143,14 @@ int main(int argc, char** argv) {
     std::vector<uint16_t> table(kHashSize, (uint16_t)kEmpty);
     // exactly the words a segment of n bytes may take (the device slot is sized for a full segment)
     slots[s].assign((size_t)(seg_data_max(n) + 2 + 2 + 3) / 4, 0xDEADBEEFu);
-    len[s] = (uint32_t)compress_segment<HostOps>(seg.data(), n, table.data(), slots[s].data(), s == 0, s == nseg - 1);
+    if (dynamic) {
+      std::vector<uint16_t> tok((size_t)n);                                   // at most one entry per stream byte
+      std::vector<DynState> st(1);
+      len[s] = (uint32_t)compress_segment_dynamic(seg.data(), n, table.data(), tok.data(), st[0], slots[s].data(), s == 0,
+                                                  s == nseg - 1);
+    } else {
+      len[s] = (uint32_t)compress_segment<HostOps>(seg.data(), n, table.data(), slots[s].data(), s == 0, s == nseg - 1);
+    }
     if ((long)len[s] > seg_data_max(n) + (s == 0 ? 2 : 0) + (s == nseg - 1 ? 2 : 0)) {
       fprintf(stderr, "segment %d: %u bytes above the bound\n", s, len[s]);
       return 1;

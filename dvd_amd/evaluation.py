@@ -198,7 +198,8 @@ def run_evaluation_docunet(settings, logger, val_loader, diffusion, model, pretr
     batched per pass (the reference: 1): ingest + the three pre-stage nets for documents that arrive as images
     (:162-216), the sampler (:247-265), then the tail (:301-306 + visualization_utils.py:75-77) as ONE fused u8 launch per
     batch (documents of one size or of different sizes alike; env.unwarp_mode 'bilinear' | 'bicubic' is its interpolation), and - if env.visualize - `visualize_dewarping` writes the PNG where the reference writes it
-    (env.png_encoder 'pil' | 'hip': PIL on a host copy, or the HIP encoder on the device; env.page_format 'jpeg' writes
+    (env.png_encoder 'pil' | 'hip': PIL on a host copy, or the HIP encoder on the device with env.png_huffman 'fixed' |
+    'dynamic' blocks; env.page_format 'jpeg' writes
     warped_<stem>.jpg with the HIP JPEG encoder instead, at env.jpeg_quality and env.jpeg_subsampling).
     env.image_decoder 'pil' | 'hip' says who decodes the input photograph: the loader (PIL), or - for items that carry the JPEG
     file as `file_bytes` - the HIP decoder on the device (`decode_documents`; the same bytes either way).
@@ -207,7 +208,7 @@ def run_evaluation_docunet(settings, logger, val_loader, diffusion, model, pretr
     (ops.ms_ssim_u8, env.metric_preset): logged per document and as a mean, written to ms_ssim.txt beside the pictures and
     left in settings.ms_ssim as [(path, value)]; a document without a ground truth is logged and skipped.
     Returns [(path, uint8 [H,W,3] device tensor)] (the reference returns None)."""
-    from utils_flow.visualization_utils import page_settings, visualize_dewarping
+    from utils_flow.visualization_utils import page_settings, png_huffman_setting, visualize_dewarping
     env = settings.env
     unwarp_mode = getattr(env, "unwarp_mode", "bilinear")       # the interpolation of the full-resolution tail
     if unwarp_mode not in ("bilinear", "bicubic"):
@@ -215,6 +216,7 @@ def run_evaluation_docunet(settings, logger, val_loader, diffusion, model, pretr
     png_encoder = getattr(env, "png_encoder", "pil")            # who writes the PNG: visualize_dewarping reads it
     if png_encoder not in ("pil", "hip"):
         raise ValueError(f"env.png_encoder must be 'pil' or 'hip', got {png_encoder!r}")
+    png_huffman_setting(env)                                    # 'fixed' | 'dynamic': the 'hip' PNG encoder's blocks
     page_settings(env)                                          # env.page_format, env.jpeg_quality, env.jpeg_subsampling
     image_decoder = getattr(env, "image_decoder", "pil")        # who decodes the input photograph: the loader reads it
     if image_decoder not in ("pil", "hip"):

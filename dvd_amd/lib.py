@@ -84,6 +84,7 @@ SSIM_REPLICATE, SSIM_VALID = 0, 1          # DVD_SSIM_*: border of the 11x11 win
 MSSSIM_DOCUNET, MSSSIM_WANG = 0, 1         # DVD_MSSSIM_*: presets of dvd_msssim_scales
 
 PNG_SEGMENT = 32768   # DVD_PNG_SEGMENT: filtered-stream bytes per IDAT chunk of the PNG encoder
+PNG_HUFFMAN_FIXED, PNG_HUFFMAN_DYNAMIC = 0, 1   # DVD_PNG_HUFFMAN_*: the block type of a segment
 
 JPEG_420, JPEG_444 = 0, 1                  # DVD_JPEG_*: chroma subsampling of the JPEG encoder
 
@@ -106,7 +107,8 @@ RAGGED_CAP = 64   # DVD_RAGGED_CAP: documents per launch of the ragged entry poi
 NON_STATUS = {"dvd_last_error", "dvd_version", "dvd_engine_workspace_bytes", "dvd_engine_tensor_count",
               "dvd_flash_attn_kernel_name", "dvd_gemm_kernel_name", "dvd_convnet_workspace_bytes", "dvd_convnet_weight_floats",
               "dvd_ingest_scratch_bytes", "dvd_ingest_ragged_scratch_bytes", "dvd_resize_gray_scratch_bytes",
-              "dvd_msssim_workspace_bytes", "dvd_png_bound", "dvd_png_scratch_bytes", "dvd_jpeg_bound", "dvd_jpeg_scratch_bytes"}
+              "dvd_msssim_workspace_bytes", "dvd_png_bound", "dvd_png_scratch_bytes", "dvd_png_scratch_bytes_huff", "dvd_jpeg_bound",
+              "dvd_jpeg_scratch_bytes"}
 
 # name -> argtypes; kept in one table so tests can check every symbol of include/dvd_hip.h
 SIGNATURES = {
@@ -174,6 +176,8 @@ SIGNATURES = {
     "dvd_png_bound": [C.c_int, C.c_int],
     "dvd_png_scratch_bytes": [C.c_int, C.c_int],
     "dvd_png_encode_rgb8": [c_void, C.c_int, C.c_int, c_void, C.c_long, c_void, c_void, c_void],
+    "dvd_png_scratch_bytes_huff": [C.c_int, C.c_int, C.c_int],
+    "dvd_png_encode_rgb8_huff": [c_void, C.c_int, C.c_int, c_void, C.c_long, c_void, c_void, C.c_int, c_void],
     "dvd_jpeg_bound": [C.c_int, C.c_int, C.c_int],
     "dvd_jpeg_scratch_bytes": [C.c_int, C.c_int, C.c_int],
     "dvd_jpeg_encode_rgb8": [c_void, C.c_int, C.c_int, C.c_int, C.c_int, c_void, C.c_long, c_void, c_void, c_void],
@@ -200,7 +204,7 @@ SIGNATURES = {
 # entries of SIGNATURES that return something other than a status
 RESTYPES = {"dvd_gemm_kernel_name": C.c_char_p, "dvd_ingest_ragged_scratch_bytes": C.c_long,
             "dvd_resize_gray_scratch_bytes": C.c_long, "dvd_msssim_workspace_bytes": C.c_long,
-            "dvd_png_bound": C.c_long, "dvd_png_scratch_bytes": C.c_long,
+            "dvd_png_bound": C.c_long, "dvd_png_scratch_bytes": C.c_long, "dvd_png_scratch_bytes_huff": C.c_long,
             "dvd_jpeg_bound": C.c_long, "dvd_jpeg_scratch_bytes": C.c_long}
 
 # entry points that exist only in the lab build (benchmarks/lab/dvd_hip_lab.h; loaded through use_library)

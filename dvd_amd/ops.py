@@ -488,14 +488,27 @@ def png_bound(h: int, w: int) -> int:
     return _size_query("dvd_png_bound", h, w)
 
 
-def png_encode(img_hwc_u8: torch.Tensor, scratch: torch.Tensor = None) -> torch.Tensor:
+PNG_HUFFMAN = {"fixed": lib.PNG_HUFFMAN_FIXED, "dynamic": lib.PNG_HUFFMAN_DYNAMIC}
+
+
+def png_huffman_flag(huffman, name="png_encode"):
+    """The library's DVD_PNG_HUFFMAN_* flag of 'fixed' | 'dynamic', or ValueError."""
+    if not isinstance(huffman, str) or huffman not in PNG_HUFFMAN:
+        raise ValueError(f"{name}: huffman must be 'fixed' or 'dynamic', got {huffman!r}")
+    return PNG_HUFFMAN[huffman]
+
+
+def png_encode(img_hwc_u8: torch.Tensor, scratch: torch.Tensor = None, huffman: str = "fixed") -> torch.Tensor:
     """[H,W,3] uint8 on the device -> the complete PNG file as uint8 [nbytes] on the device: four launches, then ONE read-back
-    (the file's length) to trim the worst-case buffer.  The bytes depend on (H, W, pixels) only.  scratch (optional): a
-    uint8 device buffer of at least dvd_png_scratch_bytes(H, W) bytes to reuse between calls; its contents do not matter."""
+    (the file's length) to trim the worst-case buffer.  The bytes depend on (H, W, pixels, huffman) only.  huffman: 'fixed'
+    (one fixed-Huffman block per segment) | 'dynamic' (per segment the smaller of a dynamic and the fixed block: never a longer
+    file).  scratch (optional): a uint8 device buffer of at least dvd_png_scratch_bytes_huff(H, W, huffman) bytes to reuse
+    between calls; its contents do not matter."""
+    flag = png_huffman_flag(huffman)
     h, w = _png_input(img_hwc_u8, "png_encode")
     _chk(img_hwc_u8, torch.uint8, "img")
     dev = img_hwc_u8.device
-    need = _size_query("dvd_png_scratch_bytes", h, w)
+    need = _size_query("dvd_png_scratch_bytes_huff", h, w, flag)
     if scratch is None:
         scratch = torch.empty(need, dtype=torch.uint8, device=dev)
     elif scratch.dtype != torch.uint8 or not scratch.is_contiguous() or scratch.numel() < need or scratch.device != dev:
@@ -503,13 +516,13 @@ def png_encode(img_hwc_u8: torch.Tensor, scratch: torch.Tensor = None) -> torch.
     cap = png_bound(h, w)
     out = torch.empty(cap, dtype=torch.uint8, device=dev)
     nbytes = torch.zeros(1, dtype=torch.int64, device=dev)
-    lib.call("dvd_png_encode_rgb8", ptr(img_hwc_u8), h, w, ptr(out), cap, ptr(nbytes), ptr(scratch), stream_ptr())
+    lib.call("dvd_png_encode_rgb8_huff", ptr(img_hwc_u8), h, w, ptr(out), cap, ptr(nbytes), ptr(scratch), flag, stream_ptr())
     return out[:int(nbytes.item())]
 
 
-def png_encode_to_file(img_hwc_u8: torch.Tensor, path: str) -> int:
+def png_encode_to_file(img_hwc_u8: torch.Tensor, path: str, huffman: str = "fixed") -> int:
     """Encode on the device and write `path`: only the compressed bytes cross to the host.  Returns the file's bytes."""
-    data = png_encode(img_hwc_u8).cpu().numpy()
+    data = png_encode(img_hwc_u8, huffman=huffman).cpu().numpy()
     with open(path, "wb") as f:
         f.write(data.tobytes())
     return int(data.size)

@@ -492,8 +492,23 @@ int dvd_msssim_scales(const float* x, const float* y, int n, int h, int w, int p
  *   The zlib stream is 78 01, the segments, the final empty fixed block 03 00 and the big-endian Adler-32 of the filtered
  *   stream (per-segment partials folded exactly mod 65521).  IDAT s holds segment s; the first also the two header bytes,
  *   the last also 03 00 and the Adler-32.  Each IDAT's CRC-32 covers that chunk only.
+ * DVD_PNG_HUFFMAN_DYNAMIC changes the segment's block alone; filter choice, segmentation, the LZ77 tokens and the rest of
+ * the container are the above.  Per segment: the histograms of the 286 literal/length symbols (one end-of-block included)
+ * and the 30 distance symbols; for each a prefix code limited to 15 bits (lengths by Huffman on the symbols sorted by
+ * (frequency, symbol); if the deepest leaf is beyond the limit, depths are clamped, the rarest symbols of the greatest depth
+ * below the limit go down until the Kraft sum is at most 1, then symbols from the most frequent to the rarest come up one
+ * level per pass while the gain fits, so the code is complete - DESIGN.md 4.4), codes canonical (RFC 1951 3.2.2).  No match
+ * in the segment: HDIST = 1 with the single length 0; one used distance symbol: length 1.  Header: HLIT / HDIST trimmed of
+ * trailing zeros (at least 257 / 1); the concatenated lengths run-length coded greedily (a zero run: 18s of up to 138, one 17
+ * for 3..10, single zeros; another length: once, 16s of up to 6, single lengths); their code limited to 7 bits, a second
+ * symbol given length 1 if only one is used; HCLEN trimmed in the permuted order (at least 4).  The exact bits of the dynamic
+ * block (3 + header + tokens + end-of-block) and of the fixed block are computed from the histograms, and the dynamic block
+ * is written only if it is strictly smaller: a segment, and so a file, is never longer than DVD_PNG_HUFFMAN_FIXED's, and
+ * dvd_png_bound holds for both.
  * ---------------------------------------------------------------------------------------- */
 #define DVD_PNG_SEGMENT 32768
+#define DVD_PNG_HUFFMAN_FIXED 0
+#define DVD_PNG_HUFFMAN_DYNAMIC 1
 /* Worst-case file bytes and scratch bytes for an h x w image; host-only.  A negative DVD_E_* value for a bad shape
  * (h < 1, w < 1 or h * (3w + 1) >= 2^31). */
 long dvd_png_bound(int h, int w);
@@ -504,6 +519,13 @@ long dvd_png_scratch_bytes(int h, int w);
  * do not matter.  Four launches on `stream`, no synchronisation, no read-back. */
 int dvd_png_encode_rgb8(const uint8_t* img_hwc, int h, int w, uint8_t* out, long cap, unsigned long long* out_len,
                         void* scratch, void* stream);
+/* The same with the block type chosen: huffman = DVD_PNG_HUFFMAN_FIXED is dvd_png_encode_rgb8 byte for byte,
+ * DVD_PNG_HUFFMAN_DYNAMIC writes per segment the smaller of a dynamic and the fixed block; any other value is DVD_E_ARG,
+ * checked before anything is launched.  scratch: dvd_png_scratch_bytes_huff(h, w, huffman) bytes (FIXED: what
+ * dvd_png_scratch_bytes returns; DYNAMIC: 2 more bytes per stream byte for the tokens). */
+long dvd_png_scratch_bytes_huff(int h, int w, int huffman);
+int dvd_png_encode_rgb8_huff(const uint8_t* img_hwc, int h, int w, uint8_t* out, long cap, unsigned long long* out_len,
+                             void* scratch, int huffman, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Baseline JPEG of a dewarped page, encoded where the unwarp tail leaves it.  The file is a pure function of (h, w, pixels,

@@ -13,7 +13,8 @@ produced from the COARSE flow - bit-identical to the long way (tests/test_gpu_op
 
 `settings.env.png_encoder` chooses who writes the PNG: 'pil' (default, the reference's Image.save on a host copy of the page) or
 'hip' (`dvd_amd.ops.png_encode_to_file`: filtered and compressed where the page lies, only the file crosses to the host - the
-same pixels in a file of other bytes).
+same pixels in a file of other bytes).  With 'hip', `settings.env.png_huffman` = 'fixed' (default) | 'dynamic' chooses
+the encoder's deflate blocks: 'dynamic' writes per segment the smaller of a dynamic-Huffman and the fixed block.
 
 `settings.env.page_format = 'jpeg'` (default 'png': all of the above, unchanged) writes `warped_<stem>.jpg` instead: baseline
 JFIF at `env.jpeg_quality` (1..100, default 90) and `env.jpeg_subsampling` ('420' default | '444'), encoded on the device by
@@ -29,6 +30,7 @@ from datasets.utils.warping import register_model2
 
 reg_model_bilin = register_model2((512, 512), "bilinear")
 PNG_ENCODERS = ("pil", "hip")
+PNG_HUFFMAN = ("fixed", "dynamic")
 PAGE_FORMATS = ("png", "jpeg")
 JPEG_SUBSAMPLINGS = ("420", "444")
 
@@ -47,6 +49,14 @@ def page_settings(env):
     return fmt, int(quality), subsampling
 
 
+def png_huffman_setting(env):
+    """env.png_huffman, checked: ValueError names the setting."""
+    huffman = getattr(env, "png_huffman", "fixed")
+    if not isinstance(huffman, str) or huffman not in PNG_HUFFMAN:
+        raise ValueError(f"env.png_huffman must be 'fixed' or 'dynamic', got {huffman!r}")
+    return huffman
+
+
 def _stem(data_path):
     name = data_path[0] if isinstance(data_path, (list, tuple)) else data_path
     return name.split("/")[-1][:-4]              # the reference's rule (:78): basename minus a 4-character extension
@@ -58,6 +68,7 @@ def visualize_dewarping(settings, sample, data, i, source_vis, data_path, ref_fl
     encoder = getattr(settings.env, "png_encoder", "pil")
     if encoder not in PNG_ENCODERS:
         raise ValueError(f"env.png_encoder must be 'pil' or 'hip', got {encoder!r}")
+    huffman = png_huffman_setting(settings.env)
     page_format, quality, subsampling = page_settings(settings.env)
     if page_format == "jpeg":
         encoder = "jpeg"                             # the device route below; png_encoder is not consulted
@@ -78,7 +89,7 @@ def visualize_dewarping(settings, sample, data, i, source_vis, data_path, ref_fl
         if encoder == "jpeg":
             ops.jpeg_encode_to_file(warped_u8, f"{out_dir}/dewarped_pred/warped_{_stem(data_path)}.jpg", quality, subsampling)
         else:
-            ops.png_encode_to_file(warped_u8, f"{out_dir}/dewarped_pred/warped_{_stem(data_path)}.png")
+            ops.png_encode_to_file(warped_u8, f"{out_dir}/dewarped_pred/warped_{_stem(data_path)}.png", huffman)
     elif warped_u8 is None:
         warped = reg_model_bilin([source_vis.to(sample.device).float(), sample])
         warped_u8 = warped[0].permute(1, 2, 0).detach().cpu().numpy().astype(np.uint8)
