@@ -56,6 +56,9 @@ _DEFAULTS = {
     # (ops.ms_ssim_u8; "" = no scoring, nothing else changes); metric_preset: 'docunet' | 'wang' 
     "gt_dir": "",
     "metric_preset": "docunet",
+    # which metrics gt_dir scores: 'ms_ssim' | 'ms_ssim,ld' | 'ld'.  'ld' adds the local distortion, the mean length of a dense
+    # SIFT-flow field from the scan to the page (ops.ld_u8): logged, written to ld.txt, left in settings.ld
+    "gt_metrics": "ms_ssim",
     # who writes dewarped_pred/warped_<stem>.png: 'pil' (the reference: copy the page to the host, Image.save) | 'hip'
     # (ops.png_encode on the device, only the compressed file crosses to the host; the same pixels, other bytes - DESIGN.md 4.4)
     "png_encoder": "pil",

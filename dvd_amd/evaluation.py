@@ -178,17 +178,31 @@ def find_gt(gt_dir, path):
     return None
 
 
-def _score_against_gt(settings, logger, path, out, device):
-    """MS-SSIM of one dewarped page (uint8 [H,W,3] on the device) against its ground-truth scan, if there is one."""
+GT_METRICS = ("ms_ssim", "ld")
+
+
+def parse_gt_metrics(value):
+    """env.gt_metrics, a comma-separated list of GT_METRICS names ('ms_ssim' | 'ms_ssim,ld' | 'ld') -> the names, in the order
+    of GT_METRICS.  Anything else is a ValueError."""
+    names = [n.strip() for n in value.split(",")] if isinstance(value, str) else None
+    if not names or any(n not in GT_METRICS for n in names) or len(set(names)) != len(names):
+        raise ValueError(f"env.gt_metrics must be a comma-separated list of {GT_METRICS} without repeats, got {value!r}")
+    return tuple(m for m in GT_METRICS if m in names)
+
+
+def _score_against_gt(settings, logger, path, out, device, metrics=("ms_ssim",)):
+    """The metrics of one dewarped page (uint8 [H,W,3] on the device) against its ground-truth scan, if there is one: MS-SSIM
+    and / or LD, on planes prepared once."""
     from PIL import Image
     gt_file = find_gt(settings.env.gt_dir, path)
     if gt_file is None:
-        logger.info(f"{path} ms_ssim skipped: no ground truth in {settings.env.gt_dir}")
+        logger.info(f"{path} {','.join(metrics)} skipped: no ground truth in {settings.env.gt_dir}")
         return
     gt = th.from_numpy(np.ascontiguousarray(np.asarray(Image.open(gt_file).convert("RGB")))).to(device)
-    value = ops.ms_ssim_u8(out.contiguous(), gt, preset=getattr(settings.env, "metric_preset", "docunet"))
-    logger.info(f"{path} ms_ssim {value:.6f}")
-    settings.ms_ssim.append((path, value))
+    values = ops.gt_metrics_u8(out.contiguous(), gt, metrics, preset=getattr(settings.env, "metric_preset", "docunet"))
+    for name in metrics:
+        logger.info(f"{path} {name} {values[name]:.6f}")
+        getattr(settings, name).append((path, values[name]))
 
 
 def run_evaluation_docunet(settings, logger, val_loader, diffusion, model, pretrained_dewarp_model,
@@ -207,6 +221,8 @@ def run_evaluation_docunet(settings, logger, val_loader, diffusion, model, pretr
     With env.gt_dir set, every dewarped page is scored against `<gt_dir>/<stem>.png` (`gt_candidates`) with MS-SSIM
     (ops.ms_ssim_u8, env.metric_preset): logged per document and as a mean, written to ms_ssim.txt beside the pictures and
     left in settings.ms_ssim as [(path, value)]; a document without a ground truth is logged and skipped.
+    env.gt_metrics 'ms_ssim' | 'ms_ssim,ld' | 'ld' chooses the metrics: 'ld' adds the local distortion (ops.ld_u8: the mean
+    SIFT-flow length from the scan to the page) in the same way - ld.txt and settings.ld.
     Returns [(path, uint8 [H,W,3] device tensor)] (the reference returns None)."""
     from utils_flow.visualization_utils import page_settings, png_huffman_setting, visualize_dewarping
     env = settings.env
@@ -221,6 +237,7 @@ def run_evaluation_docunet(settings, logger, val_loader, diffusion, model, pretr
     image_decoder = getattr(env, "image_decoder", "pil")        # who decodes the input photograph: the loader reads it
     if image_decoder not in ("pil", "hip"):
         raise ValueError(f"env.image_decoder must be 'pil' or 'hip', got {image_decoder!r}")
+    gt_metrics = parse_gt_metrics(getattr(env, "gt_metrics", "ms_ssim"))       # what env.gt_dir scores
     device = next(model.parameters()).device
     nets = (pretrained_dewarp_model, pretrained_seg_model, pretrained_line_seg_model)
     prestage_models = None if all(m is None for m in nets) else nets
@@ -230,7 +247,8 @@ def run_evaluation_docunet(settings, logger, val_loader, diffusion, model, pretr
     gt_dir = getattr(env, "gt_dir", "")
     if gt_dir:
         ops._ssim_preset(getattr(env, "metric_preset", "docunet"), "env.metric_preset")
-        settings.ms_ssim = []
+        for name in gt_metrics:
+            setattr(settings, name, [])
 
     def flush():
         if not batch:
@@ -288,7 +306,7 @@ def run_evaluation_docunet(settings, logger, val_loader, diffusion, model, pretr
                 name = d["path"] if os.path.splitext(d["path"])[1] else d["path"] + ".png"
                 visualize_dewarping(settings, None, d, len(results) - 1, None, [name], warped_u8=out)
             if gt_dir:
-                _score_against_gt(settings, logger, d["path"], out, device)
+                _score_against_gt(settings, logger, d["path"], out, device, gt_metrics)
         batch.clear()
 
     for item in val_loader:
@@ -300,13 +318,14 @@ def run_evaluation_docunet(settings, logger, val_loader, diffusion, model, pretr
     if times:
         print(len(times))
         print("Elapsed time:{:.2f} avg_second ".format(sum(times) / len(times)))
-    if gt_dir:
-        with open(f"vis_hp/{env.eval_dataset_name}/{settings.name}/ms_ssim.txt", "w") as f:
-            for path, value in settings.ms_ssim:
+    for name in gt_metrics if gt_dir else ():
+        scores = getattr(settings, name)
+        with open(f"vis_hp/{env.eval_dataset_name}/{settings.name}/{name}.txt", "w") as f:
+            for path, value in scores:
                 f.write(f"{path} {value:.6f}\n")
-        if settings.ms_ssim:
-            mean = sum(v for _, v in settings.ms_ssim) / len(settings.ms_ssim)
-            logger.info(f"mean ms_ssim {mean:.6f} over {len(settings.ms_ssim)} of {len(results)} documents")
+        if scores:
+            mean = sum(v for _, v in scores) / len(scores)
+            logger.info(f"mean {name} {mean:.6f} over {len(scores)} of {len(results)} documents")
         else:
-            logger.info(f"mean ms_ssim: no document of {len(results)} has a ground truth in {gt_dir}")
+            logger.info(f"mean {name}: no document of {len(results)} has a ground truth in {gt_dir}")
     return results

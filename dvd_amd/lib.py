@@ -102,13 +102,21 @@ JPEG_DECODE_CODES = {-20: "HEADER", -21: "PROGRESSIVE", -22: "EXTENDED", -23: "L
                      -33: "ORIENTATION", -34: "NOSYNC", -35: "DATA"}
 JPEGDEC_SUBSEQ = 128   # DVD_JPEGDEC_SUBSEQ: bytes of the scan per lane of the entropy decoder
 
+class SflowParams(C.Structure):
+    """dvd_sflow_params: the parameters of the SIFT-flow chain, ten ints in this order."""
+    _fields_ = [(name, C.c_int) for name in ("levels", "w_top", "w", "iters_top", "iters", "alpha", "d", "gamma", "T", "eps")]
+
+
+SFLOW_DEFAULTS = dict(levels=4, w_top=10, w=2, iters_top=60, iters=30, alpha=510, d=10200, gamma=1, T=8160, eps=1 << 17)
+SFLOW_MIN_TOP = 12    # DVD_SFLOW_MIN_TOP: least side of the top pyramid level
+
 RAGGED_CAP = 64   # DVD_RAGGED_CAP: documents per launch of the ragged entry points (larger batches are cut by the library)
 
 NON_STATUS = {"dvd_last_error", "dvd_version", "dvd_engine_workspace_bytes", "dvd_engine_tensor_count",
               "dvd_flash_attn_kernel_name", "dvd_gemm_kernel_name", "dvd_convnet_workspace_bytes", "dvd_convnet_weight_floats",
               "dvd_ingest_scratch_bytes", "dvd_ingest_ragged_scratch_bytes", "dvd_resize_gray_scratch_bytes",
               "dvd_msssim_workspace_bytes", "dvd_png_bound", "dvd_png_scratch_bytes", "dvd_png_scratch_bytes_huff", "dvd_jpeg_bound",
-              "dvd_jpeg_scratch_bytes"}
+              "dvd_jpeg_scratch_bytes", "dvd_sflow_level_workspace_bytes", "dvd_sflow_workspace_bytes"}
 
 # name -> argtypes; kept in one table so tests can check every symbol of include/dvd_hip.h
 SIGNATURES = {
@@ -173,6 +181,13 @@ SIGNATURES = {
     "dvd_reduce2_pair": [c_void, c_void, c_void, c_void, C.c_int, C.c_int, C.c_int, C.c_int, c_void],
     "dvd_msssim_workspace_bytes": [C.c_int, C.c_int, C.c_int],
     "dvd_msssim_scales": [c_void, c_void, C.c_int, C.c_int, C.c_int, C.c_int, c_void, c_void, c_void],
+    "dvd_dsift_u8": [c_void, C.c_int, C.c_int, C.c_int, C.c_int, c_void, c_void],
+    "dvd_sflow_cost": [c_void, c_void, c_void, C.c_int, C.c_int, C.c_int, C.POINTER(SflowParams), c_void, c_void],
+    "dvd_sflow_level_workspace_bytes": [C.c_int, C.c_int, C.c_int],
+    "dvd_sflow_level": [c_void, c_void, c_void, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(SflowParams), c_void, c_void, c_void,
+                        c_void],
+    "dvd_sflow_workspace_bytes": [C.c_int, C.c_int, C.POINTER(SflowParams)],
+    "dvd_sflow": [c_void, c_void, C.c_int, C.c_int, C.c_int, C.POINTER(SflowParams), c_void, c_void, c_void, c_void],
     "dvd_png_bound": [C.c_int, C.c_int],
     "dvd_png_scratch_bytes": [C.c_int, C.c_int],
     "dvd_png_encode_rgb8": [c_void, C.c_int, C.c_int, c_void, C.c_long, c_void, c_void, c_void],
@@ -204,6 +219,7 @@ SIGNATURES = {
 # entries of SIGNATURES that return something other than a status
 RESTYPES = {"dvd_gemm_kernel_name": C.c_char_p, "dvd_ingest_ragged_scratch_bytes": C.c_long,
             "dvd_resize_gray_scratch_bytes": C.c_long, "dvd_msssim_workspace_bytes": C.c_long,
+            "dvd_sflow_level_workspace_bytes": C.c_long, "dvd_sflow_workspace_bytes": C.c_long,
             "dvd_png_bound": C.c_long, "dvd_png_scratch_bytes": C.c_long, "dvd_png_scratch_bytes_huff": C.c_long,
             "dvd_jpeg_bound": C.c_long, "dvd_jpeg_scratch_bytes": C.c_long}
 

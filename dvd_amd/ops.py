@@ -455,18 +455,7 @@ def ms_ssim_u8(pred_hwc_u8: torch.Tensor, gt_hwc_u8: torch.Tensor, preset: str =
     """The whole protocol for one pair of uint8 RGB images [H,W,3] of any two sizes: the ground truth is resized to `area`
     pixels, the prediction to the ground truth's resized size, both go to gray, then MS-SSIM."""
     _ssim_preset(preset, "ms_ssim_u8")
-    for name, t in (("pred", pred_hwc_u8), ("gt", gt_hwc_u8)):
-        if t.dim() != 3 or t.shape[2] != 3 or min(t.shape[:2]) < 1:
-            raise ValueError(f"ms_ssim_u8: {name}: expected [H,W,3], got {tuple(t.shape)}")
-    if area < 1:
-        raise ValueError(f"ms_ssim_u8: area must be positive, got {area}")
-    th_, tw_ = msssim_target_size(gt_hwc_u8.shape[0], gt_hwc_u8.shape[1], area)
-    if min(th_, tw_) < MSSSIM_MIN_SIDE:
-        raise ValueError(f"ms_ssim_u8: the working size {th_}x{tw_} has a side below {MSSSIM_MIN_SIDE}")
-    _chk(pred_hwc_u8, torch.uint8, "pred")
-    _chk(gt_hwc_u8, torch.uint8, "gt")
-    x = resize_gray_u8(pred_hwc_u8[None], th_, tw_)
-    y = resize_gray_u8(gt_hwc_u8[None], th_, tw_)
+    x, y = _metric_planes("ms_ssim_u8", pred_hwc_u8, gt_hwc_u8, area, MSSSIM_MIN_SIDE)
     return float(ms_ssim(x, y, preset)[0])
 
 
@@ -712,3 +701,182 @@ def decode_image(path_or_bytes, device=None, max_iters: int = None, log=None):
         log(f"{what}: decoded by PIL, not on the device: {e}")
     pixels = torch.from_numpy(pil_decode_rgb8(data))
     return pixels.to(torch.device("cuda") if device is None else device), "pil"
+
+
+# ---- local distortion: dense SIFT + SIFT-flow (dvd_amd/csrc/sflow.hip; definition: DESIGN.md 4.7) --------------------------
+SFLOW_DEFAULTS = dict(lib.SFLOW_DEFAULTS)
+SFLOW_MAX_SIDE = 8192
+
+
+def sflow_top_size(h: int, w: int, levels: int):
+    """(rows, columns) of the top pyramid level: ceil(n / 2) per axis and level."""
+    for _ in range(levels - 1):
+        h, w = (h + 1) // 2, (w + 1) // 2
+    return h, w
+
+
+def sflow_params(name: str = "sift_flow", **params) -> lib.SflowParams:
+    """The chain's parameters (defaults: SFLOW_DEFAULTS) as the C struct; every range is checked here, before anything is
+    allocated or launched, and again by the library."""
+    unknown = sorted(set(params) - set(SFLOW_DEFAULTS))
+    if unknown:
+        raise ValueError(f"{name}: unknown parameter(s) {unknown}; known: {sorted(SFLOW_DEFAULTS)}")
+    p = dict(SFLOW_DEFAULTS, **params)
+    for key, value in p.items():
+        if isinstance(value, bool) or not isinstance(value, (int, np.integer)):
+            raise ValueError(f"{name}: {key} must be an integer, got {value!r}")
+    if not 1 <= p["levels"] <= 6:
+        raise ValueError(f"{name}: levels must be 1..6, got {p['levels']}")
+    for key in ("w_top", "w"):
+        if not 1 <= p[key] <= 10:
+            raise ValueError(f"{name}: {key} must be 1..10, got {p[key]}")
+    for key in ("iters_top", "iters"):
+        if not 1 <= p[key] <= 1000:
+            raise ValueError(f"{name}: {key} must be 1..1000, got {p[key]}")
+    if not 0 <= p["alpha"] <= 65535:
+        raise ValueError(f"{name}: alpha must be 0..65535, got {p['alpha']}")
+    if not 0 <= 2 * p["d"] <= 65535:
+        raise ValueError(f"{name}: d must keep a message in 16 bits (0 <= 2 d <= 65535), got {p['d']}")
+    bound = p["w_top"]
+    for _ in range(p["levels"] - 1):
+        bound = 2 * bound + p["w"]
+    if p["gamma"] < 0 or p["T"] < 0 or p["T"] + 2 * p["gamma"] * bound > 65535:
+        raise ValueError(f"{name}: T and gamma must keep a cost in 16 bits (T + gamma |f|_1 <= 65535 with |f|_1 <= "
+                         f"{2 * bound}), got T {p['T']}, gamma {p['gamma']}")
+    if not 1 <= p["eps"] <= 1 << 30:
+        raise ValueError(f"{name}: eps must be 1..2^30, got {p['eps']}")
+    return lib.SflowParams(**{k: int(v) for k, v in p.items()})
+
+
+def _sflow_check_size(name, h, w, pr):
+    th_, tw_ = sflow_top_size(h, w, pr.levels)
+    if min(th_, tw_) < lib.SFLOW_MIN_TOP or max(h, w) > SFLOW_MAX_SIDE:
+        raise ValueError(f"{name}: {h}x{w} with {pr.levels} levels has a top level of {th_}x{tw_}: each side must be >= "
+                         f"{lib.SFLOW_MIN_TOP} (and no side above {SFLOW_MAX_SIDE})")
+
+
+def dense_sift_u8(gray: torch.Tensor, eps: int = SFLOW_DEFAULTS["eps"]) -> torch.Tensor:
+    """Gray planes [N,H,W] f32 of integer values 0..255 -> dense descriptors [N,H,W,128] uint8."""
+    if gray.dim() != 3 or gray.shape[0] < 1 or min(gray.shape[1:]) < 1 or max(gray.shape[1:]) > SFLOW_MAX_SIDE:
+        raise ValueError(f"dense_sift_u8: expected [N,H,W] with N >= 1 and sides 1..{SFLOW_MAX_SIDE}, got {tuple(gray.shape)}")
+    if isinstance(eps, bool) or not isinstance(eps, (int, np.integer)) or not 1 <= eps <= 1 << 30:
+        raise ValueError(f"dense_sift_u8: eps must be an integer 1..2^30, got {eps!r}")
+    _chk(gray, torch.float32, "gray")
+    n, h, w = gray.shape
+    out = torch.empty((n, h, w, 128), dtype=torch.uint8, device=gray.device)
+    lib.call("dvd_dsift_u8", ptr(gray), n, h, w, int(eps), ptr(out), stream_ptr())
+    return out
+
+
+def _sflow_level_args(name, desc_a, desc_b, off, win):
+    if desc_a.dim() != 3 or desc_a.shape[2] != 128 or tuple(desc_a.shape) != tuple(desc_b.shape):
+        raise ValueError(f"{name}: expected two [H,W,128] descriptor planes of one shape, got {tuple(desc_a.shape)} and "
+                         f"{tuple(desc_b.shape)}")
+    h, w = desc_a.shape[:2]
+    if tuple(off.shape) != (2, h, w):
+        raise ValueError(f"{name}: off must be [2,{h},{w}], got {tuple(off.shape)}")
+    if isinstance(win, bool) or not isinstance(win, (int, np.integer)) or not 1 <= win <= 10:
+        raise ValueError(f"{name}: win must be an integer 1..10, got {win!r}")
+    _chk(desc_a, torch.uint8, "desc_a")
+    _chk(desc_b, torch.uint8, "desc_b")
+    _chk(off, torch.int16, "off")
+    return h, w
+
+
+def sflow_cost(desc_a: torch.Tensor, desc_b: torch.Tensor, off: torch.Tensor, win: int, **params) -> torch.Tensor:
+    """The cost volume of one level of one document: descriptors [H,W,128] uint8, window centres off [2,H,W] int16 ->
+    [H,W,(2 win + 1)^2] as int32 values 0..65535 (the kernel's u16)."""
+    pr = sflow_params("sflow_cost", **params)
+    h, w = _sflow_level_args("sflow_cost", desc_a, desc_b, off, win)
+    cost = torch.empty((h, w, (2 * win + 1) ** 2), dtype=torch.int16, device=desc_a.device)
+    lib.call("dvd_sflow_cost", ptr(desc_a), ptr(desc_b), ptr(off), h, w, int(win), C.byref(pr), ptr(cost), stream_ptr())
+    return cost.to(torch.int32) & 0xFFFF
+
+
+def sflow_level(desc_a: torch.Tensor, desc_b: torch.Tensor, off: torch.Tensor, win: int, iters: int, **params) -> torch.Tensor:
+    """One level of one document: cost volume, `iters` BP iterations, argmin -> the absolute flow [2,H,W] int16."""
+    pr = sflow_params("sflow_level", **params)
+    if isinstance(iters, bool) or not isinstance(iters, (int, np.integer)) or not 1 <= iters <= 1000:
+        raise ValueError(f"sflow_level: iters must be an integer 1..1000, got {iters!r}")
+    h, w = _sflow_level_args("sflow_level", desc_a, desc_b, off, win)
+    flow = torch.empty((2, h, w), dtype=torch.int16, device=desc_a.device)
+    work = torch.empty(_size_query("dvd_sflow_level_workspace_bytes", h, w, int(win)), dtype=torch.uint8, device=desc_a.device)
+    lib.call("dvd_sflow_level", ptr(desc_a), ptr(desc_b), ptr(off), h, w, int(win), int(iters), C.byref(pr), ptr(work),
+             ptr(flow), None, stream_ptr())
+    return flow
+
+
+def sift_flow(a: torch.Tensor, b: torch.Tensor, **params):
+    """SIFT-flow from the gray planes a (the scan) to b (the prediction), [N,H,W] f32 of integer values 0..255 ->
+    (flow int16 [N,2,H,W], ld float64 [N]: the mean flow length of every pair).  The documents of a batch follow each other
+    in one document's workspace."""
+    pr = sflow_params("sift_flow", **params)
+    if a.dim() != 3 or a.shape[0] < 1 or tuple(a.shape) != tuple(b.shape):
+        raise ValueError(f"sift_flow: expected two [N,H,W] planes of one shape, got {tuple(a.shape)} and {tuple(b.shape)}")
+    n, h, w = a.shape
+    _sflow_check_size("sift_flow", h, w, pr)
+    _chk(a, torch.float32, "a")
+    _chk(b, torch.float32, "b")
+    flow = torch.empty((n, 2, h, w), dtype=torch.int16, device=a.device)
+    ld = torch.empty((n,), dtype=torch.float64, device=a.device)
+    work = torch.empty(_size_query("dvd_sflow_workspace_bytes", h, w, C.byref(pr)), dtype=torch.uint8, device=a.device)
+    lib.call("dvd_sflow", ptr(a), ptr(b), n, h, w, C.byref(pr), ptr(work), ptr(flow), ptr(ld), stream_ptr())
+    return flow, ld.cpu().numpy()
+
+
+def local_distortion(a: torch.Tensor, b: torch.Tensor, **params) -> np.ndarray:
+    """LD of N pairs of gray planes [N,H,W] -> [N] float64."""
+    return sift_flow(a, b, **params)[1]
+
+
+def _metric_size(name, pred_hwc_u8, gt_hwc_u8, area, min_side):
+    """The working size of the benchmark's preparation, (rows, columns): the ground truth resized to `area` pixels."""
+    for who, t in (("pred", pred_hwc_u8), ("gt", gt_hwc_u8)):
+        if t.dim() != 3 or t.shape[2] != 3 or min(t.shape[:2]) < 1:
+            raise ValueError(f"{name}: {who}: expected [H,W,3], got {tuple(t.shape)}")
+    if area < 1:
+        raise ValueError(f"{name}: area must be positive, got {area}")
+    th_, tw_ = msssim_target_size(gt_hwc_u8.shape[0], gt_hwc_u8.shape[1], area)
+    if min(th_, tw_) < min_side:
+        raise ValueError(f"{name}: the working size {th_}x{tw_} has a side below {min_side}")
+    return th_, tw_
+
+
+def _metric_planes(name, pred_hwc_u8, gt_hwc_u8, area, min_side, pr=None):
+    """The benchmark's preparation, shared by MS-SSIM and LD: the ground truth resized to `area` pixels, the prediction to the
+    ground truth's resized size, both to gray -> (pred plane, gt plane), each [1,h,w] f32.  pr: the SIFT-flow parameters the
+    working size must suit."""
+    th_, tw_ = _metric_size(name, pred_hwc_u8, gt_hwc_u8, area, min_side)
+    if pr is not None:
+        _sflow_check_size(name, th_, tw_, pr)
+    _chk(pred_hwc_u8, torch.uint8, "pred")
+    _chk(gt_hwc_u8, torch.uint8, "gt")
+    return resize_gray_u8(pred_hwc_u8[None], th_, tw_), resize_gray_u8(gt_hwc_u8[None], th_, tw_)
+
+
+def ld_u8(pred_hwc_u8: torch.Tensor, gt_hwc_u8: torch.Tensor, area: int = MSSSIM_AREA, **params) -> float:
+    """LD for one pair of uint8 RGB images [H,W,3] of any two sizes, prepared like ms_ssim_u8: the flow runs from the
+    ground-truth scan to the prediction."""
+    pr = sflow_params("ld_u8", **params)
+    x, y = _metric_planes("ld_u8", pred_hwc_u8, gt_hwc_u8, area, 1, pr)
+    return float(local_distortion(y, x, **params)[0])
+
+
+def gt_metrics_u8(pred_hwc_u8: torch.Tensor, gt_hwc_u8: torch.Tensor, metrics, preset: str = "docunet",
+                  area: int = MSSSIM_AREA, **params) -> dict:
+    """The metrics named in `metrics` ('ms_ssim', 'ld') for one pair of uint8 RGB images, on planes prepared once:
+    {name: float}.  Each value is what ms_ssim_u8 / ld_u8 gives alone."""
+    metrics = tuple(metrics)
+    unknown = [m for m in metrics if m not in ("ms_ssim", "ld")]
+    if unknown or not metrics:
+        raise ValueError(f"gt_metrics_u8: metrics must name 'ms_ssim' and / or 'ld', got {metrics!r}")
+    _ssim_preset(preset, "gt_metrics_u8")
+    pr = sflow_params("gt_metrics_u8", **params)
+    x, y = _metric_planes("gt_metrics_u8", pred_hwc_u8, gt_hwc_u8, area, MSSSIM_MIN_SIDE if "ms_ssim" in metrics else 1,
+                          pr if "ld" in metrics else None)
+    out = {}
+    if "ms_ssim" in metrics:
+        out["ms_ssim"] = float(ms_ssim(x, y, preset)[0])
+    if "ld" in metrics:
+        out["ld"] = float(local_distortion(y, x, **params)[0])
+    return out

@@ -603,6 +603,52 @@ int dvd_jpegdec_probe(const uint8_t* file_host, long n, dvd_jpegdec_info* info);
 int dvd_jpeg_decode_rgb8(const uint8_t* file_host, const uint8_t* file_dev, long n, uint8_t* out_hwc, long cap,
                          int max_iters, int* iters_out, void* scratch, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Local distortion (LD) of the evaluation tail: the mean length of a dense SIFT-flow field from the flat ground-truth scan
+ * A to the dewarped page B, on the device where both planes already lie.  The reference leaves it to offline MATLAB and
+ * Ce Liu's mex code; the definition is this project's own (integer statement: tests/sflow_model.py), written
+ * in integers throughout, and parity with the MATLAB/mex pipeline is UNPINNED.  No kernel uses an atomic: the same inputs
+ * give the same bits on every launch, and document d of a batch gets the bits it gets alone.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct dvd_sflow_params {
+  int levels;     /* pyramid levels, 1..6 (default 4) */
+  int w_top;      /* half window of the top level, 1..10 (10) */
+  int w;          /* half window of the levels below it, 1..10 (2) */
+  int iters_top;  /* BP iterations on the top level, 1..1000 (60) */
+  int iters;      /* BP iterations below it, 1..1000 (30) */
+  int alpha;      /* slope of the smoothness term, 0..65535 (510) */
+  int d;          /* its truncation per component; messages lie in 0..2d, so 2d <= 65535 (10200) */
+  int gamma;      /* weight of |f|_1 in the data term, >= 0 (1) */
+  int T;          /* truncation of the 128-byte L1 distance; T + gamma * (largest |f|_1) <= 65535 (8160) */
+  int eps;        /* added to the descriptor norm, 1..2^30 (131072) */
+} dvd_sflow_params;
+#define DVD_SFLOW_MIN_TOP 12 /* least side of the top pyramid level: one 12 x 12 descriptor patch */
+/* gray [n,h,w] f32 planes of integer values 0..255 -> out [n,h,w,128] u8 (16-byte aligned): central differences with clamped
+ * indices, eight half-rectified orientation responses in units of 1/1024, 3 x 3 cell sums, the 4 x 4 cells at offsets
+ * 3i - 5 (clamped), n = floor(sqrt(sum h^2)) exactly, bytes min(255, 512 h / (n + eps)).  Each side 1..8192. */
+int dvd_dsift_u8(const float* gray, int n, int h, int w, int eps, uint8_t* out, void* stream);
+/* One document, one level.  desc_a, desc_b [h,w,128] u8 (16-byte aligned), off [2,h,w] int16 (window centres u then v),
+ * labels (lu, lv) in [-win, win]^2 at index (lv + win)(2 win + 1) + (lu + win):
+ * cost [h,w,L] u16 = (q inside ? min(T, L1(desc_a(p), desc_b(q))) : T) + gamma (|f_u| + |f_v|), f = off(p) + l, q = p + f. */
+int dvd_sflow_cost(const uint8_t* desc_a, const uint8_t* desc_b, const int16_t* off, int h, int w, int win,
+                   const dvd_sflow_params* params, uint16_t* cost, void* stream);
+/* One document, one level: the cost volume, `iters` synchronous min-sum BP iterations from zero messages, then the belief's
+ * argmin (ties: the smallest label index) as the absolute flow [2,h,w] int16.  workspace: dvd_sflow_level_workspace_bytes
+ * (h, w, win) bytes, 256-byte aligned (the cost volume and two message buffers [4,h,w,L] u16; a negative DVD_E_* value
+ * for a bad shape).  ld_out (device, one f64, may be null) receives sum sqrt(f_u^2 + f_v^2) / (h w). */
+long dvd_sflow_level_workspace_bytes(int h, int w, int win);
+int dvd_sflow_level(const uint8_t* desc_a, const uint8_t* desc_b, const int16_t* off, int h, int w, int win, int iters,
+                    const dvd_sflow_params* params, void* workspace, int16_t* flow, double* ld_out, void* stream);
+/* The whole chain for n pairs of gray planes a (scan), b (prediction) [n,h,w] f32 of integer values 0..255: planes to u8,
+ * the integer [1,4,6,4,1] pyramid ((sum + 128) >> 8, ceil(n/2) per axis), then coarse to fine: descriptors of both
+ * planes, offsets (0 on the top level, twice the coarser flow of p >> 1 below it), cost, BP, argmin.  flow [n,2,h,w] int16,
+ * ld [n] f64 (device).  The documents are enqueued one after the other in ONE document's workspace:
+ * dvd_sflow_workspace_bytes(h, w, params) bytes, 256-byte aligned (DESIGN.md 4.7 has the formula).  Refused with DVD_E_ARG
+ * before any launch: a side of the top level below 12 or a side above 8192, and every parameter outside its range above. */
+long dvd_sflow_workspace_bytes(int h, int w, const dvd_sflow_params* params);
+int dvd_sflow(const float* a, const float* b, int n, int h, int w, const dvd_sflow_params* params, void* workspace,
+              int16_t* flow, double* ld, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
