@@ -59,6 +59,10 @@ _DEFAULTS = {
     # which metrics gt_dir scores: 'ms_ssim' | 'ms_ssim,ld' | 'ld'.  'ld' adds the local distortion, the mean length of a dense
     # SIFT-flow field from the scan to the page (ops.ld_u8): logged, written to ld.txt, left in settings.ld
     "gt_metrics": "ms_ssim",
+    # True: gt_dir also scores every page with the aligned distortion (ops.ad_u8): the SIFT-flow left after a
+    # fitted translation and scale are taken out, weighted by the scan's gradient magnitude; logged, written to ad.txt, left in
+    # settings.ad.  With 'ld' in gt_metrics both come from one run of the chain.
+    "gt_ad": False,
     # who writes dewarped_pred/warped_<stem>.png: 'pil' (the reference: copy the page to the host, Image.save) | 'hip'
     # (ops.png_encode on the device, only the compressed file crosses to the host; the same pixels, other bytes - DESIGN.md 4.4)
     "png_encoder": "pil",

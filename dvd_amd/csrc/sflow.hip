@@ -10,9 +10,11 @@
 //   sflow_bp_iter                one synchronous iteration, sender-side: a pixel reads its cost and four messages and writes
 //                                the four it sends (registers for a 5 x 5 label grid, LDS for every other window)
 //   sflow_select / _finalize     argmin of the belief, the flow, and the LD sum in a fixed order
+//   ad_fit / ad_align / ad_weighted (+ two finalizes)   aligned distortion, at the end of the file
 // No atomics anywhere: every result is a pure function of its inputs (same bits on every launch, in any batch).
 #include "common.h"
 #include "sflow_core.h"
+#include "adist_core.h"
 
 namespace dvd {
 namespace sf {
@@ -433,6 +435,37 @@ static ChainWork chain_work(int h, int w, const dvd_sflow_params& pr) {
   return cw;
 }
 
+// the whole chain of one document: planes to u8, the pyramid, then coarse to fine
+static void chain_launch(const float* a, const float* b, int h, int w, const dvd_sflow_params& pr, const ChainWork& cw, char* base,
+                         int16_t* flow, double* ld, hipStream_t st) {
+  const LevelDims dm = level_dims(h, w, pr.levels);
+  const size_t hw = (size_t)h * w;
+  uint8_t* plane[kMaxLevels][2];
+  for (int l = 0; l < pr.levels; ++l)
+    for (int s = 0; s < 2; ++s) plane[l][s] = (uint8_t*)(base + cw.plane[l][s]);
+  sflow_prep_kernel<<<cdiv((long)hw, 256), 256, 0, st>>>(a, plane[0][0], hw);
+  sflow_prep_kernel<<<cdiv((long)hw, 256), 256, 0, st>>>(b, plane[0][1], hw);
+  for (int l = 1; l < pr.levels; ++l)
+    sflow_reduce2_kernel<<<dim3(cdiv(dm.w[l], 256), dm.h[l]), 256, 0, st>>>(plane[l - 1][0], plane[l - 1][1], plane[l][0],
+                                                                            plane[l][1], dm.h[l - 1], dm.w[l - 1], dm.h[l], dm.w[l]);
+  uint8_t* da = (uint8_t*)(base + cw.desc[0]);
+  uint8_t* db = (uint8_t*)(base + cw.desc[1]);
+  int16_t* off = (int16_t*)(base + cw.off);
+  int16_t* coarse = nullptr;
+  for (int l = pr.levels - 1; l >= 0; --l) {
+    const int lh = dm.h[l], lw_ = dm.w[l];
+    dsift_launch_u8(plane[l][0], 1, lh, lw_, pr.eps, da, st);
+    dsift_launch_u8(plane[l][1], 1, lh, lw_, pr.eps, db, st);
+    if (coarse)
+      sflow_offsets_kernel<<<dim3(cdiv(lw_, 256), lh), 256, 0, st>>>(coarse, dm.h[l + 1], dm.w[l + 1], off, lh, lw_);
+    else
+      (void)hipMemsetAsync(off, 0, (size_t)lh * lw_ * 2 * sizeof(int16_t), st);
+    int16_t* cur = l == 0 ? flow : (int16_t*)(base + cw.flow[l & 1]);
+    level_launch(da, db, off, lh, lw_, level_win(pr, l), level_iters(pr, l), pr, base + cw.level, cur, l == 0 ? ld : nullptr, st);
+    coarse = cur;
+  }
+}
+
 static bool aligned(const void* p, size_t a) { return ((uintptr_t)p % a) == 0; }
 
 }  // namespace sf
@@ -511,39 +544,290 @@ extern "C" int dvd_sflow(const float* a, const float* b, int n, int h, int w, co
   if (!why) why = check_shape(h, w, *params);
   DVD_REQUIRE(!why, "sflow: %dx%d: %s", h, w, why);
   DVD_REQUIRE(aligned(workspace, 256), "sflow: workspace must be 256-byte aligned");
+  const ChainWork cw = chain_work(h, w, *params);
+  const size_t hw = (size_t)h * w;
+  for (int doc = 0; doc < n; ++doc) {
+    chain_launch(a + doc * hw, b + doc * hw, h, w, *params, cw, (char*)workspace, flow + doc * 2 * hw, ld + doc,
+                 (hipStream_t)stream);
+    if (int e = check_launch("sflow")) return e;
+  }
+  return DVD_OK;
+}
+
+// ================================================================ aligned distortion ========================================
+// AD (tests/adist_model.py; the arithmetic: adist_core.h): the chain above from the scan A to the page B,
+// a least-squares translation and scale per axis fitted to that field, B resampled through the fit, the chain again from A to
+// the resampled page, and the mean of the second field's lengths weighted by A's gradient magnitude.  The coefficients stay
+// on the device between the two flows.  All three stages move a few bytes per pixel and are launch-bound.
+namespace dvd {
+namespace sf {
+
+// ---------------------------------------------------------------- fit -------------------------------------------------------
+// 256 consecutive pixels per workgroup -> partials[block][4] = (sum f_u, sum X f_u, sum f_v, sum Y f_v), exact in int64
+__global__ void __launch_bounds__(kSelBlock) ad_fit_kernel(const int16_t* __restrict__ flow, int h, int w,
+                                                           int64_t* __restrict__ partials) {
+  __shared__ long long red[kSelBlock / 64][4];
+  const size_t hw = (size_t)h * w;
+  const size_t p = (size_t)blockIdx.x * kSelBlock + threadIdx.x;
+  long long s[4] = {0, 0, 0, 0};
+  if (p < hw) {
+    const int y = (int)(p / w), x = (int)(p - (size_t)y * w);
+    const int fu = flow[p], fv = flow[hw + p];
+    s[0] = fu;
+    s[1] = (long long)ad::centred(x, w) * fu;
+    s[2] = fv;
+    s[3] = (long long)ad::centred(y, h) * fv;
+  }
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) s[k] += __shfl_down(s[k], d, 64);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][k] = s[k];
+  }
+  __syncthreads();
+  if (threadIdx.x < 4) {
+    const int k = threadIdx.x;
+    partials[(size_t)blockIdx.x * 4 + k] = (int64_t)(red[0][k] + red[1][k] + red[2][k] + red[3][k]);
+  }
+}
+
+// one workgroup: the four sums, then the four Q16 coefficients
+__global__ void __launch_bounds__(kFinThreads) ad_fit_finalize_kernel(const int64_t* __restrict__ partials, int blocks, int h, int w,
+                                                                      int64_t* __restrict__ sums, int32_t* __restrict__ coef) {
+  __shared__ int64_t red[4][kFinThreads];
+  const int tid = threadIdx.x;
+  int64_t a[4] = {0, 0, 0, 0};
+  for (int t = tid; t < blocks; t += kFinThreads)
+#pragma unroll
+    for (int k = 0; k < 4; ++k) a[k] += partials[(size_t)t * 4 + k];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) red[k][tid] = a[k];
+  __syncthreads();
+  for (int s = kFinThreads / 2; s >= 1; s >>= 1) {
+    if (tid < s)
+#pragma unroll
+      for (int k = 0; k < 4; ++k) red[k][tid] += red[k][tid + s];
+    __syncthreads();
+  }
+  if (tid == 0) {
+    int64_t sm[4];
+    int32_t c[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) sm[k] = red[k][0];
+    ad::fit_coefs(sm, h, w, c);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      sums[k] = sm[k];
+      coef[k] = c[k];
+    }
+  }
+}
+
+// ---------------------------------------------------------------- align -----------------------------------------------------
+// one lane per output pixel; the coefficients come from device memory (the fit's output: no read-back between the flows)
+__global__ void __launch_bounds__(256) ad_align_kernel(const float* __restrict__ b, const int32_t* __restrict__ coef, int h, int w,
+                                                       float* __restrict__ out) {
+  const size_t hw = (size_t)h * w;
+  const size_t p = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (p >= hw) return;
+  const int32_t c[4] = {coef[0], coef[1], coef[2], coef[3]};
+  const int y = (int)(p / w), x = (int)(p - (size_t)y * w);
+  out[p] = (float)ad::aligned_at(b, h, w, y, x, c);
+}
+
+// ---------------------------------------------------------------- weighted mean ---------------------------------------------
+// 256 consecutive pixels per workgroup -> one partial each of g |f| and |f| (f64, in the order of sflow_select: a butterfly
+// inside each wave, then the four waves in order) and of g (int64)
+__global__ void __launch_bounds__(kSelBlock) ad_weighted_kernel(const float* __restrict__ a, const int16_t* __restrict__ flow, int h,
+                                                                int w, double* __restrict__ wpart, double* __restrict__ lpart,
+                                                                int64_t* __restrict__ gpart) {
+  __shared__ double rw[kSelBlock / 64], rl[kSelBlock / 64];
+  __shared__ int rg[kSelBlock / 64];
+  const size_t hw = (size_t)h * w;
+  const size_t p = (size_t)blockIdx.x * kSelBlock + threadIdx.x;
+  double len = 0.0, term = 0.0;
+  int g = 0;                                   // at most 360 per pixel: 256 of them stay far inside 32 bits
+  if (p < hw) {
+    const int y = (int)(p / w), x = (int)(p - (size_t)y * w);
+    g = ad::weight_at(a, h, w, y, x);
+    len = ad::flow_len(flow[p], flow[hw + p]);
+    term = ad::weighted_term(g, len);
+  }
+#pragma unroll
+  for (int s = 32; s >= 1; s >>= 1) {
+    term += __shfl_down(term, s, 64);
+    len += __shfl_down(len, s, 64);
+    g += __shfl_down(g, s, 64);
+  }
+  if ((threadIdx.x & 63) == 0) {
+    rw[threadIdx.x >> 6] = term;
+    rl[threadIdx.x >> 6] = len;
+    rg[threadIdx.x >> 6] = g;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    wpart[blockIdx.x] = ((rw[0] + rw[1]) + rw[2]) + rw[3];
+    lpart[blockIdx.x] = ((rl[0] + rl[1]) + rl[2]) + rl[3];
+    gpart[blockIdx.x] = (int64_t)rg[0] + rg[1] + rg[2] + rg[3];
+  }
+}
+
+// one workgroup: lane t adds partials t, t + 256, ... in order, then a tree over the 256 lanes (sflow_finalize's order for the
+// two f64 sums); *out = the weighted mean, or the plain mean when no pixel has a weight
+__global__ void __launch_bounds__(kFinThreads) ad_weighted_finalize_kernel(const double* __restrict__ wpart,
+                                                                           const double* __restrict__ lpart,
+                                                                           const int64_t* __restrict__ gpart, int blocks, long count,
+                                                                           double* __restrict__ out) {
+  __shared__ double rw[kFinThreads], rl[kFinThreads];
+  __shared__ int64_t rg[kFinThreads];
+  const int tid = threadIdx.x;
+  double aw = 0.0, al = 0.0;
+  int64_t ag = 0;
+  for (int t = tid; t < blocks; t += kFinThreads) {
+    aw += wpart[t];
+    al += lpart[t];
+    ag += gpart[t];
+  }
+  rw[tid] = aw;
+  rl[tid] = al;
+  rg[tid] = ag;
+  __syncthreads();
+  for (int s = kFinThreads / 2; s >= 1; s >>= 1) {
+    if (tid < s) {
+      rw[tid] += rw[tid + s];
+      rl[tid] += rl[tid + s];
+      rg[tid] += rg[tid + s];
+    }
+    __syncthreads();
+  }
+  if (tid == 0) *out = ad::ad_value(rw[0], rl[0], rg[0], (int64_t)count);
+}
+
+// ---------------------------------------------------------------- host side -------------------------------------------------
+static void fit_launch(const int16_t* flow, int h, int w, void* scratch, int64_t* sums, int32_t* coef, hipStream_t st) {
+  const int blocks = cdiv((long)h * w, kSelBlock);
+  ad_fit_kernel<<<blocks, kSelBlock, 0, st>>>(flow, h, w, (int64_t*)scratch);
+  ad_fit_finalize_kernel<<<1, kFinThreads, 0, st>>>((const int64_t*)scratch, blocks, h, w, sums, coef);
+}
+
+static void align_launch(const float* b, const int32_t* coef, int h, int w, float* out, hipStream_t st) {
+  ad_align_kernel<<<cdiv((long)h * w, 256), 256, 0, st>>>(b, coef, h, w, out);
+}
+
+// scratch: blocks f64 of g |f|, blocks f64 of |f|, blocks int64 of g
+static void weighted_launch(const float* a, const int16_t* flow, int h, int w, void* scratch, double* out, hipStream_t st) {
+  const int blocks = cdiv((long)h * w, kSelBlock);
+  double* wpart = (double*)scratch;
+  double* lpart = wpart + blocks;
+  int64_t* gpart = (int64_t*)(lpart + blocks);
+  ad_weighted_kernel<<<blocks, kSelBlock, 0, st>>>(a, flow, h, w, wpart, lpart, gpart);
+  ad_weighted_finalize_kernel<<<1, kFinThreads, 0, st>>>(wpart, lpart, gpart, blocks, (long)h * w, out);
+}
+
+// The AD chain's workspace, for ONE document: one SIFT-flow workspace (both passes), the resampled plane (f32), the two flows,
+// the partials of the fit (32 bytes per 256 pixels; the weighted mean's 24 reuse them), sums, coefficients, pass 2's LD
+struct AdWork {
+  size_t chain, aligned, flow[2], partials, sums, coef, ld2, total;
+};
+
+static AdWork ad_work(int h, int w, const dvd_sflow_params& pr) {
+  AdWork aw;
+  const size_t hw = (size_t)h * w;
+  size_t at = 0;
+  auto take = [&](size_t bytes) { const size_t o = at; at += align_up(bytes, 256); return o; };
+  aw.chain = take(chain_work(h, w, pr).total);
+  aw.aligned = take(hw * sizeof(float));
+  for (int s = 0; s < 2; ++s) aw.flow[s] = take(hw * 2 * sizeof(int16_t));
+  aw.partials = take((size_t)cdiv((long)hw, kSelBlock) * 4 * sizeof(int64_t));
+  aw.sums = take(4 * sizeof(int64_t));
+  aw.coef = take(4 * sizeof(int32_t));
+  aw.ld2 = take(sizeof(double));
+  aw.total = at;
+  return aw;
+}
+
+static int check_plane_args(const char* what, int n, int h, int w) {
+  DVD_REQUIRE(n >= 1 && n <= 65535, "%s: bad batch %d", what, n);
+  DVD_REQUIRE(h >= 1 && w >= 1 && h <= kMaxSide && w <= kMaxSide, "%s: bad shape %dx%d (each side 1..8192)", what, h, w);
+  return DVD_OK;
+}
+
+}  // namespace sf
+}  // namespace dvd
+
+extern "C" int dvd_ad_fit(const int16_t* flow, int n, int h, int w, void* scratch, int64_t* sums, int32_t* coef, void* stream) {
+  DVD_REQUIRE(flow && scratch && sums && coef, "ad_fit: null pointer");
+  if (int e = check_plane_args("ad_fit", n, h, w)) return e;
+  DVD_REQUIRE(aligned(scratch, 8) && aligned(sums, 8) && aligned(coef, 4) && aligned(flow, 2), "ad_fit: misaligned pointer");
+  const size_t hw = (size_t)h * w;
+  for (int doc = 0; doc < n; ++doc) fit_launch(flow + doc * 2 * hw, h, w, scratch, sums + 4 * doc, coef + 4 * doc, (hipStream_t)stream);
+  return check_launch("ad_fit");
+}
+
+extern "C" int dvd_ad_align(const float* b, const int32_t* coef, int n, int h, int w, float* out, void* stream) {
+  DVD_REQUIRE(b && coef && out, "ad_align: null pointer");
+  if (int e = check_plane_args("ad_align", n, h, w)) return e;
+  DVD_REQUIRE(aligned(b, 4) && aligned(coef, 4) && aligned(out, 4), "ad_align: misaligned pointer");
+  DVD_REQUIRE(b != out, "ad_align: out must not be b");
+  const size_t hw = (size_t)h * w;
+  for (int doc = 0; doc < n; ++doc) align_launch(b + doc * hw, coef + 4 * doc, h, w, out + doc * hw, (hipStream_t)stream);
+  return check_launch("ad_align");
+}
+
+extern "C" int dvd_ad_weighted(const float* a, const int16_t* flow, int n, int h, int w, void* scratch, double* ad, void* stream) {
+  DVD_REQUIRE(a && flow && scratch && ad, "ad_weighted: null pointer");
+  if (int e = check_plane_args("ad_weighted", n, h, w)) return e;
+  DVD_REQUIRE(aligned(scratch, 8) && aligned(ad, 8) && aligned(a, 4) && aligned(flow, 2), "ad_weighted: misaligned pointer");
+  const size_t hw = (size_t)h * w;
+  for (int doc = 0; doc < n; ++doc) weighted_launch(a + doc * hw, flow + doc * 2 * hw, h, w, scratch, ad + doc, (hipStream_t)stream);
+  return check_launch("ad_weighted");
+}
+
+extern "C" long dvd_adist_workspace_bytes(int h, int w, const dvd_sflow_params* params) {
+  if (!params) {
+    set_error("adist_workspace_bytes: null pointer");
+    return DVD_E_ARG;
+  }
+  const char* why = check_params(*params);
+  if (!why) why = check_shape(h, w, *params);
+  if (why) {
+    set_error("adist_workspace_bytes: %dx%d: %s", h, w, why);
+    return DVD_E_ARG;
+  }
+  return (long)ad_work(h, w, *params).total;
+}
+
+extern "C" int dvd_adist(const float* a, const float* b, int n, int h, int w, const dvd_sflow_params* params, void* workspace,
+                         double* ld, double* ad, int16_t* flow1, int64_t* sums, int32_t* coef, float* aligned_out, int16_t* flow2,
+                         void* stream) {
+  DVD_REQUIRE(a && b && params && workspace && ld && ad, "adist: null pointer");
+  DVD_REQUIRE(n >= 1 && n <= 65535, "adist: bad batch %d", n);
+  const char* why = check_params(*params);
+  if (!why) why = check_shape(h, w, *params);
+  DVD_REQUIRE(!why, "adist: %dx%d: %s", h, w, why);
+  DVD_REQUIRE(aligned(workspace, 256), "adist: workspace must be 256-byte aligned");
+  DVD_REQUIRE(aligned(ld, 8) && aligned(ad, 8) && aligned(sums, 8) && aligned(coef, 4) && aligned(aligned_out, 4) &&
+                  aligned(flow1, 2) && aligned(flow2, 2), "adist: misaligned output pointer");
   hipStream_t st = (hipStream_t)stream;
   const dvd_sflow_params& pr = *params;
-  const LevelDims dm = level_dims(h, w, pr.levels);
   const ChainWork cw = chain_work(h, w, pr);
+  const AdWork aw = ad_work(h, w, pr);
   char* base = (char*)workspace;
   const size_t hw = (size_t)h * w;
   for (int doc = 0; doc < n; ++doc) {
-    uint8_t* plane[kMaxLevels][2];
-    for (int l = 0; l < pr.levels; ++l)
-      for (int s = 0; s < 2; ++s) plane[l][s] = (uint8_t*)(base + cw.plane[l][s]);
-    sflow_prep_kernel<<<cdiv((long)hw, 256), 256, 0, st>>>(a + doc * hw, plane[0][0], hw);
-    sflow_prep_kernel<<<cdiv((long)hw, 256), 256, 0, st>>>(b + doc * hw, plane[0][1], hw);
-    for (int l = 1; l < pr.levels; ++l)
-      sflow_reduce2_kernel<<<dim3(cdiv(dm.w[l], 256), dm.h[l]), 256, 0, st>>>(plane[l - 1][0], plane[l - 1][1], plane[l][0],
-                                                                              plane[l][1], dm.h[l - 1], dm.w[l - 1], dm.h[l], dm.w[l]);
-    uint8_t* da = (uint8_t*)(base + cw.desc[0]);
-    uint8_t* db = (uint8_t*)(base + cw.desc[1]);
-    int16_t* off = (int16_t*)(base + cw.off);
-    int16_t* coarse = nullptr;
-    for (int l = pr.levels - 1; l >= 0; --l) {
-      const int lh = dm.h[l], lw_ = dm.w[l];
-      dsift_launch_u8(plane[l][0], 1, lh, lw_, pr.eps, da, st);
-      dsift_launch_u8(plane[l][1], 1, lh, lw_, pr.eps, db, st);
-      if (coarse)
-        sflow_offsets_kernel<<<dim3(cdiv(lw_, 256), lh), 256, 0, st>>>(coarse, dm.h[l + 1], dm.w[l + 1], off, lh, lw_);
-      else
-        (void)hipMemsetAsync(off, 0, (size_t)lh * lw_ * 2 * sizeof(int16_t), st);
-      int16_t* cur = l == 0 ? flow + doc * 2 * hw : (int16_t*)(base + cw.flow[l & 1]);
-      level_launch(da, db, off, lh, lw_, level_win(pr, l), level_iters(pr, l), pr, base + cw.level, cur,
-                   l == 0 ? ld + doc : nullptr, st);
-      coarse = cur;
-    }
-    if (int e = check_launch("sflow")) return e;
+    const float* ad_ = a + doc * hw;
+    const float* bd = b + doc * hw;
+    int16_t* f1 = flow1 ? flow1 + doc * 2 * hw : (int16_t*)(base + aw.flow[0]);
+    int16_t* f2 = flow2 ? flow2 + doc * 2 * hw : (int16_t*)(base + aw.flow[1]);
+    int64_t* sm = sums ? sums + 4 * doc : (int64_t*)(base + aw.sums);
+    int32_t* cf = coef ? coef + 4 * doc : (int32_t*)(base + aw.coef);
+    float* bp = aligned_out ? aligned_out + doc * hw : (float*)(base + aw.aligned);
+    chain_launch(ad_, bd, h, w, pr, cw, base + aw.chain, f1, ld + doc, st);
+    fit_launch(f1, h, w, base + aw.partials, sm, cf, st);
+    align_launch(bd, cf, h, w, bp, st);
+    chain_launch(ad_, bp, h, w, pr, cw, base + aw.chain, f2, (double*)(base + aw.ld2), st);
+    weighted_launch(ad_, f2, h, w, base + aw.partials, ad + doc, st);
+    if (int e = check_launch("adist")) return e;
   }
   return DVD_OK;
 }

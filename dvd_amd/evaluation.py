@@ -191,8 +191,8 @@ def parse_gt_metrics(value):
 
 
 def _score_against_gt(settings, logger, path, out, device, metrics=("ms_ssim",)):
-    """The metrics of one dewarped page (uint8 [H,W,3] on the device) against its ground-truth scan, if there is one: MS-SSIM
-    and / or LD, on planes prepared once."""
+    """The metrics of one dewarped page (uint8 [H,W,3] on the device) against its ground-truth scan, if there is one: MS-SSIM,
+    LD and / or AD, on planes prepared once."""
     from PIL import Image
     gt_file = find_gt(settings.env.gt_dir, path)
     if gt_file is None:
@@ -223,6 +223,8 @@ def run_evaluation_docunet(settings, logger, val_loader, diffusion, model, pretr
     left in settings.ms_ssim as [(path, value)]; a document without a ground truth is logged and skipped.
     env.gt_metrics 'ms_ssim' | 'ms_ssim,ld' | 'ld' chooses the metrics: 'ld' adds the local distortion (ops.ld_u8: the mean
     SIFT-flow length from the scan to the page) in the same way - ld.txt and settings.ld.
+    env.gt_ad = True adds the aligned distortion (ops.ad_u8) in the same way - ad.txt and settings.ad; with 'ld'
+    among the metrics both come from one run of the chain.
     Returns [(path, uint8 [H,W,3] device tensor)] (the reference returns None)."""
     from utils_flow.visualization_utils import page_settings, png_huffman_setting, visualize_dewarping
     env = settings.env
@@ -238,6 +240,11 @@ def run_evaluation_docunet(settings, logger, val_loader, diffusion, model, pretr
     if image_decoder not in ("pil", "hip"):
         raise ValueError(f"env.image_decoder must be 'pil' or 'hip', got {image_decoder!r}")
     gt_metrics = parse_gt_metrics(getattr(env, "gt_metrics", "ms_ssim"))       # what env.gt_dir scores
+    gt_ad = getattr(env, "gt_ad", False)                        # ... and whether it scores AD as well
+    if not isinstance(gt_ad, bool):
+        raise ValueError(f"env.gt_ad must be True or False, got {gt_ad!r}")
+    if gt_ad:
+        gt_metrics += ("ad",)
     device = next(model.parameters()).device
     nets = (pretrained_dewarp_model, pretrained_seg_model, pretrained_line_seg_model)
     prestage_models = None if all(m is None for m in nets) else nets

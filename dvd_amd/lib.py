@@ -116,7 +116,8 @@ NON_STATUS = {"dvd_last_error", "dvd_version", "dvd_engine_workspace_bytes", "dv
               "dvd_flash_attn_kernel_name", "dvd_gemm_kernel_name", "dvd_convnet_workspace_bytes", "dvd_convnet_weight_floats",
               "dvd_ingest_scratch_bytes", "dvd_ingest_ragged_scratch_bytes", "dvd_resize_gray_scratch_bytes",
               "dvd_msssim_workspace_bytes", "dvd_png_bound", "dvd_png_scratch_bytes", "dvd_png_scratch_bytes_huff", "dvd_jpeg_bound",
-              "dvd_jpeg_scratch_bytes", "dvd_sflow_level_workspace_bytes", "dvd_sflow_workspace_bytes"}
+              "dvd_jpeg_scratch_bytes", "dvd_sflow_level_workspace_bytes", "dvd_sflow_workspace_bytes",
+              "dvd_adist_workspace_bytes"}
 
 # name -> argtypes; kept in one table so tests can check every symbol of include/dvd_hip.h
 SIGNATURES = {
@@ -188,6 +189,12 @@ SIGNATURES = {
                         c_void],
     "dvd_sflow_workspace_bytes": [C.c_int, C.c_int, C.POINTER(SflowParams)],
     "dvd_sflow": [c_void, c_void, C.c_int, C.c_int, C.c_int, C.POINTER(SflowParams), c_void, c_void, c_void, c_void],
+    "dvd_ad_fit": [c_void, C.c_int, C.c_int, C.c_int, c_void, c_void, c_void, c_void],
+    "dvd_ad_align": [c_void, c_void, C.c_int, C.c_int, C.c_int, c_void, c_void],
+    "dvd_ad_weighted": [c_void, c_void, C.c_int, C.c_int, C.c_int, c_void, c_void, c_void],
+    "dvd_adist_workspace_bytes": [C.c_int, C.c_int, C.POINTER(SflowParams)],
+    "dvd_adist": [c_void, c_void, C.c_int, C.c_int, C.c_int, C.POINTER(SflowParams), c_void, c_void, c_void, c_void, c_void, c_void,
+                  c_void, c_void, c_void],
     "dvd_png_bound": [C.c_int, C.c_int],
     "dvd_png_scratch_bytes": [C.c_int, C.c_int],
     "dvd_png_encode_rgb8": [c_void, C.c_int, C.c_int, c_void, C.c_long, c_void, c_void, c_void],
@@ -220,6 +227,7 @@ SIGNATURES = {
 RESTYPES = {"dvd_gemm_kernel_name": C.c_char_p, "dvd_ingest_ragged_scratch_bytes": C.c_long,
             "dvd_resize_gray_scratch_bytes": C.c_long, "dvd_msssim_workspace_bytes": C.c_long,
             "dvd_sflow_level_workspace_bytes": C.c_long, "dvd_sflow_workspace_bytes": C.c_long,
+            "dvd_adist_workspace_bytes": C.c_long,
             "dvd_png_bound": C.c_long, "dvd_png_scratch_bytes": C.c_long, "dvd_png_scratch_bytes_huff": C.c_long,
             "dvd_jpeg_bound": C.c_long, "dvd_jpeg_scratch_bytes": C.c_long}
 

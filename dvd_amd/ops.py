@@ -862,21 +862,117 @@ def ld_u8(pred_hwc_u8: torch.Tensor, gt_hwc_u8: torch.Tensor, area: int = MSSSIM
     return float(local_distortion(y, x, **params)[0])
 
 
+# ---- aligned distortion (the AD kernels of dvd_amd/csrc/sflow.hip; definition: DESIGN.md 4.8) --------------------------------
+def _ad_planes(name, t, dtype, what, lead=()):
+    """[N,*lead,H,W] with N >= 1 and sides 1..8192 -> (n, h, w)"""
+    if t.dim() != 3 + len(lead) or t.shape[0] < 1 or tuple(t.shape[1:1 + len(lead)]) != tuple(lead) or min(t.shape[-2:]) < 1 \
+            or max(t.shape[-2:]) > SFLOW_MAX_SIDE:
+        shape = ",".join(["N"] + [str(v) for v in lead] + ["H", "W"])
+        raise ValueError(f"{name}: {what}: expected [{shape}] with N >= 1 and sides 1..{SFLOW_MAX_SIDE}, got {tuple(t.shape)}")
+    if t.dtype != dtype:
+        raise ValueError(f"{name}: {what} must be {dtype}, got {t.dtype}")
+    return t.shape[0], t.shape[-2], t.shape[-1]
+
+
+def ad_fit(flow: torch.Tensor):
+    """The least-squares translation and scale per axis of flow fields [N,2,H,W] int16 -> (sums int64 [N,4] = (sum f_u,
+    sum X f_u, sum f_v, sum Y f_v) with X = 2x - (W-1), Y = 2y - (H-1); coef int32 [N,4] = (ax, bx, ay, by) in Q16), both on the
+    device."""
+    n, h, w = _ad_planes("ad_fit", flow, torch.int16, "flow", (2,))
+    _chk(flow, torch.int16, "flow")
+    sums = torch.empty((n, 4), dtype=torch.int64, device=flow.device)
+    coef = torch.empty((n, 4), dtype=torch.int32, device=flow.device)
+    scratch = torch.empty((-(-h * w // 256) * 4,), dtype=torch.int64, device=flow.device)
+    lib.call("dvd_ad_fit", ptr(flow), n, h, w, ptr(scratch), ptr(sums), ptr(coef), stream_ptr())
+    return sums, coef
+
+
+def ad_align(b: torch.Tensor, coef: torch.Tensor) -> torch.Tensor:
+    """Gray planes b [N,H,W] f32 of integer values 0..255 resampled through the fitted maps coef [N,4] int32 (ad_fit's, read
+    on the device) -> [N,H,W] f32 of integer values."""
+    n, h, w = _ad_planes("ad_align", b, torch.float32, "b")
+    if tuple(coef.shape) != (n, 4) or coef.dtype != torch.int32:
+        raise ValueError(f"ad_align: coef must be int32 [{n},4], got {coef.dtype} {tuple(coef.shape)}")
+    _chk(b, torch.float32, "b")
+    _chk(coef, torch.int32, "coef")
+    out = torch.empty_like(b)
+    lib.call("dvd_ad_align", ptr(b), ptr(coef), n, h, w, ptr(out), stream_ptr())
+    return out
+
+
+def ad_weighted(a: torch.Tensor, flow: torch.Tensor) -> np.ndarray:
+    """The mean length of flow [N,2,H,W] int16 weighted by the gradient magnitude of the gray planes a [N,H,W] f32 -> float64
+    [N] (the plain mean for a plane without a gradient)."""
+    n, h, w = _ad_planes("ad_weighted", a, torch.float32, "a")
+    if tuple(flow.shape) != (n, 2, h, w) or flow.dtype != torch.int16:
+        raise ValueError(f"ad_weighted: flow must be int16 [{n},2,{h},{w}], got {flow.dtype} {tuple(flow.shape)}")
+    _chk(a, torch.float32, "a")
+    _chk(flow, torch.int16, "flow")
+    ad = torch.empty((n,), dtype=torch.float64, device=a.device)
+    scratch = torch.empty((-(-h * w // 256) * 3,), dtype=torch.int64, device=a.device)
+    lib.call("dvd_ad_weighted", ptr(a), ptr(flow), n, h, w, ptr(scratch), ptr(ad), stream_ptr())
+    return ad.cpu().numpy()
+
+
+def aligned_distortion(a: torch.Tensor, b: torch.Tensor, intermediates: bool = False, **params):
+    """AD and LD of N pairs of gray planes a (the scan), b (the prediction), [N,H,W] f32 of integer values 0..255 ->
+    (ad float64 [N], ld float64 [N]); ld is the first pass's, the value sift_flow gives.  intermediates=True adds a dict of
+    device tensors: flow1, flow2 int16 [N,2,H,W], sums int64 [N,4], coef int32 [N,4], aligned f32 [N,H,W].  The two flows, the
+    fit, the resampling and the weighted mean are enqueued together; the only read-back is the 16 N bytes at the end."""
+    pr = sflow_params("aligned_distortion", **params)
+    if a.dim() != 3 or a.shape[0] < 1 or tuple(a.shape) != tuple(b.shape):
+        raise ValueError(f"aligned_distortion: expected two [N,H,W] planes of one shape, got {tuple(a.shape)} and {tuple(b.shape)}")
+    n, h, w = a.shape
+    _sflow_check_size("aligned_distortion", h, w, pr)
+    _chk(a, torch.float32, "a")
+    _chk(b, torch.float32, "b")
+    dev = a.device
+    res = torch.empty((2, n), dtype=torch.float64, device=dev)          # ld, ad
+    extra = {}
+    if intermediates:
+        extra = dict(flow1=torch.empty((n, 2, h, w), dtype=torch.int16, device=dev), sums=torch.empty((n, 4), dtype=torch.int64, device=dev),
+                     coef=torch.empty((n, 4), dtype=torch.int32, device=dev), aligned=torch.empty((n, h, w), dtype=torch.float32, device=dev),
+                     flow2=torch.empty((n, 2, h, w), dtype=torch.int16, device=dev))
+    work = torch.empty(_size_query("dvd_adist_workspace_bytes", h, w, C.byref(pr)), dtype=torch.uint8, device=dev)
+    lib.call("dvd_adist", ptr(a), ptr(b), n, h, w, C.byref(pr), ptr(work), ptr(res[0]), ptr(res[1]),
+             *[ptr(extra.get(k)) for k in ("flow1", "sums", "coef", "aligned", "flow2")], stream_ptr())
+    host = res.cpu().numpy()
+    return (host[1], host[0], extra) if intermediates else (host[1], host[0])
+
+
+def ad_u8(pred_hwc_u8: torch.Tensor, gt_hwc_u8: torch.Tensor, area: int = MSSSIM_AREA, **params) -> float:
+    """AD for one pair of uint8 RGB images [H,W,3] of any two sizes, prepared like ms_ssim_u8 and ld_u8: the flows run from
+    the ground-truth scan to the prediction."""
+    pr = sflow_params("ad_u8", **params)
+    x, y = _metric_planes("ad_u8", pred_hwc_u8, gt_hwc_u8, area, 1, pr)
+    return float(aligned_distortion(y, x, **params)[0][0])
+
+
+GT_METRIC_NAMES = ("ms_ssim", "ld", "ad")
+
+
 def gt_metrics_u8(pred_hwc_u8: torch.Tensor, gt_hwc_u8: torch.Tensor, metrics, preset: str = "docunet",
                   area: int = MSSSIM_AREA, **params) -> dict:
-    """The metrics named in `metrics` ('ms_ssim', 'ld') for one pair of uint8 RGB images, on planes prepared once:
-    {name: float}.  Each value is what ms_ssim_u8 / ld_u8 gives alone."""
+    """The metrics named in `metrics` ('ms_ssim', 'ld', 'ad') for one pair of uint8 RGB images, on planes prepared once:
+    {name: float}.  Each value is what ms_ssim_u8 / ld_u8 / ad_u8 gives alone; with 'ld' and 'ad' the chain runs once and LD is
+    its first pass's."""
     metrics = tuple(metrics)
-    unknown = [m for m in metrics if m not in ("ms_ssim", "ld")]
+    unknown = [m for m in metrics if m not in GT_METRIC_NAMES]
     if unknown or not metrics:
-        raise ValueError(f"gt_metrics_u8: metrics must name 'ms_ssim' and / or 'ld', got {metrics!r}")
+        raise ValueError(f"gt_metrics_u8: metrics must name 'ms_ssim', 'ld' and / or 'ad', got {metrics!r}")
     _ssim_preset(preset, "gt_metrics_u8")
     pr = sflow_params("gt_metrics_u8", **params)
+    flows = "ld" in metrics or "ad" in metrics
     x, y = _metric_planes("gt_metrics_u8", pred_hwc_u8, gt_hwc_u8, area, MSSSIM_MIN_SIDE if "ms_ssim" in metrics else 1,
-                          pr if "ld" in metrics else None)
+                          pr if flows else None)
     out = {}
     if "ms_ssim" in metrics:
         out["ms_ssim"] = float(ms_ssim(x, y, preset)[0])
-    if "ld" in metrics:
+    if "ad" in metrics:
+        ad, ld = aligned_distortion(y, x, **params)
+        out["ad"] = float(ad[0])
+        if "ld" in metrics:
+            out["ld"] = float(ld[0])
+    elif "ld" in metrics:
         out["ld"] = float(local_distortion(y, x, **params)[0])
-    return out
+    return {m: out[m] for m in GT_METRIC_NAMES if m in out}

@@ -649,6 +649,36 @@ long dvd_sflow_workspace_bytes(int h, int w, const dvd_sflow_params* params);
 int dvd_sflow(const float* a, const float* b, int n, int h, int w, const dvd_sflow_params* params, void* workspace,
               int16_t* flow, double* ld, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Aligned distortion (AD), the benchmark's third number: the SIFT-flow chain above from the scan A to the page B, a
+ * least-squares fit of a translation and a scale per axis to that field, B resampled through the fit, a second flow from A to
+ * the resampled page, and the mean length of the second field weighted by the gradient magnitude of A.  The reference leaves
+ * it to offline MATLAB (evalAlignedUnwarp, not in its tree); the definition is this project's own (integer
+ * statement: tests/adist_model.py) and parity with the MATLAB pipeline is UNPINNED.  No atomics; no host read-back inside
+ * the chain.  Every plane is [h,w] with sides 1..8192; every batch n is 1..65535.
+ * ---------------------------------------------------------------------------------------- */
+/* flow [n,2,h,w] int16 -> sums [n,4] int64 = (sum f_u, sum X f_u, sum f_v, sum Y f_v) with X = 2x - (w-1), Y = 2y - (h-1),
+ * exactly, and coef [n,4] int32 = (ax, bx, ay, by) in Q16: ax = Su / (h w), bx = 2 Sxu / (h w (w^2 - 1) / 3), likewise y; each
+ * rint(num / den * 65536) in f64 (ties to even), 0 for a zero denominator, saturated to +-(2^31 - 1).  scratch: device,
+ * 32 * ceil(h w / 256) bytes, 8-byte aligned (the partial sums; the documents follow each other in it). */
+int dvd_ad_fit(const int16_t* flow, int n, int h, int w, void* scratch, int64_t* sums, int32_t* coef, void* stream);
+/* b [n,h,w] f32 of integer values 0..255, coef [n,4] int32 ON THE DEVICE -> out [n,h,w] f32 (integer values): b at
+ * cx = clamp((x << 16) + ax + ((bx X) >> 1), 0, (w-1) << 16) and cy likewise, bilinear with the 8-bit fractions (c >> 8) & 255,
+ * (sum + 32768) >> 16.  All-zero coefficients copy b.  out must not overlap b. */
+int dvd_ad_align(const float* b, const int32_t* coef, int n, int h, int w, float* out, void* stream);
+/* a [n,h,w] f32 of integer values 0..255, flow [n,2,h,w] int16 -> ad [n] f64 (device): sum g |f| / sum g with g =
+ * floor(sqrt(gx^2 + gy^2)) of a's clamped central differences; the plain mean of |f| when sum g = 0.  The f64 additions run
+ * in the fixed order of the LD sum.  scratch: device, 24 * ceil(h w / 256) bytes, 8-byte aligned. */
+int dvd_ad_weighted(const float* a, const int16_t* flow, int n, int h, int w, void* scratch, double* ad, void* stream);
+/* The whole chain for n pairs a (scan), b (prediction) as in dvd_sflow: flow 1, fit, align, flow 2, weighted mean, enqueued
+ * per document in ONE document's workspace of dvd_adist_workspace_bytes(h, w, params) bytes, 256-byte aligned (one
+ * dvd_sflow workspace for both passes, the resampled plane, two flows, the partials).  ld [n] f64 = the first pass's LD (the
+ * bits dvd_sflow gives), ad [n] f64; flow1, flow2 [n,2,h,w] int16, sums [n,4] int64, coef [n,4] int32 and aligned [n,h,w] f32
+ * may each be null.  Refused with DVD_E_ARG before any launch like dvd_sflow. */
+long dvd_adist_workspace_bytes(int h, int w, const dvd_sflow_params* params);
+int dvd_adist(const float* a, const float* b, int n, int h, int w, const dvd_sflow_params* params, void* workspace, double* ld,
+              double* ad, int16_t* flow1, int64_t* sums, int32_t* coef, float* aligned, int16_t* flow2, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
