@@ -3,6 +3,7 @@
 // stand-alone CPU restatement adist_host_check.cpp (plain C++, no HIP).  DESIGN.md section 4.8 holds the definition;
 // tests/adist_model.py is its NumPy statement.  Everything here is a pure function of its arguments.
 #pragma once
+#include "hd.h"
 #include "sflow_core.h"
 
 namespace dvd {

@@ -40,37 +40,30 @@ static Bytes align(const Bytes& b, int h, int w, const int32_t* coef) {
 static int stage(const char* which, const char* in, const char* out) {
   const bool is_fit = strcmp(which, "fit") == 0;
   if (!is_fit && strcmp(which, "align") != 0) return 2;
-  FILE* f = fopen(in, "rb");
-  if (!f) return 2;
+  Bytes file, res;
   int32_t head[6];
-  const size_t nhead = is_fit ? 2 : 6;
-  if (fread(head, sizeof(int32_t), nhead, f) != nhead) return 2;
+  const size_t nhead = (is_fit ? 2 : 6) * sizeof(int32_t);
+  if (!read_all(in, file) || file.size() < nhead) return 2;
+  memcpy(head, file.data(), nhead);
   const int h = head[0], w = head[1];
   if (h < 1 || w < 1 || h > kMaxSide || w > kMaxSide) {
-    fclose(f);
     printf("%d\n", DVD_E_ARG);
     return 0;
   }
   const size_t hw = (size_t)h * w;
-  FILE* g = nullptr;
+  if (file.size() - nhead < (is_fit ? 4 * hw : hw)) return 2;
   if (is_fit) {
     std::vector<int16_t> flow(2 * hw);
-    if (fread(flow.data(), sizeof(int16_t), 2 * hw, f) != 2 * hw) return 2;
+    memcpy(flow.data(), file.data() + nhead, 4 * hw);
     int64_t sums[4];
     int32_t coef[4];
     fit(flow, h, w, sums, coef);
-    if (!(g = fopen(out, "wb"))) return 2;
-    fwrite(sums, sizeof(int64_t), 4, g);
-    fwrite(coef, sizeof(int32_t), 4, g);
+    append(res, sums, sizeof(sums));
+    append(res, coef, sizeof(coef));
   } else {
-    Bytes b(hw);
-    if (fread(b.data(), 1, hw, f) != hw) return 2;
-    const Bytes bp = align(b, h, w, head + 2);
-    if (!(g = fopen(out, "wb"))) return 2;
-    fwrite(bp.data(), 1, bp.size(), g);
+    res = align(Bytes(file.begin() + nhead, file.begin() + nhead + hw), h, w, head + 2);
   }
-  fclose(f);
-  fclose(g);
+  if (!write_all(out, res.data(), res.size())) return 2;
   printf("0\n");
   return 0;
 }
@@ -81,26 +74,13 @@ int main(int argc, char** argv) {
     fprintf(stderr, "usage: adist_host_check in.bin out.bin\n");
     return 2;
   }
-  FILE* f = fopen(argv[1], "rb");
-  if (!f) return 2;
-  int32_t head[12];
-  if (fread(head, sizeof(int32_t), 12, f) != 12) return 2;
-  const int h = head[0], w = head[1];
+  int h, w;
   dvd_sflow_params pr;
-  memcpy(&pr, head + 2, sizeof(pr));
-  static_assert(sizeof(dvd_sflow_params) == 10 * sizeof(int32_t), "ten int fields");
-  const char* why = check_params(pr);
-  if (!why) why = check_shape(h, w, pr);
-  if (why) {
-    fclose(f);
-    fprintf(stderr, "refused: %s\n", why);
-    printf("%d\n", DVD_E_ARG);
-    return 0;
-  }
+  Bytes a, b;
+  const int rc = read_pair(argv[1], h, w, pr, a, b);
+  if (rc == DVD_E_ARG) printf("%d\n", DVD_E_ARG);
+  if (rc) return rc == DVD_E_ARG ? 0 : rc;
   const size_t hw = (size_t)h * w;
-  Bytes a(hw), b(hw);
-  if (fread(a.data(), 1, hw, f) != hw || fread(b.data(), 1, hw, f) != hw) return 2;
-  fclose(f);
 
   std::vector<int16_t> flow1, flow2;
   const double ld = chain(a, b, h, w, pr, flow1);
@@ -125,17 +105,16 @@ int main(int argc, char** argv) {
   const double wsum = ordered_sum(term, blocks), lsum = ordered_sum(len, blocks);
   const double adv = ad::ad_value(wsum, lsum, gsum, (int64_t)hw);
 
-  FILE* g = fopen(argv[2], "wb");
-  if (!g) return 2;
-  fwrite(flow1.data(), sizeof(int16_t), flow1.size(), g);
-  fwrite(sums, sizeof(int64_t), 4, g);
-  fwrite(coef, sizeof(int32_t), 4, g);
-  fwrite(bp.data(), 1, bp.size(), g);
-  fwrite(flow2.data(), sizeof(int16_t), flow2.size(), g);
-  fwrite(&ld, sizeof(double), 1, g);
-  fwrite(&ld2, sizeof(double), 1, g);
-  fwrite(&adv, sizeof(double), 1, g);
-  fclose(g);
+  Bytes out;
+  append(out, flow1.data(), flow1.size() * sizeof(int16_t));
+  append(out, sums, sizeof(sums));
+  append(out, coef, sizeof(coef));
+  append(out, bp.data(), bp.size());
+  append(out, flow2.data(), flow2.size() * sizeof(int16_t));
+  append(out, &ld, sizeof(double));
+  append(out, &ld2, sizeof(double));
+  append(out, &adv, sizeof(double));
+  if (!write_all(argv[2], out.data(), out.size())) return 2;
   printf("0\n");
   return 0;
 }

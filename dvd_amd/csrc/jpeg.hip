@@ -6,11 +6,14 @@
 //                          the 2 x 2 chroma average, level shift, 8 x 8 DCT (rows, then columns, eight lanes per block),
 //                          quantisation -> zig-zag int16 coefficients in MCU order
 //   jpeg_entropy_kernel    one workgroup per interval, kTile blocks at a time: bit lengths, scan, the blocks' bits joined in
-//                          LDS, byte stuffing (count, scan, write) -> the interval's slot and its length
-//   jpeg_layout_kernel     scan of the interval lengths -> file offsets; the header; the file's length
+//                          LDS, byte stuffing (count, scan, write) -> the interval's slot and its length; both scans are
+//                          block_ops.h's block_scan_256
+//   jpeg_layout_kernel     scan of the interval lengths (chunked_scan_256) -> file offsets; the header; the file's length
 //   jpeg_gather_kernel     one workgroup per interval: its bytes and its marker (RSTn, EOI after the last) into the file
 #include "common.h"
+#include "block_ops.h"
 #include "jpeg_core.h"
+#include "workspace.h"
 
 namespace dvd {
 namespace jpeg {
@@ -26,20 +29,7 @@ constexpr Izz make_izz() {
 }
 __device__ const Izz kIzzDev = make_izz();
 
-// Inclusive scan of one value per thread of a 256-thread workgroup; returns the thread's prefix, *total = the sum.
-__device__ __forceinline__ uint32_t block_scan(uint32_t* lds, int tid, uint32_t v, uint32_t* total) {
-  lds[tid] = v;
-  __syncthreads();
-  for (int d = 1; d < 256; d <<= 1) {
-    const uint32_t a = tid >= d ? lds[tid - d] : 0u;
-    __syncthreads();
-    lds[tid] += a;
-    __syncthreads();
-  }
-  const uint32_t incl = lds[tid];
-  *total = lds[255];
-  return incl;
-}
+__device__ __forceinline__ uint32_t add_u32(uint32_t a, uint32_t b) { return a + b; }
 
 // ---------------------------------------------------------------- transform -------------------------------------------------
 constexpr int kStripPx = 256;                 // pixel columns per workgroup: 16 MCUs of 4:2:0, 32 of 4:4:4
@@ -165,7 +155,7 @@ __global__ void __launch_bounds__(256) jpeg_entropy_kernel(const int16_t* __rest
       bits = (uint32_t)cs.bits;
     }
     uint32_t total;
-    const uint32_t incl = block_scan(scan, tid, bits, &total);
+    const uint32_t incl = block_scan_256(scan, bits, 0u, add_u32, &total);
     const uint32_t end = carry + total;                   // bits in `words` after this tile: < 32 + kTile * kBlockBitsMax
     for (uint32_t i = 1 + tid; i <= (end >> 5); i += 256) words[i] = 0;
     __syncthreads();
@@ -189,7 +179,7 @@ __global__ void __launch_bounds__(256) jpeg_entropy_kernel(const int16_t* __rest
     uint32_t ff = 0;
     for (uint32_t i = lo; i < hi; ++i) ff += stream_byte(words, i) == 0xFF;
     uint32_t ff_total;
-    const uint32_t ff_incl = block_scan(scan, tid, ff, &ff_total);
+    const uint32_t ff_incl = block_scan_256(scan, ff, 0u, add_u32, &ff_total);
     uint8_t* dst = out + outpos + lo + (ff_incl - ff);
     for (uint32_t i = lo; i < hi; ++i) {
       const uint8_t v = stream_byte(words, i);
@@ -211,25 +201,11 @@ __global__ void __launch_bounds__(256) jpeg_layout_kernel(const uint32_t* __rest
                                                           unsigned long long* __restrict__ out_len) {
   __shared__ unsigned long long part[256];
   const int tid = threadIdx.x;
-  const int per = (n + 255) / 256;
-  const int lo = min(tid * per, n), hi = min(lo + per, n);
-  unsigned long long sum = 0;
-  for (int i = lo; i < hi; ++i) sum += 2ull + lens[i];
-  part[tid] = sum;
-  __syncthreads();
-  for (int d = 1; d < 256; d <<= 1) {          // inclusive scan
-    const unsigned long long v = tid >= d ? part[tid - d] : 0ull;
-    __syncthreads();
-    part[tid] += v;
-    __syncthreads();
-  }
-  unsigned long long pos = (unsigned long long)kHeaderBytes + part[tid] - sum;
-  for (int i = lo; i < hi; ++i) {
-    offs[i] = pos;
-    pos += 2ull + lens[i];
-  }
+  const unsigned long long body = chunked_scan_256(
+      part, n, 0ull, [&](int i) { return 2ull + lens[i]; }, [](unsigned long long a, unsigned long long b) { return a + b; },
+      [&](int i, unsigned long long pre) { offs[i] = (unsigned long long)kHeaderBytes + pre; });
   for (int i = tid; i < kHeaderBytes; i += 256) out[i] = hd.b[i];
-  if (tid == 0) *out_len = (unsigned long long)kHeaderBytes + part[255];
+  if (tid == 0) *out_len = (unsigned long long)kHeaderBytes + body;
 }
 
 // ---------------------------------------------------------------- gather ----------------------------------------------------
@@ -249,17 +225,16 @@ __global__ void __launch_bounds__(256) jpeg_gather_kernel(const uint8_t* __restr
   }
 }
 
-static size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-
 struct Layout { size_t coef, slots, lens, offs, total; };
 
 static Layout layout_of(const Geom& g) {
   Layout l;
-  l.coef = 0;
-  l.slots = align_up((size_t)g.mcus_y * (size_t)g.row_blocks * 128, 256);
-  l.lens = l.slots + (size_t)g.mcus_y * (size_t)interval_slot(g.row_blocks);
-  l.offs = l.lens + align_up((size_t)g.mcus_y * sizeof(uint32_t), 256);
-  l.total = l.offs + align_up((size_t)g.mcus_y * sizeof(unsigned long long), 256);
+  Carver c;
+  l.coef = c.take((size_t)g.mcus_y * (size_t)g.row_blocks * 128);
+  l.slots = c.take((size_t)g.mcus_y * (size_t)interval_slot(g.row_blocks), 1);   // not rounded up: a slot is a multiple of 16 only
+  l.lens = c.take((size_t)g.mcus_y * sizeof(uint32_t));
+  l.offs = c.take((size_t)g.mcus_y * sizeof(unsigned long long));
+  l.total = c.at;
   return l;
 }
 

@@ -10,13 +10,7 @@
 
 #include "../../include/dvd_hip.h"
 
-#ifndef DVD_HD
-#if defined(__HIPCC__)
-#define DVD_HD __host__ __device__ __forceinline__
-#else
-#define DVD_HD inline
-#endif
-#endif
+#include "hd.h"
 
 namespace dvd {
 namespace jpeg {

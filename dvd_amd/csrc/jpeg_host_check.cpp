@@ -11,6 +11,7 @@
 
 #include <vector>
 
+#include "host_check_io.hpp"
 #include "jpeg_core.h"
 
 using namespace dvd::jpeg;
@@ -28,10 +29,9 @@ int main(int argc, char** argv) {
   const int h = atoi(argv[1]), w = atoi(argv[2]), quality = atoi(argv[3]);
   const int ss = !strcmp(argv[4], "420") ? DVD_JPEG_420 : !strcmp(argv[4], "444") ? DVD_JPEG_444 : -1;
   if (!shape_ok(h, w) || quality < 1 || quality > 100 || ss < 0) return 2;
-  std::vector<uint8_t> img((size_t)h * w * 3);
-  FILE* f = fopen(argv[5], "rb");
-  if (!f || fread(img.data(), 1, img.size(), f) != img.size()) return 2;
-  fclose(f);
+  std::vector<uint8_t> img;
+  if (!read_all(argv[5], img) || img.size() < (size_t)h * w * 3) return 2;
+  img.resize((size_t)h * w * 3);
   const Geom g = geom_of(h, w, ss);
   const QuantTables qt = quant_tables(quality);
   const Header hd = make_header(h, w, g, qt);
@@ -179,9 +179,7 @@ int main(int argc, char** argv) {
     dst[len] = 0xFF;
     dst[len + 1] = iv == g.mcus_y - 1 ? 0xD9 : (uint8_t)(0xD0 + (iv & 7));
   }
-  f = fopen(argv[6], "wb");
-  if (!f || fwrite(file.data(), 1, file.size(), f) != file.size()) return 2;
-  fclose(f);
+  if (!write_all(argv[6], file.data(), file.size())) return 2;
   printf("%llu\n", pos);
   return 0;
 }

@@ -5,13 +5,15 @@
 // iterated to its unique fixpoint from the guesses (j kSubseq 8, 0, 0).
 //   jpegdec_init_kernel    the guesses, every lane marked changed
 //   jpegdec_sync_kernel    one iteration: E[j + 1] = walk(E[j]) for every j whose E[j] changed in the iteration before
-//   jpegdec_count_kernel   blocks completed per subsequence; jpegdec_scan_kernel their exclusive scan and total
+//   jpegdec_count_kernel   blocks completed per subsequence; jpegdec_scan_kernel their exclusive scan and total (block_ops.h's
+//                          chunked_scan_256, as is jpegdec_dc_kernel<1> with dc_join for +)
 //   jpegdec_write_kernel   decodes again into the zeroed int16 [blocks][64] buffer (zig-zag order, DC differences)
 //   jpegdec_dc_kernel<0..2>  segmented prefix sum of the DC differences per component, restarted behind RSTn
 //   jpegdec_idct_kernel    dequantisation and libjpeg's integer IDCT, eight lanes per block -> u8 planes
 //   jpegdec_final_kernel   chroma upsampling, colour, EXIF orientation -> HWC bytes
 // The Huffman tables live in LDS; no kernel uses scratch memory, spins on another workgroup or loops without a bound.
 #include "common.h"
+#include "block_ops.h"
 #include "jpegdec_core.h"
 
 namespace dvd {
@@ -78,25 +80,12 @@ __global__ void __launch_bounds__(256) jpegdec_count_kernel(Plan P, const uint8_
 __global__ void __launch_bounds__(256) jpegdec_scan_kernel(const uint32_t* __restrict__ counts, long nsub, uint32_t* __restrict__ first,
                                                            uint32_t* __restrict__ ctr) {
   __shared__ unsigned long long part[256];
-  const int tid = threadIdx.x;
-  const long per = (nsub + 255) / 256;
-  const long lo = lmin((long)tid * per, nsub), hi = lmin(lo + per, nsub);
-  unsigned long long sum = 0;
-  for (long i = lo; i < hi; ++i) sum += counts[i];
-  part[tid] = sum;
-  __syncthreads();
-  for (int d = 1; d < 256; d <<= 1) {
-    const unsigned long long v = tid >= d ? part[tid - d] : 0ull;
-    __syncthreads();
-    part[tid] += v;
-    __syncthreads();
-  }
-  unsigned long long pos = part[tid] - sum;
-  for (long i = lo; i < hi; ++i) {
-    first[i] = (uint32_t)(pos > 0xFFFFFFFFull ? 0xFFFFFFFFull : pos);
-    pos += counts[i];
-  }
-  if (tid == 0) ctr[1] = (uint32_t)(part[255] > 0xFFFFFFFFull ? 0xFFFFFFFFull : part[255]);
+  const auto saturated = [](unsigned long long v) { return (uint32_t)(v > 0xFFFFFFFFull ? 0xFFFFFFFFull : v); };
+  const unsigned long long total = chunked_scan_256(
+      part, nsub, 0ull, [&](long i) { return (unsigned long long)counts[i]; },
+      [](unsigned long long a, unsigned long long b) { return a + b; },
+      [&](long i, unsigned long long pre) { first[i] = saturated(pre); });
+  if (threadIdx.x == 0) ctr[1] = saturated(total);
 }
 
 __global__ void __launch_bounds__(256) jpegdec_write_kernel(Plan P, const uint8_t* __restrict__ scan,
@@ -116,39 +105,17 @@ __global__ void __launch_bounds__(256) jpegdec_write_kernel(Plan P, const uint8_
 //   PHASE 1  one workgroup: agg[chunk] = the same over every chunk in front of it (the segmented scan's exclusive prefix)
 //   PHASE 2  the DC differences become DC values, in place
 struct DcAcc { int f, y, cb, cr; };
-__device__ __forceinline__ DcAcc dc_join(const DcAcc& a, const DcAcc& b) {
-  return b.f ? b : DcAcc{a.f, a.y + b.y, a.cb + b.cb, a.cr + b.cr};
+// on agg's int4 (f, y, cb, cr): what stands behind a flag forgets what stood in front of it
+__device__ __forceinline__ int4 dc_join(const int4& a, const int4& b) {
+  return b.x ? b : make_int4(a.x, a.y + b.y, a.z + b.z, a.w + b.w);
 }
 template <int PHASE>
 __global__ void __launch_bounds__(256) jpegdec_dc_kernel(Plan P, int16_t* __restrict__ coef, const uint8_t* __restrict__ flags,
                                                          int4* __restrict__ agg, long nchunks) {
   if (PHASE == 1) {
     __shared__ int4 part[256];
-    const int tid = threadIdx.x;
-    const long per = (nchunks + 255) / 256;
-    const long lo = lmin((long)tid * per, nchunks), hi = lmin(lo + per, nchunks);
-    DcAcc acc{0, 0, 0, 0};
-    for (long i = lo; i < hi; ++i) {
-      const int4 v = agg[i];
-      acc = dc_join(acc, DcAcc{v.x, v.y, v.z, v.w});
-    }
-    part[tid] = make_int4(acc.f, acc.y, acc.cb, acc.cr);
-    __syncthreads();
-    for (int d = 1; d < 256; d <<= 1) {
-      const int4 v = tid >= d ? part[tid - d] : make_int4(0, 0, 0, 0);
-      const int4 me = part[tid];
-      __syncthreads();
-      const DcAcc r = dc_join(DcAcc{v.x, v.y, v.z, v.w}, DcAcc{me.x, me.y, me.z, me.w});
-      part[tid] = make_int4(r.f, r.y, r.cb, r.cr);
-      __syncthreads();
-    }
-    const int4 before = tid ? part[tid - 1] : make_int4(0, 0, 0, 0);
-    DcAcc carry{before.x, before.y, before.z, before.w};
-    for (long i = lo; i < hi; ++i) {
-      const int4 v = agg[i];
-      agg[i] = make_int4(carry.f, carry.y, carry.cb, carry.cr);
-      carry = dc_join(carry, DcAcc{v.x, v.y, v.z, v.w});
-    }
+    chunked_scan_256(
+        part, nchunks, make_int4(0, 0, 0, 0), [&](long i) { return agg[i]; }, dc_join, [&](long i, const int4& pre) { agg[i] = pre; });
     return;
   }
   const long c = (long)blockIdx.x * 256 + threadIdx.x;

@@ -8,7 +8,9 @@
 #include <stdint.h>
 #include <string.h>
 
-#include "jpeg_core.h"   // DVD_HD, kZigzag
+#include "hd.h"
+#include "jpeg_core.h"   // kZigzag
+#include "workspace.h"
 
 namespace dvd {
 namespace jpegdec {
@@ -273,27 +275,25 @@ struct Layout {
   int pitch[3], rows[3];
 };
 inline Layout layout_of(const Plan& P) {
-  auto up = [](size_t v) { return (v + 255) / 256 * 256; };
   Layout l;
   const long mcus = (long)P.mcus_x * P.mcus_y;
   l.nchunks = (mcus + kDcChunk - 1) / kDcChunk;
-  size_t o = 0;
-  l.state = o;  o += up((size_t)(P.nsub + 1) * 8);
-  l.chg0 = o;   o += up((size_t)P.nsub + 1);
-  l.chg1 = o;   o += up((size_t)P.nsub + 1);
-  l.ctr = o;    o += 256;
-  l.counts = o; o += up((size_t)P.nsub * 4 + 4);
-  l.first = o;  o += up((size_t)P.nsub * 4 + 4);
-  l.flags = o;  o += up((size_t)mcus);
-  l.agg = o;    o += up((size_t)l.nchunks * 16);
-  l.coef = o;   o += up((size_t)P.nblocks * 128);
+  Carver cv;
+  l.state = cv.take((size_t)(P.nsub + 1) * 8);
+  l.chg0 = cv.take((size_t)P.nsub + 1);
+  l.chg1 = cv.take((size_t)P.nsub + 1);
+  l.ctr = cv.take(256);
+  l.counts = cv.take((size_t)P.nsub * 4 + 4);
+  l.first = cv.take((size_t)P.nsub * 4 + 4);
+  l.flags = cv.take((size_t)mcus);
+  l.agg = cv.take((size_t)l.nchunks * 16);
+  l.coef = cv.take((size_t)P.nblocks * 128);
   for (int c = 0; c < 3; ++c) {
     l.pitch[c] = P.mcus_x * 8 * (c == 0 ? P.hs : 1);
     l.rows[c] = P.mcus_y * 8 * (c == 0 ? P.vs : 1);
-    l.plane[c] = o;
-    if (c < P.ncomp) o += up((size_t)l.pitch[c] * l.rows[c]);
+    l.plane[c] = cv.take(c < P.ncomp ? (size_t)l.pitch[c] * l.rows[c] : 0);   // a grey file has one plane
   }
-  l.total = o;
+  l.total = cv.at;
   return l;
 }
 

@@ -12,6 +12,7 @@
 
 #include <vector>
 
+#include "host_check_io.hpp"
 #include "jpegdec_core.h"
 
 using namespace dvd::jpegdec;
@@ -27,14 +28,9 @@ int main(int argc, char** argv) {
     return 2;
   }
   const int max_iters = argc == 4 ? atoi(argv[3]) : kDefaultMaxIters;
-  FILE* f = fopen(argv[1], "rb");
-  if (!f || max_iters < 1) return 2;
-  fseek(f, 0, SEEK_END);
-  const long n = ftell(f);
-  fseek(f, 0, SEEK_SET);
-  std::vector<uint8_t> file((size_t)n);
-  if (n < 1 || fread(file.data(), 1, file.size(), f) != file.size()) return 2;
-  fclose(f);
+  std::vector<uint8_t> file;
+  if (max_iters < 1 || !read_all(argv[1], file) || file.empty()) return 2;
+  const long n = (long)file.size();
 
   Plan P;
   const char* why = "";
@@ -167,8 +163,6 @@ int main(int argc, char** argv) {
       dst[1] = (uint8_t)g;
       dst[2] = (uint8_t)b;
     }
-  f = fopen(argv[2], "wb");
-  if (!f || fwrite(rgb.data(), 1, rgb.size(), f) != rgb.size()) return 2;
-  fclose(f);
+  if (!write_all(argv[2], rgb.data(), rgb.size())) return 2;
   return finish(0, it, P.out_h, P.out_w);
 }

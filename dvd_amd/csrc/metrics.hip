@@ -9,6 +9,8 @@
 //   dvd_msssim_scales    the five scales of one pair of planes, enqueued back to back
 // No atomics anywhere: every result is a pure function of its inputs (same bits on every launch, in any batch).
 #include "common.h"
+#include "block_ops.h"
+#include "workspace.h"
 
 #include <math.h>
 
@@ -171,11 +173,8 @@ __global__ void __launch_bounds__(256) ssim_scale_kernel(const float* __restrict
     }
   }
   // workgroup reduction in a fixed order: butterfly inside each wave, then the four waves in order
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) {
-    s_ssim += __shfl_down(s_ssim, d, 64);
-    s_cs += __shfl_down(s_cs, d, 64);
-  }
+  s_ssim = wave_sum(s_ssim);
+  s_cs = wave_sum(s_cs);
   if ((tid & 63) == 0) { red[0][tid >> 6] = s_ssim; red[1][tid >> 6] = s_cs; }
   __syncthreads();
   if (tid == 0) {
@@ -261,8 +260,6 @@ static int resize_maxtaps(int isize, int osize) {
   const double inv = (double)isize / (double)osize;
   return (int)floor(2.0 * (inv > 1.0 ? inv : 1.0)) + 2;     // floor(2/s) + 1 taps, and one of slack
 }
-
-static size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 constexpr int kMinSide = 176;          // the fifth scale (11 x 11) still holds one full window
 constexpr int kMaxSide = 32768;        // tile grids and index arithmetic stay far inside int
@@ -352,18 +349,26 @@ extern "C" int dvd_reduce2_pair(const float* x, const float* y, float* x_out, fl
 }
 
 // workspace: partials [n, tiles of scale 1, 2] f64, then for each of scales 2..5 the planes x [n,h_s,w_s] and y [n,h_s,w_s] f32
+struct MsssimWork { size_t partials, plane[5][2], total; };   // plane[0] is unused: scale 1 reads the caller's planes
+
+static MsssimWork msssim_work(int h, int w, int n) {
+  MsssimWork wk{};
+  Carver c;
+  wk.partials = c.take((size_t)n * cdiv(h, kTile) * cdiv(w, kTile) * 2 * sizeof(double));
+  for (int s = 1; s < 5; ++s) {
+    h = (h + 1) / 2, w = (w + 1) / 2;
+    for (int k = 0; k < 2; ++k) wk.plane[s][k] = c.take((size_t)n * h * w * sizeof(float));
+  }
+  wk.total = c.at;
+  return wk;
+}
+
 extern "C" long dvd_msssim_workspace_bytes(int h, int w, int n) {
   if (h < kMinSide || w < kMinSide || h > kMaxSide || w > kMaxSide || n < 1 || n > kMaxDocs) {
     set_error("msssim_workspace_bytes: bad shape %dx%d (each side 176..32768) or batch %d", h, w, n);
     return DVD_E_ARG;
   }
-  size_t bytes = align_up((size_t)n * cdiv(h, kTile) * cdiv(w, kTile) * 2 * sizeof(double), 256);
-  for (int s = 1; s < 5; ++s) {
-    h = (h + 1) / 2;
-    w = (w + 1) / 2;
-    bytes += 2 * align_up((size_t)n * h * w * sizeof(float), 256);
-  }
-  return (long)bytes;
+  return (long)msssim_work(h, w, n).total;
 }
 
 extern "C" int dvd_msssim_scales(const float* x, const float* y, int n, int h, int w, int preset, void* workspace,
@@ -376,8 +381,9 @@ extern "C" int dvd_msssim_scales(const float* x, const float* y, int n, int h, i
   hipStream_t st = (hipStream_t)stream;
   const int border = preset == DVD_MSSSIM_WANG ? DVD_SSIM_VALID : DVD_SSIM_REPLICATE;
   const int taps = preset == DVD_MSSSIM_WANG ? 2 : 5;
-  double* partials = (double*)workspace;
-  char* next = (char*)workspace + align_up((size_t)n * cdiv(h, kTile) * cdiv(w, kTile) * 2 * sizeof(double), 256);
+  const MsssimWork wk = msssim_work(h, w, n);
+  char* base = (char*)workspace;
+  double* partials = (double*)(base + wk.partials);
   const float* cx = x;
   const float* cy = y;
   for (int s = 0; s < 5; ++s) {
@@ -386,10 +392,8 @@ extern "C" int dvd_msssim_scales(const float* x, const float* y, int n, int h, i
     ssim_finalize_kernel<<<n, 256, 0, st>>>(partials, cdiv(mh, kTile) * cdiv(mw, kTile), (double)mh * (double)mw, out_n52, s);
     if (s < 4) {
       const int oh = (h + 1) / 2, ow = (w + 1) / 2;
-      const size_t pb = align_up((size_t)n * oh * ow * sizeof(float), 256);
-      float* nx = (float*)next;
-      float* ny = (float*)(next + pb);
-      next += 2 * pb;
+      float* nx = (float*)(base + wk.plane[s + 1][0]);
+      float* ny = (float*)(base + wk.plane[s + 1][1]);
       reduce2_launch(cx, cy, nx, ny, n, h, w, taps, st);
       cx = nx; cy = ny; h = oh; w = ow;
     }

@@ -6,10 +6,14 @@
 //                         its length and Adler-32 partials
 //   png_compress_dyn_kernel  DVD_PNG_HUFFMAN_DYNAMIC: the same token loop into 16-bit tokens, their histograms, the two
 //                         length-limited codes, then the smaller of the dynamic and the fixed block written by all lanes
-//   png_layout_kernel     exclusive scan of the chunk sizes, signature, IHDR, IEND, the Adler-32, the file's length
+//   png_layout_kernel     exclusive scan of the chunk sizes (chunked_scan_256), signature, IHDR, IEND, the Adler-32, the
+//                         file's length
 //   png_gather_kernel     one workgroup per segment: its IDAT chunk (length, type, data, CRC-32) into the contiguous file
+// Both compress kernels begin with stage_segment; the wave sums and the scan are block_ops.h's, the scratch layout workspace.h's.
 #include "common.h"
+#include "block_ops.h"
 #include "png_core.h"
+#include "workspace.h"
 
 namespace dvd {
 namespace png {
@@ -35,9 +39,7 @@ __global__ void __launch_bounds__(256) png_filter_kernel(const uint8_t* __restri
   unsigned long long sum[5];
 #pragma unroll
   for (int f = 0; f < 5; ++f) {
-    sum[f] = cost[f];
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) sum[f] += __shfl_down(sum[f], d, 64);
+    sum[f] = wave_sum((unsigned long long)cost[f]);
     if ((tid & 63) == 0) red[f][tid >> 6] = sum[f];
   }
   __syncthreads();
@@ -78,13 +80,11 @@ struct WaveOps {
   static __device__ __forceinline__ void count(uint32_t* p) { atomicAdd(p, 1u); }
 };
 
-// LDS: the segment (kSeg bytes) and the hash table (8 KB), both written by this kernel before they are read.
-__global__ void __launch_bounds__(kWave) png_compress_kernel(const uint8_t* __restrict__ filt, long stream, int nseg,
-                                                              uint8_t* __restrict__ slots, SegMeta* __restrict__ meta) {
-  __shared__ __attribute__((aligned(16))) uint8_t seg[kSeg];
-  __shared__ uint16_t table[kHashSize];
+// What both compress kernels begin with: the segment's bytes into LDS, the hash table cleared, the segment's Adler-32
+// partials (valid in lane 0).  Returns the segment's length.
+__device__ __forceinline__ int stage_segment(const uint8_t* __restrict__ filt, long stream, long s, uint8_t* seg, uint16_t* table,
+                                             uint32_t* adler_a, uint32_t* adler_b) {
   const int lane = threadIdx.x;
-  const long s = blockIdx.x;
   const long base = s * kSeg;
   const int n = (int)(stream - base < kSeg ? stream - base : kSeg);
   // 16 bytes per lane; the filtered stream's buffer is padded to a multiple of 256 bytes, so the last vector stays inside it
@@ -97,13 +97,21 @@ __global__ void __launch_bounds__(kWave) png_compress_kernel(const uint8_t* __re
     a += seg[k];
     b += (unsigned long long)(n - k) * seg[k];
   }
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) {
-    a += __shfl_down(a, d, 64);
-    b += __shfl_down(b, d, 64);
-  }
+  *adler_a = (uint32_t)(wave_sum(a) % kAdlerMod);
+  *adler_b = (uint32_t)(wave_sum(b) % kAdlerMod);
+  return n;
+}
+
+// LDS: the segment (kSeg bytes) and the hash table (8 KB), both written by this kernel before they are read.
+__global__ void __launch_bounds__(kWave) png_compress_kernel(const uint8_t* __restrict__ filt, long stream, int nseg,
+                                                              uint8_t* __restrict__ slots, SegMeta* __restrict__ meta) {
+  __shared__ __attribute__((aligned(16))) uint8_t seg[kSeg];
+  __shared__ uint16_t table[kHashSize];
+  const long s = blockIdx.x;
+  uint32_t a, b;
+  const int n = stage_segment(filt, stream, s, seg, table, &a, &b);
   const int len = compress_segment<WaveOps>(seg, n, table, (uint32_t*)(slots + s * kSlot), s == 0, s == nseg - 1);
-  if (lane == 0) meta[s] = SegMeta{(uint32_t)len, (uint32_t)(a % kAdlerMod), (uint32_t)(b % kAdlerMod), 0u};
+  if (threadIdx.x == 0) meta[s] = SegMeta{(uint32_t)len, a, b, 0u};
 }
 
 // ---------------------------------------------------------------- segment compressor, dynamic Huffman ----------------------
@@ -127,23 +135,9 @@ __global__ void __launch_bounds__(kWave) png_compress_dyn_kernel(const uint8_t* 
   static_assert(sizeof(DynState) <= kSeg && alignof(DynState) <= 16, "the DynState takes the segment's place");
   const int lane = threadIdx.x;
   const long s = blockIdx.x;
-  const long base = s * kSeg;
-  const int n = (int)(stream - base < kSeg ? stream - base : kSeg);
-  const uint4* src = (const uint4*)(filt + base);
-  for (int k = lane; k * 16 < n; k += kWave) ((uint4*)seg)[k] = src[k];
-  for (int k = lane; k < kHashSize; k += kWave) table[k] = (uint16_t)kEmpty;
-  __syncthreads();
-  unsigned long long a = 0, b = 0;
-  for (int k = lane; k < n; k += kWave) {
-    a += seg[k];
-    b += (unsigned long long)(n - k) * seg[k];
-  }
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) {
-    a += __shfl_down(a, d, 64);
-    b += __shfl_down(b, d, 64);
-  }
-  if (lane == 0) meta[s] = SegMeta{0u, (uint32_t)(a % kAdlerMod), (uint32_t)(b % kAdlerMod), 0u};
+  uint32_t a, b;
+  const int n = stage_segment(filt, stream, s, seg, table, &a, &b);
+  if (lane == 0) meta[s] = SegMeta{0u, a, b, 0u};
   uint16_t* tok = tokens + s * kSeg;           // at most n <= kSeg entries
   TokenSink<WaveOps> sink{tok, 0};
   tokenise<WaveOps>(seg, n, table, sink);
@@ -215,25 +209,11 @@ __global__ void __launch_bounds__(256) png_layout_kernel(const SegMeta* __restri
                                                          unsigned long long* __restrict__ offs, uint32_t* __restrict__ adler_out,
                                                          uint8_t* __restrict__ out, unsigned long long* __restrict__ out_len) {
   __shared__ unsigned long long part[256];
-  const int tid = threadIdx.x;
-  const int per = (nseg + 255) / 256;
-  const int lo = min(tid * per, nseg), hi = min(lo + per, nseg);
-  unsigned long long sum = 0;
-  for (int s = lo; s < hi; ++s) sum += 12ull + meta[s].len + (s == nseg - 1 ? 4u : 0u);
-  part[tid] = sum;
-  __syncthreads();
-  for (int d = 1; d < 256; d <<= 1) {          // inclusive scan
-    const unsigned long long v = tid >= d ? part[tid - d] : 0ull;
-    __syncthreads();
-    part[tid] += v;
-    __syncthreads();
-  }
-  unsigned long long pos = 33ull + part[tid] - sum;
-  for (int s = lo; s < hi; ++s) {
-    offs[s] = pos;
-    pos += 12ull + meta[s].len + (s == nseg - 1 ? 4u : 0u);
-  }
-  if (tid == 0) {
+  // a chunk is 12 bytes and its data; the signature and IHDR take the file's first 33 bytes
+  const unsigned long long chunks = chunked_scan_256(
+      part, nseg, 0ull, [&](int s) { return 12ull + meta[s].len + (s == nseg - 1 ? 4u : 0u); },
+      [](unsigned long long a, unsigned long long b) { return a + b; }, [&](int s, unsigned long long pre) { offs[s] = 33ull + pre; });
+  if (threadIdx.x == 0) {
     const uint8_t sig[8] = {0x89, 'P', 'N', 'G', 0x0D, 0x0A, 0x1A, 0x0A};
     for (int k = 0; k < 8; ++k) out[k] = sig[k];
     uint8_t* ih = out + 8;
@@ -249,7 +229,7 @@ __global__ void __launch_bounds__(256) png_layout_kernel(const SegMeta* __restri
       adler_fold(A, B, (uint32_t)(left < kSeg ? left : kSeg), meta[s].a, meta[s].b);
     }
     *adler_out = (B << 16) | A;
-    const unsigned long long end = 33ull + part[255];
+    const unsigned long long end = 33ull + chunks;
     const uint8_t iend[12] = {0, 0, 0, 0, 'I', 'E', 'N', 'D', 0xAE, 0x42, 0x60, 0x82};
     for (int k = 0; k < 12; ++k) out[end + k] = iend[k];
     *out_len = end + 12;
@@ -299,21 +279,20 @@ __global__ void __launch_bounds__(256) png_gather_kernel(const uint8_t* __restri
   }
 }
 
-static size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-
 struct Layout { size_t filt, slots, meta, offs, adler, total, tokens, total_dyn; };
 
 static Layout layout_of(long stream) {
   const size_t ns = (size_t)segments(stream);
   Layout l;
-  l.filt = 0;
-  l.slots = align_up((size_t)stream, 256);
-  l.meta = l.slots + ns * (size_t)kSlot;
-  l.offs = l.meta + align_up(ns * sizeof(SegMeta), 256);
-  l.adler = l.offs + align_up(ns * sizeof(unsigned long long), 256);
-  l.total = l.adler + 256;                     // the fixed route's scratch ends here
-  l.tokens = l.total;                          // the dynamic route's: 2 bytes per stream byte of a full segment
-  l.total_dyn = l.tokens + ns * (size_t)kSeg * sizeof(uint16_t);
+  Carver c;
+  l.filt = c.take((size_t)stream);
+  l.slots = c.take(ns * (size_t)kSlot, 1);     // not rounded up: kSlot is a multiple of 16 only
+  l.meta = c.take(ns * sizeof(SegMeta));
+  l.offs = c.take(ns * sizeof(unsigned long long));
+  l.adler = c.take(256);
+  l.total = c.at;                              // the fixed route's scratch ends here
+  l.tokens = c.take(ns * (size_t)kSeg * sizeof(uint16_t), 1);   // the dynamic route's: 2 bytes per stream byte of a full segment
+  l.total_dyn = c.at;
   return l;
 }
 

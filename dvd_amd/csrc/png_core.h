@@ -15,11 +15,7 @@
 
 #include "../../include/dvd_hip.h"
 
-#if defined(__HIPCC__)
-#define DVD_HD __host__ __device__ __forceinline__
-#else
-#define DVD_HD inline
-#endif
+#include "hd.h"
 
 namespace dvd {
 namespace png {

@@ -13,6 +13,7 @@
 
 #include <vector>
 
+#include "host_check_io.hpp"
 #include "png_core.h"
 
 using namespace dvd::png;
@@ -109,10 +110,9 @@ int main(int argc, char** argv) {
   const int h = atoi(argv[1]), w = atoi(argv[2]);
   if (h < 1 || w < 1 || 3L * w + 1 > ((1L << 31) - 1) / h) return 2;
   const long rb = 3L * w, stream = stream_bytes(h, w);
-  std::vector<uint8_t> img((size_t)h * rb);
-  FILE* f = fopen(argv[3], "rb");
-  if (!f || fread(img.data(), 1, img.size(), f) != img.size()) return 2;
-  fclose(f);
+  std::vector<uint8_t> img;
+  if (!read_all(argv[3], img) || img.size() < (size_t)h * rb) return 2;
+  img.resize((size_t)h * rb);
 
   // filter: exactly the stream's bytes, so that any access past it is the sanitizer's to find
   std::vector<uint8_t> filt((size_t)stream);
@@ -224,9 +224,7 @@ int main(int argc, char** argv) {
     put_be32(dst + 8 + N, ~(crc_mul(head, crc_xpow8((unsigned long long)N)) ^ part[0]));
   }
 
-  f = fopen(argv[4], "wb");
-  if (!f || fwrite(out.data(), 1, out.size(), f) != out.size()) return 2;
-  fclose(f);
+  if (!write_all(argv[4], out.data(), out.size())) return 2;
   printf("%llu\n", total);
   return 0;
 }

@@ -11,10 +11,13 @@
 //                                the four it sends (registers for a 5 x 5 label grid, LDS for every other window)
 //   sflow_select / _finalize     argmin of the belief, the flow, and the LD sum in a fixed order
 //   ad_fit / ad_align / ad_weighted (+ two finalizes)   aligned distortion, at the end of the file
-// No atomics anywhere: every result is a pure function of its inputs (same bits on every launch, in any batch).
+// No atomics anywhere: every result is a pure function of its inputs (same bits on every launch, in any batch).  The sums inside
+// a wave are block_ops.h's wave_sum, whose order the f64 results are defined by; the workspaces are carved with workspace.h.
 #include "common.h"
+#include "block_ops.h"
 #include "sflow_core.h"
 #include "adist_core.h"
+#include "workspace.h"
 
 namespace dvd {
 namespace sf {
@@ -333,8 +336,7 @@ __global__ void __launch_bounds__(kSelBlock) sflow_select_kernel(const uint16_t*
     flow[hw + p] = (int16_t)fv;
     len = flow_length(fu, fv);
   }
-#pragma unroll
-  for (int s = 32; s >= 1; s >>= 1) len += __shfl_down(len, s, 64);
+  len = wave_sum(len);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = len;
   __syncthreads();
   if (threadIdx.x == 0) partials[blockIdx.x] = ((red[0] + red[1]) + red[2]) + red[3];
@@ -357,8 +359,6 @@ __global__ void __launch_bounds__(kFinThreads) sflow_finalize_kernel(const doubl
 }
 
 // ---------------------------------------------------------------- host side -------------------------------------------------
-static size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-
 static void dsift_launch_u8(const uint8_t* img, int n, int h, int w, int eps, uint8_t* out, hipStream_t st) {
   sflow_dsift_kernel<uint8_t><<<dim3(cdiv(w, kDsTile), cdiv(h, kDsTile), n), 256, 0, st>>>(img, h, w, eps, out);
 }
@@ -368,18 +368,19 @@ static void cost_launch(const uint8_t* da, const uint8_t* db, const int16_t* off
   sflow_cost_kernel<<<dim3(cdiv((long)h * w, 256), 2 * win + 1), 256, 0, st>>>(da, db, off, h, w, win, pr.gamma, pr.T, cost);
 }
 
-// one level's workspace: the cost volume, two message buffers, the LD partials
+// one level's workspace, as offsets: the cost volume, two message buffers (one behind the other), the LD partials
 struct LevelWork {
-  size_t cost, msg, partials, total;
+  size_t cost, msg[2], partials, total;
 };
 
 static LevelWork level_work(int h, int w, int win) {
   const size_t L = (size_t)(2 * win + 1) * (2 * win + 1), hw = (size_t)h * w;
   LevelWork lw;
-  lw.cost = align_up(hw * L * sizeof(uint16_t), 256);
-  lw.msg = align_up(4 * hw * L * sizeof(uint16_t), 256);
-  lw.partials = align_up((size_t)cdiv((long)hw, kSelBlock) * sizeof(double), 256);
-  lw.total = lw.cost + 2 * lw.msg + lw.partials;
+  Carver c;
+  lw.cost = c.take(hw * L * sizeof(uint16_t));
+  for (int s = 0; s < 2; ++s) lw.msg[s] = c.take(4 * hw * L * sizeof(uint16_t));
+  lw.partials = c.take((size_t)cdiv((long)hw, kSelBlock) * sizeof(double));
+  lw.total = c.at;
   return lw;
 }
 
@@ -387,12 +388,13 @@ static LevelWork level_work(int h, int w, int win) {
 static void level_launch(const uint8_t* da, const uint8_t* db, const int16_t* off, int h, int w, int win, int iters,
                          const dvd_sflow_params& pr, void* workspace, int16_t* flow, double* ld_out, hipStream_t st) {
   const LevelWork lw = level_work(h, w, win);
-  uint16_t* cost = (uint16_t*)workspace;
-  uint16_t* msg[2] = {(uint16_t*)((char*)workspace + lw.cost), (uint16_t*)((char*)workspace + lw.cost + lw.msg)};
-  double* partials = (double*)((char*)workspace + lw.cost + 2 * lw.msg);
+  char* base = (char*)workspace;
+  uint16_t* cost = (uint16_t*)(base + lw.cost);
+  uint16_t* msg[2] = {(uint16_t*)(base + lw.msg[0]), (uint16_t*)(base + lw.msg[1])};
+  double* partials = (double*)(base + lw.partials);
   const long hw = (long)h * w;
   cost_launch(da, db, off, h, w, win, pr, cost, st);
-  (void)hipMemsetAsync(msg[0], 0, 2 * lw.msg, st);
+  (void)hipMemsetAsync(msg[0], 0, lw.partials - lw.msg[0], st);   // both message buffers
   for (int it = 0; it < iters; ++it) {
     const uint16_t* in = msg[it & 1];
     uint16_t* out = msg[(it + 1) & 1];
@@ -418,20 +420,19 @@ struct ChainWork {
 static ChainWork chain_work(int h, int w, const dvd_sflow_params& pr) {
   const LevelDims dm = level_dims(h, w, pr.levels);
   ChainWork cw;
-  size_t at = 0;
-  auto take = [&](size_t bytes) { const size_t o = at; at += align_up(bytes, 256); return o; };
+  Carver c;
   for (int l = 0; l < pr.levels; ++l)
-    for (int s = 0; s < 2; ++s) cw.plane[l][s] = take((size_t)dm.h[l] * dm.w[l]);
-  for (int s = 0; s < 2; ++s) cw.desc[s] = take((size_t)h * w * kDesc);
-  cw.off = take((size_t)h * w * 2 * sizeof(int16_t));
-  for (int s = 0; s < 2; ++s) cw.flow[s] = take((size_t)h * w * 2 * sizeof(int16_t));
+    for (int s = 0; s < 2; ++s) cw.plane[l][s] = c.take((size_t)dm.h[l] * dm.w[l]);
+  for (int s = 0; s < 2; ++s) cw.desc[s] = c.take((size_t)h * w * kDesc);
+  cw.off = c.take((size_t)h * w * 2 * sizeof(int16_t));
+  for (int s = 0; s < 2; ++s) cw.flow[s] = c.take((size_t)h * w * 2 * sizeof(int16_t));
   size_t lvl = 0;
   for (int l = 0; l < pr.levels; ++l) {
     const size_t t = level_work(dm.h[l], dm.w[l], level_win(pr, l)).total;
     lvl = t > lvl ? t : lvl;
   }
-  cw.level = take(lvl);
-  cw.total = at;
+  cw.level = c.take(lvl);
+  cw.total = c.at;
   return cw;
 }
 
@@ -580,8 +581,7 @@ __global__ void __launch_bounds__(kSelBlock) ad_fit_kernel(const int16_t* __rest
   }
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) s[k] += __shfl_down(s[k], d, 64);
+    s[k] = wave_sum(s[k]);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][k] = s[k];
   }
   __syncthreads();
@@ -653,12 +653,9 @@ __global__ void __launch_bounds__(kSelBlock) ad_weighted_kernel(const float* __r
     len = ad::flow_len(flow[p], flow[hw + p]);
     term = ad::weighted_term(g, len);
   }
-#pragma unroll
-  for (int s = 32; s >= 1; s >>= 1) {
-    term += __shfl_down(term, s, 64);
-    len += __shfl_down(len, s, 64);
-    g += __shfl_down(g, s, 64);
-  }
+  term = wave_sum(term);
+  len = wave_sum(len);
+  g = wave_sum(g);
   if ((threadIdx.x & 63) == 0) {
     rw[threadIdx.x >> 6] = term;
     rl[threadIdx.x >> 6] = len;
@@ -733,16 +730,15 @@ struct AdWork {
 static AdWork ad_work(int h, int w, const dvd_sflow_params& pr) {
   AdWork aw;
   const size_t hw = (size_t)h * w;
-  size_t at = 0;
-  auto take = [&](size_t bytes) { const size_t o = at; at += align_up(bytes, 256); return o; };
-  aw.chain = take(chain_work(h, w, pr).total);
-  aw.aligned = take(hw * sizeof(float));
-  for (int s = 0; s < 2; ++s) aw.flow[s] = take(hw * 2 * sizeof(int16_t));
-  aw.partials = take((size_t)cdiv((long)hw, kSelBlock) * 4 * sizeof(int64_t));
-  aw.sums = take(4 * sizeof(int64_t));
-  aw.coef = take(4 * sizeof(int32_t));
-  aw.ld2 = take(sizeof(double));
-  aw.total = at;
+  Carver c;
+  aw.chain = c.take(chain_work(h, w, pr).total);
+  aw.aligned = c.take(hw * sizeof(float));
+  for (int s = 0; s < 2; ++s) aw.flow[s] = c.take(hw * 2 * sizeof(int16_t));
+  aw.partials = c.take((size_t)cdiv((long)hw, kSelBlock) * 4 * sizeof(int64_t));
+  aw.sums = c.take(4 * sizeof(int64_t));
+  aw.coef = c.take(4 * sizeof(int32_t));
+  aw.ld2 = c.take(sizeof(double));
+  aw.total = c.at;
   return aw;
 }
 

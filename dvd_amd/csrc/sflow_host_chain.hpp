@@ -6,11 +6,36 @@
 
 #include <vector>
 
+#include "host_check_io.hpp"
 #include "sflow_core.h"
 
 using namespace dvd::sf;
 
 typedef std::vector<uint8_t> Bytes;
+
+// in.bin of both programs: int32 h, w, the ten int32 fields of dvd_sflow_params in their order, plane A, plane B.  Returns 0,
+// 2 for a file that cannot be read or is too short, DVD_E_ARG for a refused shape or parameter (said on stderr).
+static int read_pair(const char* path, int& h, int& w, dvd_sflow_params& pr, Bytes& a, Bytes& b) {
+  Bytes in;
+  int32_t head[12];
+  if (!read_all(path, in) || in.size() < sizeof(head)) return 2;
+  memcpy(head, in.data(), sizeof(head));
+  h = head[0];
+  w = head[1];
+  memcpy(&pr, head + 2, sizeof(pr));
+  static_assert(sizeof(dvd_sflow_params) == 10 * sizeof(int32_t), "ten int fields");
+  const char* why = check_params(pr);
+  if (!why) why = check_shape(h, w, pr);
+  if (why) {
+    fprintf(stderr, "refused: %s\n", why);
+    return DVD_E_ARG;
+  }
+  const size_t hw = (size_t)h * w;
+  if (in.size() - sizeof(head) < 2 * hw) return 2;
+  a.assign(in.begin() + sizeof(head), in.begin() + sizeof(head) + hw);
+  b.assign(in.begin() + sizeof(head) + hw, in.begin() + sizeof(head) + 2 * hw);
+  return 0;
+}
 
 static Bytes dsift(const Bytes& img, int h, int w, int eps) {
   std::vector<int> r((size_t)h * w * 8), c((size_t)h * w * 8);

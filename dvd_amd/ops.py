@@ -460,16 +460,30 @@ def ms_ssim_u8(pred_hwc_u8: torch.Tensor, gt_hwc_u8: torch.Tensor, preset: str =
 
 
 # ---- PNG of a dewarped page, encoded on the device (dvd_amd/csrc/png.hip; format: DESIGN.md 4.4) ------------------------------
-def _png_input(img, name):
-    """The encoder's input: checked before anything is allocated or launched."""
+def _rgb8_input(img, name):
+    """(h, w) of an encoder's input, a contiguous uint8 [H,W,3] tensor: checked before anything is allocated or launched."""
     if not torch.is_tensor(img) or img.dim() != 3 or img.shape[2] != 3 or min(img.shape[:2]) < 1:
         raise ValueError(f"{name}: expected a [H,W,3] tensor, got {tuple(img.shape) if torch.is_tensor(img) else type(img)}")
     if img.dtype != torch.uint8 or not img.is_contiguous():
         raise ValueError(f"{name}: expected contiguous uint8, got {img.dtype} contiguous={img.is_contiguous()}")
-    h, w = int(img.shape[0]), int(img.shape[1])
-    if h * (3 * w + 1) >= 2 ** 31:
-        raise ValueError(f"{name}: image {h}x{w} too large (h * (3w + 1) must be below 2^31)")
-    return h, w
+    return int(img.shape[0]), int(img.shape[1])
+
+
+def _scratch(scratch, need, dev, name):
+    """The caller's optional scratch buffer, checked, or a fresh one of `need` bytes on `dev`."""
+    if scratch is None:
+        return torch.empty(need, dtype=torch.uint8, device=dev)
+    if scratch.dtype != torch.uint8 or not scratch.is_contiguous() or scratch.numel() < need or scratch.device != dev:
+        raise ValueError(f"{name}: scratch must be a contiguous uint8 buffer of >= {need} bytes on {dev}")
+    return scratch
+
+
+def _device_bytes_to_file(data, path):
+    """Write a uint8 device tensor to `path`: only these bytes cross to the host.  Returns their number."""
+    data = data.cpu().numpy()
+    with open(path, "wb") as f:
+        f.write(data.tobytes())
+    return int(data.size)
 
 
 def png_bound(h: int, w: int) -> int:
@@ -494,14 +508,13 @@ def png_encode(img_hwc_u8: torch.Tensor, scratch: torch.Tensor = None, huffman: 
     file).  scratch (optional): a uint8 device buffer of at least dvd_png_scratch_bytes_huff(H, W, huffman) bytes to reuse
     between calls; its contents do not matter."""
     flag = png_huffman_flag(huffman)
-    h, w = _png_input(img_hwc_u8, "png_encode")
+    h, w = _rgb8_input(img_hwc_u8, "png_encode")
+    if h * (3 * w + 1) >= 2 ** 31:
+        raise ValueError(f"png_encode: image {h}x{w} too large (h * (3w + 1) must be below 2^31)")
     _chk(img_hwc_u8, torch.uint8, "img")
     dev = img_hwc_u8.device
     need = _size_query("dvd_png_scratch_bytes_huff", h, w, flag)
-    if scratch is None:
-        scratch = torch.empty(need, dtype=torch.uint8, device=dev)
-    elif scratch.dtype != torch.uint8 or not scratch.is_contiguous() or scratch.numel() < need or scratch.device != dev:
-        raise ValueError(f"png_encode: scratch must be a contiguous uint8 buffer of >= {need} bytes on {dev}")
+    scratch = _scratch(scratch, need, dev, "png_encode")
     cap = png_bound(h, w)
     out = torch.empty(cap, dtype=torch.uint8, device=dev)
     nbytes = torch.zeros(1, dtype=torch.int64, device=dev)
@@ -511,10 +524,7 @@ def png_encode(img_hwc_u8: torch.Tensor, scratch: torch.Tensor = None, huffman: 
 
 def png_encode_to_file(img_hwc_u8: torch.Tensor, path: str, huffman: str = "fixed") -> int:
     """Encode on the device and write `path`: only the compressed bytes cross to the host.  Returns the file's bytes."""
-    data = png_encode(img_hwc_u8, huffman=huffman).cpu().numpy()
-    with open(path, "wb") as f:
-        f.write(data.tobytes())
-    return int(data.size)
+    return _device_bytes_to_file(png_encode(img_hwc_u8, huffman=huffman), path)
 
 
 # ---- JPEG of a dewarped page, encoded on the device (dvd_amd/csrc/jpeg.hip; format: DESIGN.md 4.5) ----------------------------
@@ -530,18 +540,6 @@ def jpeg_settings(quality, subsampling, name="jpeg_encode"):
     return int(quality), JPEG_SUBSAMPLINGS[subsampling]
 
 
-def _jpeg_input(img, name):
-    """The encoder's input: checked before anything is allocated or launched."""
-    if not torch.is_tensor(img) or img.dim() != 3 or img.shape[2] != 3 or min(img.shape[:2]) < 1:
-        raise ValueError(f"{name}: expected a [H,W,3] tensor, got {tuple(img.shape) if torch.is_tensor(img) else type(img)}")
-    if img.dtype != torch.uint8 or not img.is_contiguous():
-        raise ValueError(f"{name}: expected contiguous uint8, got {img.dtype} contiguous={img.is_contiguous()}")
-    h, w = int(img.shape[0]), int(img.shape[1])
-    if max(h, w) > 65535 or 3 * (-(-h // 16) * 16) * (-(-w // 16) * 16) >= 2 ** 31:
-        raise ValueError(f"{name}: image {h}x{w} too large (h, w <= 65535 and the padded planes below 2^31 bytes)")
-    return h, w
-
-
 def jpeg_bound(h: int, w: int, subsampling: str = "420") -> int:
     """Worst-case bytes of the JPEG file of an h x w RGB image (dvd_jpeg_bound)."""
     return _size_query("dvd_jpeg_bound", h, w, jpeg_settings(90, subsampling, "jpeg_bound")[1])
@@ -552,15 +550,14 @@ def jpeg_encode(img_hwc_u8: torch.Tensor, quality: int = 90, subsampling: str = 
     read-back (the file's length) to trim the worst-case buffer.  The bytes depend on (H, W, pixels, quality, subsampling) only.
     The tensor's first byte may lie at any address.  scratch (optional): a uint8 device buffer of at least
     dvd_jpeg_scratch_bytes(H, W, subsampling) bytes to reuse between calls; its contents do not matter."""
-    h, w = _jpeg_input(img_hwc_u8, "jpeg_encode")
+    h, w = _rgb8_input(img_hwc_u8, "jpeg_encode")
+    if max(h, w) > 65535 or 3 * (-(-h // 16) * 16) * (-(-w // 16) * 16) >= 2 ** 31:
+        raise ValueError(f"jpeg_encode: image {h}x{w} too large (h, w <= 65535 and the padded planes below 2^31 bytes)")
     quality, flag = jpeg_settings(quality, subsampling)
     _chk(img_hwc_u8, torch.uint8, "img")
     dev = img_hwc_u8.device
     need = _size_query("dvd_jpeg_scratch_bytes", h, w, flag)
-    if scratch is None:
-        scratch = torch.empty(need, dtype=torch.uint8, device=dev)
-    elif scratch.dtype != torch.uint8 or not scratch.is_contiguous() or scratch.numel() < need or scratch.device != dev:
-        raise ValueError(f"jpeg_encode: scratch must be a contiguous uint8 buffer of >= {need} bytes on {dev}")
+    scratch = _scratch(scratch, need, dev, "jpeg_encode")
     cap = _size_query("dvd_jpeg_bound", h, w, flag)
     out = torch.empty(cap, dtype=torch.uint8, device=dev)
     nbytes = torch.zeros(1, dtype=torch.int64, device=dev)
@@ -570,10 +567,7 @@ def jpeg_encode(img_hwc_u8: torch.Tensor, quality: int = 90, subsampling: str = 
 
 def jpeg_encode_to_file(img_hwc_u8: torch.Tensor, path: str, quality: int = 90, subsampling: str = "420") -> int:
     """Encode on the device and write `path`: only the compressed bytes cross to the host.  Returns the file's bytes."""
-    data = jpeg_encode(img_hwc_u8, quality, subsampling).cpu().numpy()
-    with open(path, "wb") as f:
-        f.write(data.tobytes())
-    return int(data.size)
+    return _device_bytes_to_file(jpeg_encode(img_hwc_u8, quality, subsampling), path)
 
 
 # ---- JPEG decoder for the input photograph (dvd_amd/csrc/jpegdec.hip; definition: DESIGN.md 4.6) ------------------------------
@@ -649,10 +643,7 @@ def jpeg_decode(data, device=None, max_iters: int = None, scratch: torch.Tensor 
     dev = dev_file.device
     _chk(dev_file, torch.uint8, "file")
     need, numel = int(info.scratch_bytes), 3 * info.h * info.w
-    if scratch is None:
-        scratch = torch.empty(need, dtype=torch.uint8, device=dev)
-    elif scratch.dtype != torch.uint8 or not scratch.is_contiguous() or scratch.numel() < need or scratch.device != dev:
-        raise ValueError(f"jpeg_decode: scratch must be a contiguous uint8 buffer of >= {need} bytes on {dev}")
+    scratch = _scratch(scratch, need, dev, "jpeg_decode")
     if out is None:
         out = torch.empty(numel, dtype=torch.uint8, device=dev)
     elif out.dtype != torch.uint8 or not out.is_contiguous() or out.numel() < numel or out.device != dev:

@@ -258,9 +258,9 @@ def _of_stream(n, seed):
     return _rand(h, w, seed=seed, hi=4)               # few values: matches of every length
 
 
-def _page():
+def _page(h=700, w=500):
     from benchmarks.png_time import page_image
-    return page_image(700, 500)
+    return page_image(h, w)
 
 
 DEEP_RARE, DEEP_BYTES, DEEP_SEED = 11, 30000, 0
@@ -305,13 +305,17 @@ CASES = {
     "page_700x500": _page,
     "deep": deep_image,
 }
+# For the digests alone (the block parser above would take minutes on its 5 MB): a stream of 2731 * 3073 bytes = 257 segments of
+# 32 KiB, so that a lane of png_layout_kernel's scan owns more than one segment.
+LARGE_CASES = {"257_segments_2731x1024": lambda: _page(2731, 1024)}
+DIGEST_CASES = {**CASES, **LARGE_CASES}
 _cache = {}
 
 
 def case(name):
     """The image of a case, made once and never changed (read-only)."""
     if name not in _cache:
-        img = np.ascontiguousarray(CASES[name]())
+        img = np.ascontiguousarray(DIGEST_CASES[name]())
         img.setflags(write=False)
         _cache[name] = img
     return _cache[name]

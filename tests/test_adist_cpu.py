@@ -15,6 +15,7 @@ import torch
 
 import adist_model as A
 import sflow_model as M
+from host_check import build_host_check
 from dvd_amd import lib, ops
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
@@ -147,11 +148,7 @@ def test_ad_sum_against_a_plain_sum():
 # ---- 3. the CPU restatement of the kernels' arithmetic, under AddressSanitizer and UBSan --------------------------------------
 @pytest.fixture(scope="module")
 def host_check(tmp_path_factory):
-    exe = tmp_path_factory.mktemp("adist_host") / "adist_host_check"
-    src = os.path.join(ROOT, "dvd_amd", "csrc", "adist_host_check.cpp")
-    subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", src, "-o",
-                    str(exe)], check=True)
-    return exe
+    return build_host_check("adist", tmp_path_factory.mktemp("adist_host"))
 
 
 def _run(exe, tmp_path, payload, *mode):

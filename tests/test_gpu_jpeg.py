@@ -1,8 +1,9 @@
 """The JPEG encoder's kernels (dvd_amd/csrc/jpeg.hip) on the GPU: the library's file must EQUAL the integer model's
 (tests/jpeg_model.py, itself held to PIL and to the sanitized CPU restatement by tests/test_jpeg_cpu.py) byte for byte.  The
 shapes are the smallest at which each part can go wrong: images below one MCU, sizes that are no multiple of it, ten intervals
-(RST wraps), 513 MCUs in one interval (more than one tile of 256 blocks per interval, a strip boundary every 256 pixels), stuffed
-0xFF bytes, ZRL and EOB; one full page for the sizes no small image reaches."""
+(RST wraps), 257 intervals (two to a lane of the layout scan), 513 MCUs in one interval (more than one tile of 256 blocks per
+interval, a strip boundary every 256 pixels), stuffed 0xFF bytes, ZRL and EOB; one full page for the sizes no small image
+reaches."""
 import numpy as np
 import pytest
 import torch
@@ -42,6 +43,17 @@ def test_file_equals_the_model(name, subsampling):
         assert data == want, (quality, len(data), len(want), next((i for i, (a, b) in enumerate(zip(data, want)) if a != b), None))
         assert len(data) <= lib.raw().dvd_jpeg_bound(h, w, J.SUBSAMPLINGS[subsampling])
     J.check_jpeg(data, img, qualities[-1], subsampling)
+
+
+def test_257_intervals_two_to_a_lane_of_the_layout_scan():
+    """2056 x 8 in 4:4:4 = 257 restart intervals: a lane of jpeg_layout_kernel's scan over the interval lengths owns two."""
+    img = J.noise_image(2056, 8, seed=2056 * 131 + 8)
+    for quality in J.QUALITIES:
+        data = _encode(img, quality, "444")
+        want = J.model_file(img, quality, "444")
+        assert data == want, (quality, len(data), len(want), next((i for i, (a, b) in enumerate(zip(data, want)) if a != b), None))
+        assert len(data) <= lib.raw().dvd_jpeg_bound(2056, 8, J.SUBSAMPLINGS["444"])
+    J.check_jpeg(data, img, J.QUALITIES[-1], "444")
 
 
 @pytest.mark.parametrize("subsampling", SS)

@@ -1,5 +1,5 @@
 """The PNG encoder's dynamic-Huffman route (png_compress_dyn_kernel) on the GPU.  Every case of
-png_dyn_model.CASES is encoded with huffman='dynamic', taken apart by png_model.check_png and compared BYTE FOR BYTE (length and
+png_dyn_model.DIGEST_CASES is encoded with huffman='dynamic', taken apart by png_model.check_png and compared BYTE FOR BYTE (length and
 SHA-256) with tests/golden/png_dynamic_digests.json, which the CPU restatement png_host_check wrote: the GPU computes what the
 restatement computes.  huffman='fixed' and the old entry point are held to tests/golden/png_fixed_digests.json, written by the
 host program as it was before the dynamic route existed: the fixed route's bytes have not changed."""
@@ -39,7 +39,7 @@ def _want(table, name):
     return {k: table[name][k] for k in ("length", "sha256")}
 
 
-@pytest.mark.parametrize("name", list(D.CASES))
+@pytest.mark.parametrize("name", list(D.DIGEST_CASES))
 def test_dynamic_file_is_the_host_restatements(name):
     img = D.case(name)
     h, w, _ = img.shape
@@ -49,7 +49,7 @@ def test_dynamic_file_is_the_host_restatements(name):
     assert len(data) <= FIXED[name]["length"]
 
 
-@pytest.mark.parametrize("name", list(D.CASES))
+@pytest.mark.parametrize("name", list(D.DIGEST_CASES))
 def test_fixed_route_writes_the_bytes_it_wrote_before(name):
     img = D.case(name)
     h, w, _ = img.shape

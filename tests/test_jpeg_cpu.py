@@ -13,6 +13,7 @@ import torch
 from PIL import Image
 
 import jpeg_model as J
+from host_check import build_host_check
 from dvd_amd import lib, ops
 
 ROOT = J.ROOT
@@ -84,11 +85,7 @@ def test_stress_inputs_exercise_stuffing_zrl_and_eob(subsampling):
 def host_check(tmp_path_factory):
     """dvd_amd/csrc/jpeg_host_check.cpp: jpeg.hip's transform, tiles, emitter, stuffing, layout and gather on the shared
     jpeg_core.h, as a stand-alone program with exact-size buffers."""
-    exe = tmp_path_factory.mktemp("jpeg_host") / "jpeg_host_check"
-    src = os.path.join(ROOT, "dvd_amd", "csrc", "jpeg_host_check.cpp")
-    subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", src, "-o",
-                    str(exe)], check=True)
-    return exe
+    return build_host_check("jpeg", tmp_path_factory.mktemp("jpeg_host"))
 
 
 def _host_encode(exe, img, quality, subsampling, tmp_path):

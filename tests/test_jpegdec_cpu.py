@@ -16,6 +16,7 @@ from PIL import Image
 
 import jpeg_model as J
 import jpegdec_model as M
+from host_check import build_host_check
 from dvd_amd import lib, ops
 
 ROOT = J.ROOT
@@ -87,11 +88,7 @@ def test_fixpoint_synchronises_within_64_iterations():
 # ---- 2. the CPU restatement of the kernels' arithmetic, under AddressSanitizer and UBSan --------------------------------------
 @pytest.fixture(scope="module")
 def host_check(tmp_path_factory):
-    exe = tmp_path_factory.mktemp("jpegdec_host") / "jpegdec_host_check"
-    src = os.path.join(ROOT, "dvd_amd", "csrc", "jpegdec_host_check.cpp")
-    subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", src, "-o",
-                    str(exe)], check=True)
-    return exe
+    return build_host_check("jpegdec", tmp_path_factory.mktemp("jpegdec_host"))
 
 
 def _host_decode(exe, data, tmp_path, max_iters=None):

@@ -9,6 +9,7 @@ import pytest
 import torch
 
 import png_model as P
+from host_check import build_host_check
 from dvd_amd import lib, ops
 
 ROOT = P.ROOT
@@ -152,11 +153,7 @@ def test_pil_route_writes_image_save_bytes(tmp_path, monkeypatch):
 def host_check(tmp_path_factory):
     """dvd_amd/csrc/png_host_check.cpp: png.hip's filter, segment compressor, bit writer, layout and CRC tree on the shared
     png_core.h, as a stand-alone program with exact-size buffers."""
-    exe = tmp_path_factory.mktemp("png_host") / "png_host_check"
-    src = os.path.join(ROOT, "dvd_amd", "csrc", "png_host_check.cpp")
-    subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", src, "-o",
-                    str(exe)], check=True)
-    return exe
+    return build_host_check("png", tmp_path_factory.mktemp("png_host"))
 
 
 def _host_encode(exe, img, tmp_path):

@@ -15,6 +15,7 @@ import torch
 
 import png_dyn_model as D
 import png_model as P
+from host_check import build_host_check
 from dvd_amd import lib, ops
 
 ROOT = P.ROOT
@@ -23,11 +24,7 @@ S = D.S
 
 @pytest.fixture(scope="module")
 def host_check(tmp_path_factory):
-    exe = tmp_path_factory.mktemp("png_dyn_host") / "png_host_check"
-    src = os.path.join(ROOT, "dvd_amd", "csrc", "png_host_check.cpp")
-    subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", src, "-o",
-                    str(exe)], check=True)
-    return exe
+    return build_host_check("png", tmp_path_factory.mktemp("png_dyn_host"))
 
 
 def _lengths(exe, freq, limit):
@@ -114,7 +111,7 @@ def files(host_check, tmp_path_factory):
     """name -> (fixed-mode file in the five-argument form, dynamic-mode file), each encoded once."""
     tmp = tmp_path_factory.mktemp("png_dyn_files")
     return {name: (_host_encode(host_check, D.case(name), tmp), _host_encode(host_check, D.case(name), tmp, "dynamic"))
-            for name in D.CASES}
+            for name in D.DIGEST_CASES}
 
 
 def _digest(data):
@@ -130,7 +127,7 @@ def test_both_routes_reproduce_their_digests(files):
     """png_fixed_digests.json was written by the host program as it was BEFORE the token sink and the dynamic route, in its
     five-argument form: the fixed route's bytes have not moved.  png_dynamic_digests.json holds this program's dynamic files;
     tests/test_gpu_png_dyn.py holds the kernels to the same table."""
-    assert set(_golden("fixed")) == set(_golden("dynamic")) == set(D.CASES)
+    assert set(_golden("fixed")) == set(_golden("dynamic")) == set(D.DIGEST_CASES)
     assert {n: _digest(f[0]) for n, f in files.items()} == _golden("fixed")
     assert {n: _digest(f[1]) for n, f in files.items()} == _golden("dynamic")
 

@@ -13,6 +13,7 @@ import pytest
 import torch
 
 import sflow_model as M
+from host_check import build_host_check
 from dvd_amd import lib, ops
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
@@ -84,11 +85,7 @@ def test_model_pieces():
 # ---- 3. the CPU restatement of the kernels' arithmetic, under AddressSanitizer and UBSan --------------------------------------
 @pytest.fixture(scope="module")
 def host_check(tmp_path_factory):
-    exe = tmp_path_factory.mktemp("sflow_host") / "sflow_host_check"
-    src = os.path.join(ROOT, "dvd_amd", "csrc", "sflow_host_check.cpp")
-    subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", src, "-o",
-                    str(exe)], check=True)
-    return exe
+    return build_host_check("sflow", tmp_path_factory.mktemp("sflow_host"))
 
 
 def _host_run(exe, a, b, tmp_path, **kw):
