@@ -79,6 +79,10 @@ _DEFAULTS = {
     # the device) | 'hip' (a .jpg/.jpeg FILE crosses and ops.jpeg_decode makes the same bytes there; a file the device decoder
     # does not cover, and every other format, is decoded by PIL with one log line naming the reason - DESIGN.md 4.6)
     "image_decoder": "pil",
+    # who decodes PNG files - the .png photographs of the image-directory path and the ground-truth scans of gt_dir: 'pil' (on
+    # the CPU, the pixels cross to the device) | 'hip' (the FILE crosses and ops.png_decode inflates and unfilters it there:
+    # the same bytes; a file the device decoder hands back is decoded by PIL with one log line naming the reason - DESIGN.md 4.9)
+    "png_decoder": "pil",
     "num_synthetic_docs": 4,
     "full_res": (1024, 768), # synthetic full-resolution source size (H, W)
     "conditioning_dir": "",   # directory of per-document conditioning .npz files (skips ingest + pre-stage nets)

@@ -18,7 +18,10 @@ With `decode='hip'` (env.image_decoder) a `.jpg` / `.jpeg` item is not decoded h
     path              str
 
 and `dvd_amd.evaluation.decode_documents` makes the same RGB bytes on the device (ops.decode_image: the HIP JPEG decoder,
-or PIL for a file it does not cover).  Other extensions behave as with 'pil'."""
+or PIL for a file it does not cover).  Other extensions behave as with 'pil'.
+
+`decode_png='hip'` (env.png_decoder) does the same for `.png` items, whatever `decode` says: they carry `file_bytes` + `path`
+and the HIP PNG decoder makes the pixels.  `decode='hip'` alone leaves `.png` items as they are."""
 from __future__ import annotations
 
 import os
@@ -31,9 +34,12 @@ _IMAGE_EXTS = (".jpg", ".jpeg", ".png", ".bmp", ".tif", ".tiff", ".webp")
 
 
 class Doc_benchmark(Dataset):
-    def __init__(self, data_root, input_transform, decode="pil") -> None:
+    def __init__(self, data_root, input_transform, decode="pil", decode_png="pil") -> None:
         if decode not in ("pil", "hip"):
             raise ValueError(f"Doc_benchmark: decode must be 'pil' or 'hip', got {decode!r}")
+        if decode_png not in ("pil", "hip"):
+            raise ValueError(f"Doc_benchmark: decode_png must be 'pil' or 'hip', got {decode_png!r}")
+        self.decode_png = decode_png
         self.data_root = data_root
         self.input_transform = input_transform
         self.decode = decode
@@ -54,7 +60,9 @@ class Doc_benchmark(Dataset):
 
     def __getitem__(self, idx):
         sample_path = os.path.join(self.data_root, self.data_paths[idx])
-        if self.decode == "hip" and sample_path.lower().endswith(_JPEG_EXTS):
+        as_file = (self.decode == "hip" and sample_path.lower().endswith(_JPEG_EXTS)) or \
+                  (self.decode_png == "hip" and sample_path.lower().endswith(".png"))
+        if as_file:
             import torch
             return {"file_bytes": torch.from_numpy(np.fromfile(sample_path, dtype=np.uint8)), "path": sample_path}
         img_ori = self.load_rgb_u8(sample_path)

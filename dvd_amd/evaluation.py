@@ -66,23 +66,24 @@ def npz_documents(settings, indices, files):
         yield d
 
 
-def decode_documents(batch, device, log=None):
-    """Documents that arrive as FILES (`file_bytes`: the 1-D uint8 tensor a Doc_benchmark(decode='hip') item carries) get
-    `image_u8` [H,W,3] uint8 on the device - the bytes PIL's decode of the file gives, EXIF orientation applied - and
-    `decode_route` ('hip' | 'pil': ops.decode_image).  Other documents pass through untouched."""
+def decode_documents(batch, device, log=None, png=False):
+    """Documents that arrive as FILES (`file_bytes`: the 1-D uint8 tensor a Doc_benchmark(decode='hip') or
+    Doc_benchmark(decode_png='hip') item carries) get `image_u8` [H,W,3] uint8 on the device - the bytes PIL's decode of the
+    file gives, EXIF orientation applied - and `decode_route` ('hip' | 'pil': ops.decode_image).  png (env.png_decoder ==
+    'hip'): PNG files go to the device's PNG decoder.  Other documents pass through untouched."""
     for d in batch:
         if "file_bytes" in d and "image_u8" not in d and "y512" not in d:
-            d["image_u8"], d["decode_route"] = ops.decode_image(d.pop("file_bytes"), device, log=log)
+            d["image_u8"], d["decode_route"] = ops.decode_image(d.pop("file_bytes"), device, log=log, png=png)
 
 
-def prepare_conditioning(batch, device, grid, prestage_models, use_init_flow=False):
+def prepare_conditioning(batch, device, grid, prestage_models, use_init_flow=False, decode_png=False):
     """Documents given as decoded images: ingest (cv2.resize to 512^2, / 255; doc_benchmark.py:84-88) and the pre-stage
     nets (evaluation.py:162-216) fill in y512 / mask_cat / mask_y512 / line_msk / src_u8 as DEVICE tensors.  Documents
     that already carry their conditioning tensors (synthetic ones with env.use_prestage_nets=False, .npz files of
     env.conditioning_dir) pass through untouched and need no pre-stage nets.  use_init_flow: every document also gets
     `init_flow` [2,G,G] from GeoTr (evaluation.py:172-178), in the same pre-stage pass when that runs."""
     from . import prestage
-    decode_documents(batch, device)
+    decode_documents(batch, device, png=decode_png)
     need_ingest = [d for d in batch if "image_u8" in d and "y512" not in d]
     imgs = [(d["image_u8"] if th.is_tensor(d["image_u8"]) else th.from_numpy(d["image_u8"])).to(device).contiguous()
             for d in need_ingest]
@@ -190,6 +191,15 @@ def parse_gt_metrics(value):
     return tuple(m for m in GT_METRICS if m in names)
 
 
+def png_decoder_setting(env):
+    """env.png_decoder 'pil' | 'hip': who decodes PNG files (input photographs and ground-truth scans).  Anything else is a
+    ValueError."""
+    value = getattr(env, "png_decoder", "pil")
+    if value not in ("pil", "hip"):
+        raise ValueError(f"env.png_decoder must be 'pil' or 'hip', got {value!r}")
+    return value
+
+
 def _score_against_gt(settings, logger, path, out, device, metrics=("ms_ssim",)):
     """The metrics of one dewarped page (uint8 [H,W,3] on the device) against its ground-truth scan, if there is one: MS-SSIM,
     LD and / or AD, on planes prepared once."""
@@ -198,7 +208,19 @@ def _score_against_gt(settings, logger, path, out, device, metrics=("ms_ssim",))
     if gt_file is None:
         logger.info(f"{path} {','.join(metrics)} skipped: no ground truth in {settings.env.gt_dir}")
         return
-    gt = th.from_numpy(np.ascontiguousarray(np.asarray(Image.open(gt_file).convert("RGB")))).to(device)
+    gt = None
+    if png_decoder_setting(settings.env) == "hip":
+        # the scan is inflated and unfiltered on the device; a file the decoder hands back (or one that is no PNG) takes
+        # the host route below, untouched, so that the scores are the same bits either way
+        with open(gt_file, "rb") as f:
+            data = f.read()
+        if data[:8] == ops.PNG_SIGNATURE:
+            try:
+                gt = ops.png_decode(data, device)
+            except ops.PngUnsupported as e:
+                logger.info(f"{gt_file}: decoded by PIL, not on the device: {e}")
+    if gt is None:
+        gt = th.from_numpy(np.ascontiguousarray(np.asarray(Image.open(gt_file).convert("RGB")))).to(device)
     values = ops.gt_metrics_u8(out.contiguous(), gt, metrics, preset=getattr(settings.env, "metric_preset", "docunet"))
     for name in metrics:
         logger.info(f"{path} {name} {values[name]:.6f}")
@@ -217,6 +239,8 @@ def run_evaluation_docunet(settings, logger, val_loader, diffusion, model, pretr
     warped_<stem>.jpg with the HIP JPEG encoder instead, at env.jpeg_quality and env.jpeg_subsampling).
     env.image_decoder 'pil' | 'hip' says who decodes the input photograph: the loader (PIL), or - for items that carry the JPEG
     file as `file_bytes` - the HIP decoder on the device (`decode_documents`; the same bytes either way).
+    env.png_decoder 'pil' | 'hip' says the same for PNG files: `.png` items that carry the file, and the ground-truth scans of
+    env.gt_dir, are decoded by the HIP PNG decoder; a file it hands back goes to PIL.
     The pre-stage models may all be None when every document carries ready conditioning tensors.
     With env.gt_dir set, every dewarped page is scored against `<gt_dir>/<stem>.png` (`gt_candidates`) with MS-SSIM
     (ops.ms_ssim_u8, env.metric_preset): logged per document and as a mean, written to ms_ssim.txt beside the pictures and
@@ -239,6 +263,7 @@ def run_evaluation_docunet(settings, logger, val_loader, diffusion, model, pretr
     image_decoder = getattr(env, "image_decoder", "pil")        # who decodes the input photograph: the loader reads it
     if image_decoder not in ("pil", "hip"):
         raise ValueError(f"env.image_decoder must be 'pil' or 'hip', got {image_decoder!r}")
+    png_decoder = png_decoder_setting(env)                      # who decodes PNG files: the loader and the scoring read it
     gt_metrics = parse_gt_metrics(getattr(env, "gt_metrics", "ms_ssim"))       # what env.gt_dir scores
     gt_ad = getattr(env, "gt_ad", False)                        # ... and whether it scores AD as well
     if not isinstance(gt_ad, bool):
@@ -273,7 +298,7 @@ def run_evaluation_docunet(settings, logger, val_loader, diffusion, model, pretr
                 elif "y512" not in d:
                     raise ValueError(f"{d['path']}: no 'source_image' and a non-integer 'source_image_ori' to make it from")
         use_init_flow = bool(getattr(env, "use_init_flow", False))
-        prepare_conditioning(batch, device, G, prestage_models, use_init_flow)
+        prepare_conditioning(batch, device, G, prestage_models, use_init_flow, decode_png=png_decoder == "hip")
         t0 = time.time()
         src, msk, seg, line = stack("y512"), stack("mask_cat"), stack("mask_y512"), stack("line_msk")
         init_flow = stack("init_flow") if use_init_flow else th.zeros(nb, 2, G, G, device=device)       # :176-181

@@ -102,6 +102,23 @@ JPEG_DECODE_CODES = {-20: "HEADER", -21: "PROGRESSIVE", -22: "EXTENDED", -23: "L
                      -33: "ORIENTATION", -34: "NOSYNC", -35: "DATA"}
 JPEGDEC_SUBSEQ = 128   # DVD_JPEGDEC_SUBSEQ: bytes of the scan per lane of the entropy decoder
 
+
+class PngDecInfo(C.Structure):
+    """dvd_pngdec_info: what dvd_pngdec_probe reads from a PNG file's chunks."""
+    _fields_ = [("h", C.c_int), ("w", C.c_int), ("colour_type", C.c_int), ("bpp", C.c_int), ("idat_chunks", C.c_long),
+                ("payload_bytes", C.c_long), ("scratch_bytes", C.c_long)]
+
+
+class PngDecStats(C.Structure):
+    """dvd_pngdec_stats: what a decode ran."""
+    _fields_ = [("candidates", C.c_int), ("segments", C.c_int), ("rounds", C.c_int), ("bands", C.c_int)]
+
+
+# DVD_E_PNG_*: why the PNG decoder hands a file back (a refusal on the host, or DATA / NOSPLIT after the inflate ran)
+PNG_DECODE_CODES = {-36: "HEADER", -37: "INTERLACE", -38: "DEPTH", -39: "COLOUR", -40: "TRNS", -41: "APNG", -42: "METADATA",
+                    -43: "ZLIB", -44: "SIZE", -45: "DATA", -46: "NOSPLIT"}
+PNG_SIGNATURE = b"\x89PNG\r\n\x1a\n"
+
 class SflowParams(C.Structure):
     """dvd_sflow_params: the parameters of the SIFT-flow chain, ten ints in this order."""
     _fields_ = [(name, C.c_int) for name in ("levels", "w_top", "w", "iters_top", "iters", "alpha", "d", "gamma", "T", "eps")]
@@ -205,6 +222,8 @@ SIGNATURES = {
     "dvd_jpeg_encode_rgb8": [c_void, C.c_int, C.c_int, C.c_int, C.c_int, c_void, C.c_long, c_void, c_void, c_void],
     "dvd_jpegdec_probe": [c_void, C.c_long, C.POINTER(JpegDecInfo)],
     "dvd_jpeg_decode_rgb8": [c_void, c_void, C.c_long, c_void, C.c_long, C.c_int, C.POINTER(C.c_int), c_void, c_void],
+    "dvd_pngdec_probe": [c_void, C.c_long, C.POINTER(PngDecInfo)],
+    "dvd_png_decode_rgb8": [c_void, c_void, C.c_long, c_void, C.c_long, C.c_long, C.POINTER(PngDecStats), c_void, c_void],
     "dvd_dither_f16": [c_void, c_void, c_void, C.c_long, C.c_uint, C.c_uint, c_void],
     "dvd_engine_create": [C.c_int, C.c_int, C.c_int, C.POINTER(c_void)],
     "dvd_engine_destroy": [c_void],

@@ -672,11 +672,91 @@ def pil_decode_rgb8(path_or_bytes) -> np.ndarray:
     return np.array(im.convert("RGB"), dtype=np.uint8)       # a writable, contiguous copy
 
 
-def decode_image(path_or_bytes, device=None, max_iters: int = None, log=None):
+# ---- PNG decoder for input photographs and ground-truth scans (dvd_amd/csrc/pngdec.hip; definition: DESIGN.md 4.9) ------------
+PNG_SIGNATURE = lib.PNG_SIGNATURE
+
+
+class PngUnsupported(ValueError):
+    """The device decoder hands the file back: a refusal of the host-side chunk check (interlace, palette, tRNS, ...), or
+    DATA / NOSPLIT after the inflate ran.  `code` is the name of the library's DVD_E_PNG_* code.  A normal outcome:
+    decode_image(png=True) falls back to PIL."""
+
+    def __init__(self, code: str, message: str):
+        super().__init__(f"{code}: {message}")
+        self.code = code
+
+
+def _png_status(name, rc):
+    if rc == 0:
+        return
+    message = lib.raw().dvd_last_error().decode()
+    if rc in lib.PNG_DECODE_CODES:
+        raise PngUnsupported(lib.PNG_DECODE_CODES[rc], message)
+    raise lib.DvdError(f"{name} failed ({rc}): {message}")
+
+
+def _png_probe(host, name):
+    info = lib.PngDecInfo()
+    _png_status(name, lib.raw().dvd_pngdec_probe(C.c_void_p(host.ctypes.data), host.size, C.byref(info)))
+    return info
+
+
+def png_probe(data) -> dict:
+    """What the decoder reads from the chunks of a PNG file (bytes or a 1-D uint8 tensor), on the host: h, w, colour_type,
+    bpp, idat_chunks, payload_bytes, scratch_bytes.  Raises PngUnsupported for a file the device decoder refuses."""
+    info = _png_probe(_jpeg_file(data, "png_probe")[0], "png_probe")
+    return {k: int(getattr(info, k)) for k, _ in lib.PngDecInfo._fields_}
+
+
+def png_decode(data, device=None, max_work: int = None, scratch: torch.Tensor = None, out: torch.Tensor = None,
+               return_stats: bool = False):
+    """A PNG file (bytes or a 1-D uint8 tensor, on the host or already on the device) -> [H,W,3] uint8 RGB on the device:
+    the bytes ImageOps.exif_transpose(Image.open(f)).convert("RGB") gives.  Only the file crosses to the device.
+    max_work caps the symbols + stored bytes one lane of the inflate may spend (None: the library's 2^20).
+    scratch (optional): a uint8 device buffer of at least png_probe(data)['scratch_bytes'] bytes to reuse between calls.
+    out (optional): a contiguous uint8 device tensor of >= 3 H W elements, at any byte address, to decode into.
+    return_stats: also return {'candidates', 'segments', 'rounds', 'bands'}.  Raises PngUnsupported (a ValueError) for a
+    file the decoder refuses, for 'DATA' (damaged data, a checksum mismatch) and for 'NOSPLIT' (max_work reached); `out` is
+    untouched then.  The call synchronises its stream (dvd_hip.h says where)."""
+    host, dev_file = _jpeg_file(data, "png_decode")
+    if max_work is not None and (isinstance(max_work, bool) or not isinstance(max_work, (int, np.integer)) or max_work < 1):
+        raise ValueError(f"png_decode: max_work must be a positive integer or None, got {max_work!r}")
+    info = _png_probe(host, "png_decode")
+    if dev_file is None:
+        dev_file = torch.from_numpy(host).to(torch.device("cuda") if device is None else device)
+    elif device is not None and torch.device(device) != dev_file.device:
+        dev_file = dev_file.to(device)
+    dev = dev_file.device
+    _chk(dev_file, torch.uint8, "file")
+    need, numel = int(info.scratch_bytes), 3 * info.h * info.w
+    scratch = _scratch(scratch, need, dev, "png_decode")
+    if out is None:
+        out = torch.empty(numel, dtype=torch.uint8, device=dev)
+    elif out.dtype != torch.uint8 or not out.is_contiguous() or out.numel() < numel or out.device != dev:
+        raise ValueError(f"png_decode: out must be a contiguous uint8 tensor of >= {numel} elements on {dev}")
+    stats = lib.PngDecStats()
+    with torch.cuda.device(dev):
+        rc = lib.raw().dvd_png_decode_rgb8(C.c_void_p(host.ctypes.data), ptr(dev_file), host.size, ptr(out), out.numel(),
+                                           0 if max_work is None else int(max_work), C.byref(stats), ptr(scratch), stream_ptr())
+    _png_status("dvd_png_decode_rgb8", rc)
+    img = out.view(-1)[:numel].view(info.h, info.w, 3)
+    if return_stats:
+        return img, {k: int(getattr(stats, k)) for k, _ in lib.PngDecStats._fields_}
+    return img
+
+
+def png_decode_from_file(path: str, device=None, max_work: int = None) -> torch.Tensor:
+    """Read `path` and decode it on the device (png_decode)."""
+    with open(path, "rb") as f:
+        return png_decode(f.read(), device=device, max_work=max_work)
+
+
+def decode_image(path_or_bytes, device=None, max_iters: int = None, log=None, png: bool = False):
     """An image file (a path, bytes or a 1-D uint8 tensor) -> ([H,W,3] uint8 RGB on the device, the route that ran): 'hip'
     = the device decoder, 'pil' = PIL on the host plus an upload of the pixels, for every file the device decoder hands back
-    (JpegUnsupported) - with ONE line to `log` (default: dvd_amd.logger.info) that names the reason.  The pixels are the
-    same on both routes."""
+    (JpegUnsupported / PngUnsupported) - with ONE line to `log` (default: dvd_amd.logger.info) that names the reason.  The
+    pixels are the same on both routes.  png=True sends a file that starts with the PNG signature to png_decode; by default
+    only the JPEG decoder is tried (which hands a PNG file back as 'HEADER')."""
     if isinstance(path_or_bytes, (str, os.PathLike)):
         with open(path_or_bytes, "rb") as f:
             data, what = f.read(), str(path_or_bytes)
@@ -684,8 +764,10 @@ def decode_image(path_or_bytes, device=None, max_iters: int = None, log=None):
         data = path_or_bytes.cpu().numpy().tobytes() if torch.is_tensor(path_or_bytes) else bytes(path_or_bytes)
         what = f"<{len(data)} bytes>"
     try:
+        if png and data[:8] == PNG_SIGNATURE:
+            return png_decode(data, device=device), "hip"
         return jpeg_decode(data, device=device, max_iters=max_iters), "hip"
-    except JpegUnsupported as e:
+    except (JpegUnsupported, PngUnsupported) as e:
         if log is None:
             from . import logger
             log = logger.info

@@ -79,7 +79,8 @@ def run(settings):
         # the workers only decode (PIL); uint8 CHW crosses PCIe (the reference ships float32: get_float=True), the
         # resize to 512 x 512 and everything after it runs on the GPU.  Unshuffled: rank r owns files r, r+world, ...
         test_set = datasets.Doc_benchmark(env.eval_dataset, ArrayToTensor(get_float=False),
-                                          decode=getattr(env, "image_decoder", "pil"))
+                                          decode=getattr(env, "image_decoder", "pil"),
+                                          decode_png=getattr(env, "png_decoder", "pil"))
         mine = dist_util.shard_documents(len(test_set))
         documents = DataLoader(Subset(test_set, list(mine)), batch_size=1, shuffle=False, drop_last=False,
                                num_workers=int(getattr(env, "num_workers", 0)))

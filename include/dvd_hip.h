@@ -604,6 +604,55 @@ int dvd_jpeg_decode_rgb8(const uint8_t* file_host, const uint8_t* file_dev, long
                          int max_iters, int* iters_out, void* scratch, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * PNG decoder for input photographs and ground-truth scans: the FILE goes to the device, the [H,W,3] u8 RGB page is made
+ * there - DESIGN.md 4.9.  Integer work throughout: byte for byte what
+ * ImageOps.exif_transpose(Image.open(f)).convert("RGB") returns for an accepted file.
+ * Accepted: bit depth 8, colour type 0 (gray, replicated), 2 (RGB) or 6 (RGBA, alpha dropped), no interlace, one or more
+ * consecutive IDAT chunks of any lengths, a zlib header with CM = 8 and no preset dictionary, IEND; other ancillary chunks
+ * are skipped.  Everything else is REFUSED on the host with one of the codes below before anything is launched; DATA and
+ * NOSPLIT are found on the device and leave the output untouched.  A refusal is a normal outcome (the caller decodes on
+ * the CPU).
+ * ---------------------------------------------------------------------------------------- */
+#define DVD_E_PNG_HEADER (-36)     /* no signature, a truncated or malformed chunk layout, a bad IHDR */
+#define DVD_E_PNG_INTERLACE (-37)  /* Adam7 */
+#define DVD_E_PNG_DEPTH (-38)      /* bit depth other than 8 */
+#define DVD_E_PNG_COLOUR (-39)     /* colour type 3 (palette) or 4 (gray + alpha) */
+#define DVD_E_PNG_TRNS (-40)       /* a tRNS chunk */
+#define DVD_E_PNG_APNG (-41)       /* an acTL chunk */
+#define DVD_E_PNG_METADATA (-42)   /* eXIf, or a text chunk "Raw profile type..." / "XML:com.adobe.xmp": an orientation may hide there */
+#define DVD_E_PNG_ZLIB (-43)       /* a bad zlib header or a preset dictionary */
+#define DVD_E_PNG_SIZE (-44)       /* 3 h w >= 2^31, or 2^29 bytes of IDAT data */
+#define DVD_E_PNG_DATA (-45)       /* an invalid block, code, length or distance; a wrong inflated length; a filter byte above 4;
+                                      an Adler-32 or IDAT CRC-32 mismatch */
+#define DVD_E_PNG_NOSPLIT (-46)    /* a lane of the inflate exceeded max_work (a long stream of fixed or stored blocks) */
+typedef struct dvd_pngdec_info {
+  int h, w;                /* as in IHDR */
+  int colour_type;         /* 0, 2 or 6 */
+  int bpp;                 /* bytes per pixel in the file: 1, 3 or 4 */
+  long idat_chunks;        /* IDAT chunks, empty ones included */
+  long payload_bytes;      /* their data together: zlib header, deflate stream, Adler-32 */
+  long scratch_bytes;      /* device bytes dvd_png_decode_rgb8 needs */
+} dvd_pngdec_info;
+typedef struct dvd_pngdec_stats {
+  int candidates;          /* block starts the finder kept, segment 0 included */
+  int segments;            /* those of them on the chain from segment 0 */
+  int rounds;              /* pointer-doubling rounds, the last one (which changed nothing) included */
+  int bands;               /* runs of rows the unfilter handles independently */
+} dvd_pngdec_stats;
+/* Host only: parses the n bytes of the file at file_host; 0 and *info, or the refusal code (dvd_last_error says why). */
+int dvd_pngdec_probe(const uint8_t* file_host, long n, dvd_pngdec_info* info);
+/* file_host / file_dev: the same n bytes on the host (parsed there) and on the device.  out_hwc [h,w,3] u8, any byte
+ * alignment; cap = bytes writable at it: cap < 3 h w is DVD_E_ARG.  Every bad argument and every header refusal is decided
+ * before anything is launched.  scratch: info.scratch_bytes device bytes, 16-byte aligned; its contents do not matter.
+ * max_work >= 1 (0 = the default, 2^20) is the symbols + stored bytes one lane of the inflate may spend.  *stats_out (host,
+ * may be null) receives what ran.  SYNCHRONISES `stream`: after the block finder (the candidate count), after the count
+ * pass (the candidate table), after every 4 doubling rounds (4 bytes) and once before the unfilter (the status word: both
+ * checksums, the filter bytes, the band count).  Returns 0, a refusal code, DVD_E_PNG_DATA or DVD_E_PNG_NOSPLIT (out_hwc is
+ * untouched then), DVD_E_ARG or DVD_E_LAUNCH. */
+int dvd_png_decode_rgb8(const uint8_t* file_host, const uint8_t* file_dev, long n, uint8_t* out_hwc, long cap,
+                        long max_work, dvd_pngdec_stats* stats_out, void* scratch, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Local distortion (LD) of the evaluation tail: the mean length of a dense SIFT-flow field from the flat ground-truth scan
  * A to the dewarped page B, on the device where both planes already lie.  The reference leaves it to offline MATLAB and
  * Ce Liu's mex code; the definition is this project's own (integer statement: tests/sflow_model.py), written
