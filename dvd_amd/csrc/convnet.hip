@@ -31,6 +31,7 @@ struct ConvNet {
   std::vector<CnSlot> slots;
   std::vector<int> kpad;       // per op (conv only): padded K
   std::vector<int> ksplit;     // per op (conv only): K slices (1 = none)
+  std::vector<int> path;       // per op: DVD_CN_PATH_* - the route convnet_run takes, decided ONCE in convnet_create
   size_t part_off = 0, part_bytes = 0;   // split-K partial sums
   size_t col_off = 0, col_bytes = 0, need_bytes = 0;
   long weight_floats = 0;
@@ -415,6 +416,7 @@ extern "C" int dvd_convnet_create_batched(const dvd_cn_op* ops, int n_ops, int n
   n->slots.resize(n_slots);
   n->kpad.assign(n_ops, 0);
   n->ksplit.assign(n_ops, 1);
+  n->path.assign(n_ops, DVD_CN_PATH_NONE);
   size_t partmax = 0;
   n->in_c = in_c; n->in_h = in_h; n->in_w = in_w;
   n->slots[0].h = in_h; n->slots[0].w = in_w; n->slots[0].c = in_c; n->slots[0].set = true;
@@ -457,6 +459,7 @@ extern "C" int dvd_convnet_create_batched(const dvd_cn_op* ops, int n_ops, int n
           const int pad = o.dil * (o.ks / 2), span = o.dil * (o.ks - 1);
           d.h = (a.h + 2 * pad - span - 1) / 2 + 1; d.w = (a.w + 2 * pad - span - 1) / 2 + 1;
           if (d.h < 1 || d.w < 1) return fail("strided conv of a too small map", i);
+          n->path[i] = DVD_CN_PATH_STRIDED;
           colmax = std::max(colmax, nb * d.h * d.w * kp * 4);
         } else {
           // Small maps with wide channels (the UNet's deep layers: 324 ... 1296 pixels, K up to 9216) give the 128 x 128
@@ -471,14 +474,29 @@ extern "C" int dvd_convnet_create_batched(const dvd_cn_op* ops, int n_ops, int n
               if (units % c == 0 && kp / c >= 128) S = c;
           }
           n->ksplit[i] = S;
-          if (S > 1) partmax = std::max(partmax, nb * S * a.h * a.w * o.cout * 4);
-          // the im2col matrix is sized only for the convs that write one (the same two predicates convnet_run takes the
-          // implicit-GEMM kernel / the direct 1x1 read on): the 16 -> 64-channel 3x3 convs at full resolution would
-          // otherwise reserve 382 MB per image that nothing ever touches
+          // The route, in the order of preference: the narrow implicit kernel (no im2col matrix), the wide implicit GEMM
+          // (gathers its A tiles from the maps), the direct read of a 1x1 conv's single 16-aligned source, and for the
+          // rest the gather into the im2col matrix.  convnet_run switches on what is stored here, and the two workspace
+          // regions below are sized from it, so what a kernel writes and what was reserved for it cannot disagree.
           const int cb = o.b >= 0 ? n->slots[o.b].c : 0;
-          const bool implicit = o.cout <= 64 && a.c % 8 == 0 && cb % 8 == 0 && (a.c + cb) % 16 == 0 && S == 1;
-          const bool direct = o.ks == 1 && o.b < 0 && a.c == kp;
-          if (!implicit && !direct) colmax = std::max(colmax, nb * a.h * a.w * kp * 4);
+          const long rows = (long)nb * a.h * a.w;
+          int path;
+          if (o.cout <= 64 && a.c % 8 == 0 && cb % 8 == 0 && (a.c + cb) % 16 == 0 && S == 1)
+            // one 32-column tile per wave; a 33..64-channel layer on a small map gets its two tiles from two workgroups
+            // (twice the waves on a chip that is mostly idle there; per output the same chain of MFMAs: same bits)
+            path = o.cout <= 32 ? DVD_CN_PATH_NARROW1 : rows < NARROW_SPLIT_ROWS ? DVD_CN_PATH_NARROW1X2 : DVD_CN_PATH_NARROW2;
+          else if (a.c % 16 == 0 && cb % 16 == 0 && kp == o.ks * o.ks * (a.c + cb) && S == 1 && rows < (1l << 31) &&
+                   !(o.ks == 1 && o.b < 0))
+            path = DVD_CN_PATH_WIDE;
+          else if (o.ks == 1 && o.b < 0 && a.c == kp)
+            path = DVD_CN_PATH_DIRECT;
+          else
+            path = DVD_CN_PATH_GATHER;
+          n->path[i] = path;
+          if (S > 1) partmax = std::max(partmax, nb * S * a.h * a.w * o.cout * 4);
+          // the im2col matrix is sized only for the convs that write one: the 16 -> 64-channel 3x3 convs at full
+          // resolution would otherwise reserve 382 MB per image that nothing ever touches
+          if (path == DVD_CN_PATH_GATHER) colmax = std::max(colmax, nb * a.h * a.w * kp * 4);
         }
         break;
       }
@@ -535,6 +553,14 @@ extern "C" int dvd_convnet_slot_shape(void* handle, int slot, int* h, int* w, in
   return DVD_OK;
 }
 
+extern "C" int dvd_convnet_op_info(void* handle, int op, int* path, int* ksplit) {
+  DVD_REQUIRE(handle && path && ksplit, "convnet_op_info: null pointer");
+  ConvNet* n = (ConvNet*)handle;
+  DVD_REQUIRE(op >= 0 && op < (int)n->ops.size(), "convnet_op_info: op %d out of range", op);
+  *path = n->path[op]; *ksplit = n->ksplit[op];
+  return DVD_OK;
+}
+
 extern "C" int dvd_conv3x3_nhwc(const float* in, int c, const float* wgt, int kp, const float* bias, float* out, int cout,
                                 int h, int w, int relu, void* stream) {
   DVD_REQUIRE(in && wgt && bias && out, "conv3x3_nhwc: null pointer");
@@ -581,72 +607,56 @@ extern "C" int dvd_convnet_run(void* handle, const float* in_nchw, const float* 
       case DVD_CN_CONV: {
         const int kp = n->kpad[i];
         const int cb = o.b >= 0 ? n->slots[o.b].c : 0;
-        if (o.flag == 2) {                  // stride 2: gather the output pixels' windows, then the exact-f32 GEMM
-          const long orows = B * d.h * d.w, total4 = orows * (kp / 4);
-          im2col_cat_kernel<<<cdiv(total4, 256), 256, 0, st>>>(P(o.a), a.c, nullptr, 0, col, kp, o.ks, o.dil, a.h, a.w, 2,
-                                                              d.h, d.w, total4);
-          dvd_gemm_desc g;
-          memset(&g, 0, sizeof(g));
-          DVD_REQUIRE(orows < (1l << 31), "convnet_run: batch too large for one GEMM");
-          g.dtype = 1; g.M = (int)orows; g.N = o.cout; g.K = kp; g.batch = 1;
-          g.A = col; g.lda = kp; g.B = weights + o.w_off; g.ldb = kp;
-          g.C32 = P(o.dst); g.ldc = o.cout;
-          g.bias = weights + o.w_off + (long)o.cout * kp; g.act = o.act;
-          g.lo_scale = 1.f;
-          if (int e = dvd_gemm_nt(&g, stream)) return e;
-          break;
-        }
-        if (o.cout <= 64 && a.c % 8 == 0 && cb % 8 == 0 && (a.c + cb) % 16 == 0 && n->ksplit[i] == 1) {
+        const int path = n->path[i], S = n->ksplit[i];
+        const float* wgt = weights + o.w_off;
+        const float* bias = wgt + (long)o.cout * kp;
+        const float* pb = o.b >= 0 ? P(o.b) : nullptr;
+        if (path == DVD_CN_PATH_NARROW1 || path == DVD_CN_PATH_NARROW1X2 || path == DVD_CN_PATH_NARROW2) {
           // narrow output over 16-aligned channels: implicit GEMM, no im2col matrix
           const dim3 grd(cdiv(rows, 128));
-          const float* wgt = weights + o.w_off;
-          if (o.cout <= 32 || rows < NARROW_SPLIT_ROWS)
-            // one 32-column tile per wave; a 33..64-channel layer on a small map gets its two tiles from two workgroups
-            // (twice the waves on a chip that is mostly idle there; per output the same chain of MFMAs: same bits)
-            conv_f32_narrow_kernel<1><<<dim3(grd.x, o.cout <= 32 ? 1 : 2), 256, narrow_lds(), st>>>(P(o.a), a.c, o.b >= 0 ? P(o.b) : nullptr, cb, wgt, kp,
-                                                           wgt + (long)o.cout * kp, P(o.dst), o.cout, o.ks, o.dil, a.h, a.w,
-                                                           o.act, rows);
+          if (path == DVD_CN_PATH_NARROW2)
+            conv_f32_narrow_kernel<2><<<grd, 256, narrow_lds(), st>>>(P(o.a), a.c, pb, cb, wgt, kp, bias, P(o.dst), o.cout, o.ks,
+                                                                      o.dil, a.h, a.w, o.act, rows);
           else
-            conv_f32_narrow_kernel<2><<<grd, 256, narrow_lds(), st>>>(P(o.a), a.c, o.b >= 0 ? P(o.b) : nullptr, cb, wgt, kp,
-                                                           wgt + (long)o.cout * kp, P(o.dst), o.cout, o.ks, o.dil, a.h, a.w,
-                                                           o.act, rows);
+            conv_f32_narrow_kernel<1><<<dim3(grd.x, path == DVD_CN_PATH_NARROW1 ? 1 : 2), 256, narrow_lds(), st>>>(
+                P(o.a), a.c, pb, cb, wgt, kp, bias, P(o.dst), o.cout, o.ks, o.dil, a.h, a.w, o.act, rows);
           break;
         }
-        if (a.c % 16 == 0 && cb % 16 == 0 && kp == o.ks * o.ks * (a.c + cb) && n->ksplit[i] == 1 && rows < (1l << 31) &&
-            !(o.ks == 1 && o.b < 0)) {
+        if (path == DVD_CN_PATH_WIDE) {
           // wide output over 16-aligned channels (round 5): the 128 x 128 exact-f32 GEMM gathers its A tiles from the map(s)
           // itself - the im2col matrix (up to 9216 columns per pixel) is never written or read
-          if (int e = launch_gemm_conv_f32(P(o.a), a.c, o.b >= 0 ? P(o.b) : nullptr, cb, a.h, a.w, o.ks, o.dil, rows,
-                                           weights + o.w_off, kp, weights + o.w_off + (long)o.cout * kp, P(o.dst), o.cout, o.act,
-                                           stream))
+          if (int e = launch_gemm_conv_f32(P(o.a), a.c, pb, cb, a.h, a.w, o.ks, o.dil, rows, wgt, kp, bias, P(o.dst), o.cout,
+                                           o.act, stream))
             return e;
           break;
         }
+        // the exact-f32 GEMM over rows the op reads somewhere: the im2col matrix of the output pixels' windows (stride 2, or
+        // stride 1 when nothing above applies), or a 1x1 conv's single 16-aligned source itself
+        const long grows = path == DVD_CN_PATH_STRIDED ? B * d.h * d.w : rows;
+        DVD_REQUIRE(grows < (1l << 31), "convnet_run: batch too large for one GEMM");
         const float* A = P(o.a);
         int lda = a.c;
-        if (!(o.ks == 1 && o.b < 0 && a.c == kp)) {   // a 1x1 conv over a 16-aligned single source reads the slot directly
-          const long total4 = rows * (kp / 4);
-          im2col_cat_kernel<<<cdiv(total4, 256), 256, 0, st>>>(P(o.a), a.c, o.b >= 0 ? P(o.b) : nullptr, cb, col, kp,
-                                                              o.ks, o.dil, a.h, a.w, 1, a.h, a.w, total4);
+        if (path != DVD_CN_PATH_DIRECT) {
+          const long total4 = grows * (kp / 4);
+          const bool strided = path == DVD_CN_PATH_STRIDED;
+          im2col_cat_kernel<<<cdiv(total4, 256), 256, 0, st>>>(P(o.a), a.c, pb, cb, col, kp, o.ks, o.dil, a.h, a.w,
+                                                              strided ? 2 : 1, d.h, d.w, total4);
           A = col; lda = kp;
         }
         dvd_gemm_desc g;
         memset(&g, 0, sizeof(g));
-        DVD_REQUIRE(rows < (1l << 31), "convnet_run: batch too large for one GEMM");
-        g.dtype = 1; g.M = (int)rows; g.N = o.cout; g.K = kp; g.batch = 1;
-        g.A = A; g.lda = lda; g.B = weights + o.w_off; g.ldb = kp;
+        g.dtype = 1; g.M = (int)grows; g.N = o.cout; g.K = kp; g.batch = 1;
+        g.A = A; g.lda = lda; g.B = wgt; g.ldb = kp;
         g.C32 = P(o.dst); g.ldc = o.cout;
-        g.bias = weights + o.w_off + (long)o.cout * kp; g.act = o.act;
+        g.bias = bias; g.act = o.act;
         g.lo_scale = 1.f;
-        const int S = n->ksplit[i];
         if (S > 1) {                    // split-K: S partial products in one batched launch, then reduce + bias + act
           float* part = (float*)(ws + n->part_off);
           const long mn = (long)g.M * g.N;
           g.K = kp / S; g.batch = S; g.strideA = kp / S; g.strideB = kp / S;
           g.C32 = part; g.strideC32 = mn; g.bias = nullptr; g.act = 0;
           if (int e = dvd_gemm_nt(&g, stream)) return e;
-          splitk_reduce_kernel<<<cdiv(mn, 256), 256, 0, st>>>(part, S, mn, weights + o.w_off + (long)o.cout * kp, o.cout,
-                                                             o.act, P(o.dst));
+          splitk_reduce_kernel<<<cdiv(mn, 256), 256, 0, st>>>(part, S, mn, bias, o.cout, o.act, P(o.dst));
           break;
         }
         if (int e = dvd_gemm_nt(&g, stream)) return e;

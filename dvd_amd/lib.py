@@ -179,6 +179,7 @@ SIGNATURES = {
     "dvd_convnet_create_batched": [C.POINTER(CnOp), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(c_void)],
     "dvd_convnet_destroy": [c_void],
     "dvd_convnet_slot_shape": [c_void, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)],
+    "dvd_convnet_op_info": [c_void, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)],
     "dvd_convnet_run": [c_void, c_void, c_void, c_void, C.c_long, C.c_int, C.POINTER(C.c_int), C.POINTER(c_void), c_void],
     "dvd_resize_bilinear_nchw": [c_void, c_void, C.c_long, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_void],
     "dvd_threshold_mask_mul": [c_void, c_void, c_void, c_void, C.c_int, C.c_long, C.c_float, c_void],

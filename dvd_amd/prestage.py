@@ -26,6 +26,8 @@ _log = logging.getLogger(__name__)
 
 CONV, POOL, RESIZE, ADD, SIGMOID, INSTNORM = range(6)
 BN_EPS = 1e-5
+# DVD_CN_PATH_*: the route the executor takes for a conv (include/dvd_hip.h, dvd_convnet_op_info)
+PATH_NONE, PATH_NARROW1, PATH_NARROW1X2, PATH_NARROW2, PATH_WIDE, PATH_DIRECT, PATH_GATHER, PATH_STRIDED = range(8)
 
 
 # ---------------------------------------------------------------------------------------------------------
@@ -60,6 +62,11 @@ class Program:
     def resize_like(self, a, like, align):
         dst = self._new(self.ch[a])
         self.ops.append(dict(op=RESIZE, a=a, b=like, dst=dst, flag=int(align)))
+        return dst
+
+    def resize_to(self, a, h, w, align):
+        dst = self._new(self.ch[a])
+        self.ops.append(dict(op=RESIZE, a=a, b=-1, dst=dst, h=int(h), w=int(w), flag=int(align)))
         return dst
 
     def add(self, a, b, relu=False):
@@ -254,6 +261,12 @@ class ConvNet:
 
     def weight_bytes(self) -> int:
         return self.program.w_floats * 4
+
+    def op_info(self, op: int):
+        """(PATH_*, split-K factor) of op `op` of the program: what the library decided at creation (host-only)."""
+        path, ksplit = C.c_int(), C.c_int()
+        lib.call("dvd_convnet_op_info", self._h, op, C.byref(path), C.byref(ksplit))
+        return path.value, ksplit.value
 
     def bind_weights(self, blob_f32: torch.Tensor):
         assert blob_f32.dtype == torch.float32 and blob_f32.numel() == self.program.w_floats

@@ -317,6 +317,21 @@ int dvd_convnet_destroy(void* handle);
 long dvd_convnet_workspace_bytes(void* handle);
 long dvd_convnet_weight_floats(void* handle);
 int dvd_convnet_slot_shape(void* handle, int slot, int* h, int* w, int* c);
+/* The route dvd_convnet_run takes for op `op` of the list, decided once in dvd_convnet_create from the shapes alone
+ * (host-only; tests assert it so that a case written for one kernel cannot silently move to another):
+ *   NARROW1    conv_f32_narrow_kernel<1>, one column group       (cout <= 32, sources 8-aligned, their sum 16-aligned)
+ *   NARROW1X2  conv_f32_narrow_kernel<1>, two column groups      (cout 33..64, fewer than 16384 rows in the batch)
+ *   NARROW2    conv_f32_narrow_kernel<2>                         (cout 33..64, at least 16384 rows)
+ *   WIDE       the 128 x 128 GEMM gathering its A tiles itself   (cout > 64, sources 16-aligned, no split-K, not a
+ *                                                                 single-source 1x1)
+ *   DIRECT     the GEMM reads a 1x1 conv's single 16-aligned source in place
+ *   GATHER     im2col matrix + GEMM (everything else at stride 1)
+ *   STRIDED    im2col matrix of the output pixels + GEMM (stride 2)
+ * *ksplit: the number of K slices (1 = none; > 1 only with GATHER and DIRECT: S partial GEMMs, then a reduction in slice
+ * order).  Ops that are no conv report NONE and 1. */
+enum { DVD_CN_PATH_NONE = 0, DVD_CN_PATH_NARROW1 = 1, DVD_CN_PATH_NARROW1X2 = 2, DVD_CN_PATH_NARROW2 = 3,
+       DVD_CN_PATH_WIDE = 4, DVD_CN_PATH_DIRECT = 5, DVD_CN_PATH_GATHER = 6, DVD_CN_PATH_STRIDED = 7 };
+int dvd_convnet_op_info(void* handle, int op, int* path, int* ksplit);
 /* One forward pass: in_nchw [batch, in_c, in_h, in_w] f32 planar (batch = 1 for dvd_convnet_create); the requested slots
  * are written to out_nchw[k] as planar [batch, c, h, w].  workspace: >= dvd_convnet_workspace_bytes, 256-byte aligned. */
 int dvd_convnet_run(void* handle, const float* in_nchw, const float* weights, void* workspace, long workspace_bytes,

@@ -60,6 +60,112 @@ def test_attention_hd32_vs_float64():
     assert lib.flash_attn_kernel_name(32, 1296, 1296) == "flash_attn_f32_hd32_kernel"
 
 
+def _call(name, *args):
+    lib.call(name, *args, lib.stream_ptr())
+    torch.cuda.synchronize()
+
+
+@pytest.mark.parametrize("rows", [1, 3, 4, 5, 1297])
+def test_layernorm256_vs_float64(rows):
+    """One wave per row, four rows per workgroup: rows below, at and past a workgroup, and a ragged last one."""
+    import ctypes as C
+    x = torch.from_numpy(synth.normalish(f"geotr/ln/x{rows}", (rows, 256), 3)) * 2.0 + 0.5
+    gamma = torch.from_numpy(synth.uniform("geotr/ln/g", (256,), 0.5, 1.5, 3))
+    beta = torch.from_numpy(synth.uniform("geotr/ln/b", (256,), -0.5, 0.5, 3))
+    out = torch.full((rows + 1, 256), 7.0, device="cuda")
+    xd, gd, bd = x.cuda(), gamma.cuda(), beta.cuda()
+    _call("dvd_layernorm256_f32", lib.ptr(xd), lib.ptr(out), rows, lib.ptr(gd), lib.ptr(bd), C.c_float(1e-5))
+    want = F.layer_norm(x.double(), (256,), gamma.double(), beta.double(), 1e-5)
+    err = float((out[:rows].cpu().double() - want).abs().max() / want.abs().max())
+    print(f"layernorm256 rows {rows}: max abs / max |want| {err:.2e}")
+    assert err <= 2e-6, err
+    assert bool((out[rows] == 7.0).all()), "wrote past the last row"
+
+
+@pytest.mark.parametrize("c", [4, 256])
+def test_add_rows_ragged_position_table(c):
+    rows, pos_rows = 7, 3                            # rows % pos_rows != 0: the table wraps and the last pass is cut short
+    a = torch.from_numpy(synth.normalish(f"geotr/addrows/a{c}", (rows, c), 3))
+    pos = torch.from_numpy(synth.normalish(f"geotr/addrows/p{c}", (pos_rows, c), 3))
+    out = torch.full((rows + 1, c), 7.0, device="cuda")
+    ad, pd = a.cuda(), pos.cuda()
+    _call("dvd_add_rows_f32", lib.ptr(ad), lib.ptr(pd), lib.ptr(out), rows, pos_rows, c)
+    assert torch.equal(out[:rows].cpu(), a + pos[torch.arange(rows) % pos_rows])
+    assert bool((out[rows] == 7.0).all())
+
+
+@pytest.mark.parametrize("n", [1, 3])
+@pytest.mark.parametrize("rows,cols", [(33, 31), (1, 70), (1296, 256)])
+def test_transpose(n, rows, cols):
+    x = torch.from_numpy(synth.normalish(f"geotr/tr/{rows}x{cols}", (n, rows, cols), 3))
+    out = torch.full((n * rows * cols + 64,), 7.0, device="cuda")
+    xd = x.cuda()
+    _call("dvd_transpose_f32", lib.ptr(xd), lib.ptr(out), n, rows, cols)
+    assert torch.equal(out[:n * rows * cols].cpu().reshape(n, cols, rows), x.transpose(1, 2))
+    assert bool((out[n * rows * cols:] == 7.0).all())
+
+
+@pytest.mark.parametrize("hw", [1, 255, 257])
+@pytest.mark.parametrize("c", [1, 3])
+def test_soft_mask_mul(hw, c):
+    n = 2
+    msk = torch.from_numpy(synth.uniform(f"geotr/smm/m{hw}", (n, 1, 1, hw), 0, 1, 3))
+    x = torch.from_numpy(synth.normalish(f"geotr/smm/x{hw}/{c}", (n, c, 1, hw), 3))
+    got = prestage.soft_mask_mul(msk.cuda(), x.cuda())
+    assert torch.equal(got.cpu(), msk * x)
+
+
+def _convex_upsample_float64(mask, dflow):
+    """GeoTr.upsample_flow(coords1 - coords0, 0.25 * mask) in float64 (RAFT's convex upsampling): softmax over the 9 taps, the
+    zero-padded 3x3 unfold of 8 * flow with flow = (coords0 + dflow) - coords0, summed over the taps."""
+    n, _, h, w = dflow.shape
+    ys, xs = torch.meshgrid(torch.arange(h, dtype=torch.float64), torch.arange(w, dtype=torch.float64), indexing="ij")
+    coords0 = torch.stack((xs, ys))[None]
+    flow = (coords0 + dflow.double()) - coords0
+    m = torch.softmax((0.25 * mask.double()).view(n, 1, 9, 8, 8, h, w), dim=2)
+    up = F.unfold(8 * flow, [3, 3], padding=1).view(n, 2, 9, 1, 1, h, w)
+    return torch.sum(m * up, dim=2).permute(0, 1, 4, 2, 5, 3).reshape(n, 2, 8 * h, 8 * w)
+
+
+@pytest.mark.parametrize("h,w", [(3, 5), (4, 4)])
+def test_convex_upsample_vs_float64(h, w):
+    """Maps so small that every coarse pixel touches a border (zero-padded taps everywhere), two documents.
+
+    bm is checked on a rough field (large random flows, sharp random tap weights) and on a gentle one; init_flow on the
+    gentle one only, because its bar of 5e-7 presumes a map as smooth as a real backward map: the kernel forms the source
+    position as ATen does, scale * index in f32, which is off the exact position by up to 2 * 2^-24 * (8 max(h, w) - 1)
+    fine pixels per axis, and that offset times the slope of bm / norm per fine pixel is a difference from the float64
+    reference no kernel following ATen can avoid.  The test asserts on its OWN reference field that this term stays below
+    1e-7 (a fifth of the bar); on the rough field the term may reach 4.5e-6."""
+    import ctypes as C
+    n, norm = 2, float(8 * max(h, w) - 1)
+    for kind, mask_scale, amp in (("rough", 4.0, 0.5 * max(h, w)), ("gentle", 1.0, 0.1)):
+        mask = torch.from_numpy(synth.normalish(f"geotr/cu/m{h}x{w}", (n, 576, h, w), 3)) * mask_scale
+        dflow = torch.from_numpy(synth.uniform(f"geotr/cu/f{h}x{w}", (n, 2, h, w), -amp, amp, 3))
+        want = _convex_upsample_float64(mask, dflow)
+        md, fd = mask.cuda(), dflow.cuda()
+        v = want / norm
+        slope = float((v[..., 1:] - v[..., :-1]).abs().max()) + float((v[..., 1:, :] - v[..., :-1, :]).abs().max())
+        index_term = slope * 2.0 ** -23 * norm
+        if kind == "gentle":
+            assert index_term <= 1e-7, index_term           # about the test's data, not about the kernel
+        for g in (7, 16):
+            bm = torch.empty(n, 2, 8 * h, 8 * w, device="cuda")
+            init = torch.empty(n, 2, g, g, device="cuda")
+            _call("dvd_convex_upsample", lib.ptr(md), lib.ptr(fd), n, h, w, lib.ptr(bm), lib.ptr(init), g, C.c_float(norm))
+            e_bm = float((bm.cpu().double() - want).abs().max())
+            want_init = F.interpolate(v, size=(g, g), mode="bilinear", align_corners=True)
+            e_if = float((init.cpu().double() - want_init).abs().max())
+            print(f"convex upsample {h}x{w} {kind} g {g}: bm max abs {e_bm:.2e} px, init_flow max abs {e_if:.2e} "
+                  f"(source-position term of the reference field <= {index_term:.1e})")
+            assert e_bm <= 1.5e-4, e_bm
+            assert e_if <= 5e-7 + (0.0 if kind == "gentle" else index_term), e_if
+            # init_flow alone (bm not requested) is the same kernel on the same values
+            init2 = torch.empty_like(init)
+            _call("dvd_convex_upsample", lib.ptr(md), lib.ptr(fd), n, h, w, None, lib.ptr(init2), g, C.c_float(norm))
+            assert torch.equal(init2, init)
+
+
 def test_strided_conv_instnorm_residual_vs_torch():
     """The executor's new ops on a small net: 7x7/2 conv, InstanceNorm + ReLU, 3x3/2 conv, 1x1/2 conv, relu(a + b)."""
     P = prestage.Program(3)

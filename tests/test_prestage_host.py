@@ -1,39 +1,14 @@
 """CPU checks of the pre-stage nets' HOST side (dvd_amd/prestage.py): the op-list builder and the weight packer are
-validated by interpreting the op list with plain torch ops (this interpreter is test infrastructure - the product runs
-the list on the HIP executor) and comparing with the oracle, which is itself pinned to the real reference (golden G8)."""
+validated by interpreting the op list with plain torch ops (tests/convnet_model.py: test infrastructure - the product
+runs the list on the HIP executor) and comparing with the oracle, which is itself pinned to the real reference (golden G8)."""
 import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
 
+from convnet_model import interpret
 from dvd_amd import prestage, synth
 from oracle import prestage_oracle as PO
-
-
-def interpret(program, weights, x):
-    """Run a prestage.Program on the CPU: x [1,C,H,W] -> {slot: tensor}."""
-    slots = {0: x}
-    for op, (src, cin, cout, ks, kp) in zip([o for o in program.ops if o["op"] == prestage.CONV], program.convs):
-        op["_meta"] = (cin, cout, ks, kp)
-    for o in program.ops:
-        a = slots[o["a"]]
-        if o["op"] == prestage.CONV:
-            cin, cout, ks, kp = o["_meta"]
-            off = o["w_off"]
-            w = weights[off:off + cout * kp].reshape(cout, kp)[:, :ks * ks * cin].reshape(cout, ks, ks, cin).permute(0, 3, 1, 2)
-            b = weights[off + cout * kp:off + cout * kp + cout]
-            inp = a if o.get("b", -1) < 0 else torch.cat((a, slots[o["b"]]), 1)
-            y = F.conv2d(inp, w.contiguous(), b, padding=o["dil"] * (ks // 2), dilation=o["dil"])
-            slots[o["dst"]] = F.relu(y) if o["act"] == 2 else y
-        elif o["op"] == prestage.POOL:
-            slots[o["dst"]] = F.max_pool2d(a, 2, stride=2, ceil_mode=bool(o["flag"]))
-        elif o["op"] == prestage.RESIZE:
-            slots[o["dst"]] = F.interpolate(a, size=slots[o["b"]].shape[2:], mode="bilinear", align_corners=bool(o["flag"]))
-        elif o["op"] == prestage.ADD:
-            slots[o["dst"]] = a + slots[o["b"]]
-        elif o["op"] == prestage.SIGMOID:
-            slots[o["dst"]] = torch.sigmoid(a)
-    return slots
 
 
 @pytest.fixture(scope="module")
