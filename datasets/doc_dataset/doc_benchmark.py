@@ -29,15 +29,17 @@ import os
 import numpy as np
 from torch.utils.data import Dataset
 
+from dvd_amd.run_options import CODEC_ROUTES
+
 _JPEG_EXTS = (".jpg", ".jpeg")
 _IMAGE_EXTS = (".jpg", ".jpeg", ".png", ".bmp", ".tif", ".tiff", ".webp")
 
 
 class Doc_benchmark(Dataset):
     def __init__(self, data_root, input_transform, decode="pil", decode_png="pil") -> None:
-        if decode not in ("pil", "hip"):
+        if decode not in CODEC_ROUTES:
             raise ValueError(f"Doc_benchmark: decode must be 'pil' or 'hip', got {decode!r}")
-        if decode_png not in ("pil", "hip"):
+        if decode_png not in CODEC_ROUTES:
             raise ValueError(f"Doc_benchmark: decode_png must be 'pil' or 'hip', got {decode_png!r}")
         self.decode_png = decode_png
         self.data_root = data_root

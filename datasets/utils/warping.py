@@ -15,6 +15,7 @@ import torch
 from torch import nn
 
 from dvd_amd import ops
+from dvd_amd.run_options import WARP_MODES
 
 
 class SpatialTransformer2(nn.Module):
@@ -23,7 +24,7 @@ class SpatialTransformer2(nn.Module):
 
     def __init__(self, size, mode="bilinear"):
         super().__init__()
-        if mode not in ("bilinear", "bicubic"):
+        if mode not in WARP_MODES:
             raise NotImplementedError(f"mode {mode!r}: the warps are 'bilinear' (the sampling path, gaussian_diffusion.py:20,218) "
                                       "and 'bicubic'")
         self.size, self.mode = tuple(size), mode      # `size` is unused by the reference's forward as well

@@ -15,7 +15,8 @@ import time
 import numpy as np
 import torch as th
 
-from . import ops, synth
+from . import ops, run_options, synth
+from .run_options import GT_METRICS, RunOptions, parse_gt_metrics  # noqa: F401 - parse_gt_metrics is imported from here
 
 
 def run_sample_lr_dewarping(settings, logger, diffusion, model, radius, source, feature_size, raw_corr, init_flow, c20,
@@ -34,8 +35,9 @@ def run_sample_lr_dewarping(settings, logger, diffusion, model, radius, source, 
     logger.info("\nStarting sampling")
     B = source.shape[0]
     extra = {}
-    if getattr(settings.env, "sampler", "ddim") != "ddim":
-        extra["sampler_kind"] = settings.env.sampler          # engine-side extension (BASELINE configs[3]: 'ddpm')
+    sampler = run_options.read(settings.env, "sampler")
+    if sampler != "ddim":
+        extra["sampler_kind"] = sampler                       # engine-side extension (BASELINE configs[3]: 'ddpm')
     sample, _ = diffusion.ddim_sample_loop(
         model, (B, 2, feature_size, feature_size), noise=None, clip_denoised=settings.env.clip_denoised,
         model_kwargs=kw, eta=0.0, progress=True, denoised_fn=None, sampling_kwargs={"src_img": source}, logger=logger,
@@ -48,7 +50,7 @@ def synthetic_documents(settings, indices):
     nets -> sampler -> unwarp), otherwise random conditioning tensors in the value ranges of SURVEY 8(d)."""
     G = settings.env.grid_size
     for i in indices:
-        if getattr(settings.env, "use_prestage_nets", False):
+        if run_options.read(settings.env, "use_prestage_nets"):
             h, w = settings.env.full_res
             img = synth.smooth_image(f"doc{i}/image", h, w, seed=1234)
             d = {"image_u8": np.ascontiguousarray((img.transpose(1, 2, 0) * 255.0).astype(np.uint8))}
@@ -179,37 +181,23 @@ def find_gt(gt_dir, path):
     return None
 
 
-GT_METRICS = ("ms_ssim", "ld")
-
-
-def parse_gt_metrics(value):
-    """env.gt_metrics, a comma-separated list of GT_METRICS names ('ms_ssim' | 'ms_ssim,ld' | 'ld') -> the names, in the order
-    of GT_METRICS.  Anything else is a ValueError."""
-    names = [n.strip() for n in value.split(",")] if isinstance(value, str) else None
-    if not names or any(n not in GT_METRICS for n in names) or len(set(names)) != len(names):
-        raise ValueError(f"env.gt_metrics must be a comma-separated list of {GT_METRICS} without repeats, got {value!r}")
-    return tuple(m for m in GT_METRICS if m in names)
-
-
 def png_decoder_setting(env):
     """env.png_decoder 'pil' | 'hip': who decodes PNG files (input photographs and ground-truth scans).  Anything else is a
     ValueError."""
-    value = getattr(env, "png_decoder", "pil")
-    if value not in ("pil", "hip"):
-        raise ValueError(f"env.png_decoder must be 'pil' or 'hip', got {value!r}")
-    return value
+    return run_options.check(env, "png_decoder")
 
 
-def _score_against_gt(settings, logger, path, out, device, metrics=("ms_ssim",)):
+def _score_against_gt(settings, logger, path, out, device, opts):
     """The metrics of one dewarped page (uint8 [H,W,3] on the device) against its ground-truth scan, if there is one: MS-SSIM,
-    LD and / or AD, on planes prepared once."""
+    LD and / or AD (opts.gt_metrics), on planes prepared once."""
     from PIL import Image
-    gt_file = find_gt(settings.env.gt_dir, path)
+    metrics = opts.gt_metrics
+    gt_file = find_gt(opts.gt_dir, path)
     if gt_file is None:
-        logger.info(f"{path} {','.join(metrics)} skipped: no ground truth in {settings.env.gt_dir}")
+        logger.info(f"{path} {','.join(metrics)} skipped: no ground truth in {opts.gt_dir}")
         return
     gt = None
-    if png_decoder_setting(settings.env) == "hip":
+    if opts.png_decoder == "hip":
         # the scan is inflated and unfiltered on the device; a file the decoder hands back (or one that is no PNG) takes
         # the host route below, untouched, so that the scores are the same bits either way
         with open(gt_file, "rb") as f:
@@ -221,143 +209,140 @@ def _score_against_gt(settings, logger, path, out, device, metrics=("ms_ssim",))
                 logger.info(f"{gt_file}: decoded by PIL, not on the device: {e}")
     if gt is None:
         gt = th.from_numpy(np.ascontiguousarray(np.asarray(Image.open(gt_file).convert("RGB")))).to(device)
-    values = ops.gt_metrics_u8(out.contiguous(), gt, metrics, preset=getattr(settings.env, "metric_preset", "docunet"))
+    values = ops.gt_metrics_u8(out.contiguous(), gt, metrics, preset=opts.metric_preset)
     for name in metrics:
         logger.info(f"{path} {name} {values[name]:.6f}")
         getattr(settings, name).append((path, values[name]))
 
 
-def run_evaluation_docunet(settings, logger, val_loader, diffusion, model, pretrained_dewarp_model,
-                           pretrained_line_seg_model=None, pretrained_seg_model=None):
-    """Document loop with the reference's positional signature (evaluation.py:142-327; call site val_TDiff.py:103-104).
-    `val_loader` yields the reference's dicts or this package's documents (`documents_of`); `env.batch_docs` documents are
-    batched per pass (the reference: 1): ingest + the three pre-stage nets for documents that arrive as images
-    (:162-216), the sampler (:247-265), then the tail (:301-306 + visualization_utils.py:75-77) as ONE fused u8 launch per
-    batch (documents of one size or of different sizes alike; env.unwarp_mode 'bilinear' | 'bicubic' is its interpolation), and - if env.visualize - `visualize_dewarping` writes the PNG where the reference writes it
-    (env.png_encoder 'pil' | 'hip': PIL on a host copy, or the HIP encoder on the device with env.png_huffman 'fixed' |
-    'dynamic' blocks; env.page_format 'jpeg' writes
-    warped_<stem>.jpg with the HIP JPEG encoder instead, at env.jpeg_quality and env.jpeg_subsampling).
-    env.image_decoder 'pil' | 'hip' says who decodes the input photograph: the loader (PIL), or - for items that carry the JPEG
-    file as `file_bytes` - the HIP decoder on the device (`decode_documents`; the same bytes either way).
-    env.png_decoder 'pil' | 'hip' says the same for PNG files: `.png` items that carry the file, and the ground-truth scans of
-    env.gt_dir, are decoded by the HIP PNG decoder; a file it hands back goes to PIL.
-    The pre-stage models may all be None when every document carries ready conditioning tensors.
-    With env.gt_dir set, every dewarped page is scored against `<gt_dir>/<stem>.png` (`gt_candidates`) with MS-SSIM
-    (ops.ms_ssim_u8, env.metric_preset): logged per document and as a mean, written to ms_ssim.txt beside the pictures and
-    left in settings.ms_ssim as [(path, value)]; a document without a ground truth is logged and skipped.
-    env.gt_metrics 'ms_ssim' | 'ms_ssim,ld' | 'ld' chooses the metrics: 'ld' adds the local distortion (ops.ld_u8: the mean
-    SIFT-flow length from the scan to the page) in the same way - ld.txt and settings.ld.
-    env.gt_ad = True adds the aligned distortion (ops.ad_u8) in the same way - ad.txt and settings.ad; with 'ld'
-    among the metrics both come from one run of the chain.
-    Returns [(path, uint8 [H,W,3] device tensor)] (the reference returns None)."""
-    from utils_flow.visualization_utils import page_settings, png_huffman_setting, visualize_dewarping
-    env = settings.env
-    unwarp_mode = getattr(env, "unwarp_mode", "bilinear")       # the interpolation of the full-resolution tail
-    if unwarp_mode not in ("bilinear", "bicubic"):
-        raise ValueError(f"env.unwarp_mode must be 'bilinear' or 'bicubic', got {unwarp_mode!r}")
-    png_encoder = getattr(env, "png_encoder", "pil")            # who writes the PNG: visualize_dewarping reads it
-    if png_encoder not in ("pil", "hip"):
-        raise ValueError(f"env.png_encoder must be 'pil' or 'hip', got {png_encoder!r}")
-    png_huffman_setting(env)                                    # 'fixed' | 'dynamic': the 'hip' PNG encoder's blocks
-    page_settings(env)                                          # env.page_format, env.jpeg_quality, env.jpeg_subsampling
-    image_decoder = getattr(env, "image_decoder", "pil")        # who decodes the input photograph: the loader reads it
-    if image_decoder not in ("pil", "hip"):
-        raise ValueError(f"env.image_decoder must be 'pil' or 'hip', got {image_decoder!r}")
-    png_decoder = png_decoder_setting(env)                      # who decodes PNG files: the loader and the scoring read it
-    gt_metrics = parse_gt_metrics(getattr(env, "gt_metrics", "ms_ssim"))       # what env.gt_dir scores
-    gt_ad = getattr(env, "gt_ad", False)                        # ... and whether it scores AD as well
-    if not isinstance(gt_ad, bool):
-        raise ValueError(f"env.gt_ad must be True or False, got {gt_ad!r}")
-    if gt_ad:
-        gt_metrics += ("ad",)
-    device = next(model.parameters()).device
-    nets = (pretrained_dewarp_model, pretrained_seg_model, pretrained_line_seg_model)
-    prestage_models = None if all(m is None for m in nets) else nets
-    os.makedirs(f"vis_hp/{env.eval_dataset_name}/{settings.name}", exist_ok=True)
-    G, B = env.grid_size, env.batch_docs
-    times, results, batch = [], [], []
-    gt_dir = getattr(env, "gt_dir", "")
-    if gt_dir:
-        ops._ssim_preset(getattr(env, "metric_preset", "docunet"), "env.metric_preset")
-        for name in gt_metrics:
-            setattr(settings, name, [])
+def _on_device(v, device):
+    return v.to(device) if th.is_tensor(v) else th.from_numpy(v).to(device)
 
-    def flush():
-        if not batch:
-            return
-        nb = len(batch)
-        dev_t = lambda v: v.to(device) if th.is_tensor(v) else th.from_numpy(v).to(device)  # noqa: E731
-        stack = lambda k: th.stack([dev_t(d[k]) for d in batch]).contiguous()  # noqa: E731
-        for d in batch:                                     # reference-shaped items: the source as u8 for ingest / tail
-            if "source_vis" in d and "src_u8" not in d:
-                u8 = _source_u8(d, device)
-                if u8 is not None:
-                    d["src_u8"] = u8
-                    if "y512" not in d:
-                        d["image_u8"] = u8
-                elif "y512" not in d:
-                    raise ValueError(f"{d['path']}: no 'source_image' and a non-integer 'source_image_ori' to make it from")
-        use_init_flow = bool(getattr(env, "use_init_flow", False))
-        prepare_conditioning(batch, device, G, prestage_models, use_init_flow, decode_png=png_decoder == "hip")
-        t0 = time.time()
-        src, msk, seg, line = stack("y512"), stack("mask_cat"), stack("mask_y512"), stack("line_msk")
-        init_flow = stack("init_flow") if use_init_flow else th.zeros(nb, 2, G, G, device=device)       # :176-181
-        flow = run_sample_lr_dewarping(settings, logger, diffusion, model, 4, src, G, None,
-                                       init_flow, None, None, None, msk, seg, line,
-                                       th.zeros(nb, 256, G, G, device=device))
-        th.cuda.synchronize()
-        times.append((time.time() - t0) / nb)
-        # :301-306 + viz :75-77 - one launch for the batch when its documents are byte images
-        if all("src_u8" in d for d in batch) and len({tuple(d["src_u8"].shape) for d in batch}) == 1:
-            outs = ops.unwarp_u8_batch(flow.contiguous(), stack("src_u8"), mode=unwarp_mode)
-        else:
-            # byte images of different sizes: still one launch (the ragged tail); a float source that is not a byte image
-            # takes the fused f32 tail on its own, truncated like numpy's astype(uint8) (bicubic: the grid and the f32
-            # drop-in kernel, clamped to 0..255 first - bicubic overshoots)
-            outs = [None] * nb
-            u8 = [j for j, d in enumerate(batch) if "src_u8" in d]
-            if u8:
-                fl = flow.contiguous() if len(u8) == nb else flow[u8].contiguous()
-                for j, out in zip(u8, ops.unwarp_u8_ragged(fl, [dev_t(batch[j]["src_u8"]).contiguous() for j in u8],
-                                                             mode=unwarp_mode)):
-                    outs[j] = out
-            for j, d in enumerate(batch):
-                if outs[j] is None and unwarp_mode == "bicubic":
-                    vis = d["source_vis"].to(device).float()[None].contiguous()
-                    grid = ops.unwarp_grid(flow[j:j + 1].contiguous(), vis.shape[-2], vis.shape[-1])
-                    f32 = ops.grid_sample(vis, grid, mode="bicubic")[0]
-                    # NaN (a non-finite grid value) -> 0, as the u8 kernels give; then np.clip(a, 0, 255).astype(uint8)
-                    outs[j] = th.nan_to_num(f32, nan=0.0).clamp(0, 255).to(th.uint8).permute(1, 2, 0).contiguous()
-                elif outs[j] is None:
-                    outs[j] = ops.unwarp_f32(flow[j:j + 1].contiguous(),
-                                             d["source_vis"].to(device).float()[None].contiguous()).to(th.uint8)
-        for j, d in enumerate(batch):
-            out = outs[j]
-            results.append((d["path"], out))
-            if env.visualize:
-                name = d["path"] if os.path.splitext(d["path"])[1] else d["path"] + ".png"
-                visualize_dewarping(settings, None, d, len(results) - 1, None, [name], warped_u8=out)
-            if gt_dir:
-                _score_against_gt(settings, logger, d["path"], out, device, gt_metrics)
-        batch.clear()
 
+def _stack(batch, key, device):
+    return th.stack([_on_device(d[key], device) for d in batch]).contiguous()
+
+
+def batches_of(val_loader, size):
+    """The loader's documents (`documents_of`) in lists of `size`; the last one may be shorter."""
+    batch = []
     for item in val_loader:
         for d in documents_of(item):
             batch.append(d)
-            if len(batch) == B:
-                flush()
-    flush()
+            if len(batch) == size:
+                yield batch
+                batch = []
+    if batch:
+        yield batch
+
+
+def adopt_reference_items(batch, device):
+    """Reference-shaped items (`source_vis`): the source as `src_u8` for the tail and, without a `source_image`, as `image_u8`
+    for ingest."""
+    for d in batch:
+        if "source_vis" in d and "src_u8" not in d:
+            u8 = _source_u8(d, device)
+            if u8 is not None:
+                d["src_u8"] = u8
+                if "y512" not in d:
+                    d["image_u8"] = u8
+            elif "y512" not in d:
+                raise ValueError(f"{d['path']}: no 'source_image' and a non-integer 'source_image_ori' to make it from")
+
+
+def sample_batch(settings, logger, diffusion, model, batch, grid, device):
+    """The conditioned documents of one batch through `run_sample_lr_dewarping` (evaluation.py:247-265): the flow [B,2,G,G]."""
+    nb = len(batch)
+    src, msk, seg, line = (_stack(batch, k, device) for k in ("y512", "mask_cat", "mask_y512", "line_msk"))
+    init_flow = _stack(batch, "init_flow", device) if settings.env.use_init_flow else th.zeros(nb, 2, grid, grid, device=device)  # :176-181
+    return run_sample_lr_dewarping(settings, logger, diffusion, model, 4, src, grid, None, init_flow, None, None, None, msk,
+                                   seg, line, th.zeros(nb, 256, grid, grid, device=device))
+
+
+def unwarp_tail(batch, flow, mode, device):
+    """The full-resolution pages of one batch (:301-306 + viz :75-77) as a list of uint8 [H,W,3] device tensors: one launch
+    for the batch when its documents are byte images."""
+    nb = len(batch)
+    if all("src_u8" in d for d in batch) and len({tuple(d["src_u8"].shape) for d in batch}) == 1:
+        return list(ops.unwarp_u8_batch(flow.contiguous(), _stack(batch, "src_u8", device), mode=mode))
+    # byte images of different sizes: still one launch (the ragged tail); a float source that is not a byte image takes the
+    # fused f32 tail on its own, truncated like numpy's astype(uint8) (bicubic: the grid and the f32 drop-in kernel, clamped
+    # to 0..255 first - bicubic overshoots)
+    outs = [None] * nb
+    u8 = [j for j, d in enumerate(batch) if "src_u8" in d]
+    if u8:
+        fl = flow.contiguous() if len(u8) == nb else flow[u8].contiguous()
+        srcs = [_on_device(batch[j]["src_u8"], device).contiguous() for j in u8]
+        for j, out in zip(u8, ops.unwarp_u8_ragged(fl, srcs, mode=mode)):
+            outs[j] = out
+    for j, d in enumerate(batch):
+        if outs[j] is not None:
+            continue
+        vis = d["source_vis"].to(device).float()[None].contiguous()
+        if mode == "bicubic":
+            grid = ops.unwarp_grid(flow[j:j + 1].contiguous(), vis.shape[-2], vis.shape[-1])
+            f32 = ops.grid_sample(vis, grid, mode="bicubic")[0]
+            # NaN (a non-finite grid value) -> 0, as the u8 kernels give; then np.clip(a, 0, 255).astype(uint8)
+            outs[j] = th.nan_to_num(f32, nan=0.0).clamp(0, 255).to(th.uint8).permute(1, 2, 0).contiguous()
+        else:
+            outs[j] = ops.unwarp_f32(flow[j:j + 1].contiguous(), vis).to(th.uint8)
+    return outs
+
+
+def emit(settings, logger, batch, outs, results, opts, device):
+    """The pages of one batch into `results`; the picture if env.visualize, the scores if env.gt_dir."""
+    for d, out in zip(batch, outs):
+        results.append((d["path"], out))
+        if settings.env.visualize:
+            from utils_flow.visualization_utils import visualize_dewarping
+            name = d["path"] if os.path.splitext(d["path"])[1] else d["path"] + ".png"
+            visualize_dewarping(settings, None, d, len(results) - 1, None, [name], warped_u8=out)
+        if opts.gt_dir:
+            _score_against_gt(settings, logger, d["path"], out, device, opts)
+
+
+def summarize(settings, logger, opts, times, results):
+    """The end of a run: the timing, and per metric of env.gt_dir its <name>.txt and the mean."""
     if times:
         print(len(times))
         print("Elapsed time:{:.2f} avg_second ".format(sum(times) / len(times)))
-    for name in gt_metrics if gt_dir else ():
+    for name in opts.gt_metrics if opts.gt_dir else ():
         scores = getattr(settings, name)
-        with open(f"vis_hp/{env.eval_dataset_name}/{settings.name}/{name}.txt", "w") as f:
+        with open(f"vis_hp/{settings.env.eval_dataset_name}/{settings.name}/{name}.txt", "w") as f:
             for path, value in scores:
                 f.write(f"{path} {value:.6f}\n")
         if scores:
             mean = sum(v for _, v in scores) / len(scores)
             logger.info(f"mean {name} {mean:.6f} over {len(scores)} of {len(results)} documents")
         else:
-            logger.info(f"mean {name}: no document of {len(results)} has a ground truth in {gt_dir}")
+            logger.info(f"mean {name}: no document of {len(results)} has a ground truth in {opts.gt_dir}")
+
+
+def run_evaluation_docunet(settings, logger, val_loader, diffusion, model, pretrained_dewarp_model,
+                           pretrained_line_seg_model=None, pretrained_seg_model=None):
+    """Document loop with the reference's positional signature (evaluation.py:142-327; call site val_TDiff.py:103-104).
+    `val_loader` yields the reference's dicts or this package's documents (`documents_of`); env.batch_docs of them go through
+    each pass (the reference: 1): adopt, ingest + pre-stage nets (:162-216), the sampler (:247-265), the unwarp tail, then the
+    picture and the scores.  The engine-side switches (dvd_amd/run_options.py) are read and checked once, before the loader is
+    touched and before anything is written.  The pre-stage models may all be None when every document carries ready
+    conditioning tensors.  Returns [(path, uint8 [H,W,3] device tensor)] (the reference returns None)."""
+    opts = RunOptions.from_env(settings.env)
+    device = next(model.parameters()).device
+    nets = (pretrained_dewarp_model, pretrained_seg_model, pretrained_line_seg_model)
+    prestage_models = None if all(m is None for m in nets) else nets
+    os.makedirs(f"vis_hp/{settings.env.eval_dataset_name}/{settings.name}", exist_ok=True)
+    for name in opts.gt_metrics if opts.gt_dir else ():
+        setattr(settings, name, [])
+    times, results = [], []
+    for batch in batches_of(val_loader, opts.batch_docs):
+        adopt_reference_items(batch, device)
+        prepare_conditioning(batch, device, opts.grid_size, prestage_models, bool(settings.env.use_init_flow),
+                             decode_png=opts.png_decoder == "hip")
+        t0 = time.time()
+        flow = sample_batch(settings, logger, diffusion, model, batch, opts.grid_size, device)
+        th.cuda.synchronize()
+        times.append((time.time() - t0) / len(batch))
+        outs = unwarp_tail(batch, flow, opts.unwarp_mode, device)
+        emit(settings, logger, batch, outs, results, opts, device)
+    summarize(settings, logger, opts, times, results)
     return results

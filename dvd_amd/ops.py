@@ -10,12 +10,14 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+from typing import NamedTuple
 
 import numpy as np
 import torch
 
-from . import lib
+from . import lib, run_options
 from .lib import ptr, stream_ptr
+from .run_options import either
 
 
 def _chk(t: torch.Tensor, dtype, name):
@@ -25,13 +27,10 @@ def _chk(t: torch.Tensor, dtype, name):
         raise lib.DvdError(f"{name}: expected contiguous {dtype}, got {t.dtype} contiguous={t.is_contiguous()}")
 
 
-_WARP_MODES = ("bilinear", "bicubic")
-
-
 def _warp_mode(mode, name):
     """The interpolation of a warp: checked before anything is allocated or launched."""
-    if mode not in _WARP_MODES:
-        raise ValueError(f"{name}: mode must be 'bilinear' or 'bicubic', got {mode!r}")
+    if mode not in run_options.WARP_MODES:
+        raise ValueError(f"{name}: mode must be {either(run_options.WARP_MODES)}, got {mode!r}")
     return mode == "bicubic"
 
 
@@ -374,13 +373,13 @@ def resize_bilinear_nhwc(x, c, hin, win, hout, wout):
 MSSSIM_WEIGHTS = (0.0448, 0.2856, 0.3001, 0.2363, 0.1333)
 MSSSIM_MIN_SIDE = 176          # the fifth scale must still hold one full 11 x 11 window
 MSSSIM_AREA = 598400           # working size of the DocUNet benchmark protocol, in pixels
-_SSIM_PRESETS = {"docunet": lib.MSSSIM_DOCUNET, "wang": lib.MSSSIM_WANG}
+_SSIM_PRESETS = dict(zip(run_options.METRIC_PRESETS, (lib.MSSSIM_DOCUNET, lib.MSSSIM_WANG)))
 
 
 def _ssim_preset(preset, name):
     """The metric's preset: checked before anything is allocated or launched."""
     if preset not in _SSIM_PRESETS:
-        raise ValueError(f"{name}: preset must be 'docunet' or 'wang', got {preset!r}")
+        raise ValueError(f"{name}: preset must be {either(_SSIM_PRESETS)}, got {preset!r}")
     return _SSIM_PRESETS[preset]
 
 
@@ -491,13 +490,13 @@ def png_bound(h: int, w: int) -> int:
     return _size_query("dvd_png_bound", h, w)
 
 
-PNG_HUFFMAN = {"fixed": lib.PNG_HUFFMAN_FIXED, "dynamic": lib.PNG_HUFFMAN_DYNAMIC}
+PNG_HUFFMAN = dict(zip(run_options.PNG_HUFFMAN, (lib.PNG_HUFFMAN_FIXED, lib.PNG_HUFFMAN_DYNAMIC)))
 
 
 def png_huffman_flag(huffman, name="png_encode"):
     """The library's DVD_PNG_HUFFMAN_* flag of 'fixed' | 'dynamic', or ValueError."""
     if not isinstance(huffman, str) or huffman not in PNG_HUFFMAN:
-        raise ValueError(f"{name}: huffman must be 'fixed' or 'dynamic', got {huffman!r}")
+        raise ValueError(f"{name}: huffman must be {either(PNG_HUFFMAN)}, got {huffman!r}")
     return PNG_HUFFMAN[huffman]
 
 
@@ -528,15 +527,15 @@ def png_encode_to_file(img_hwc_u8: torch.Tensor, path: str, huffman: str = "fixe
 
 
 # ---- JPEG of a dewarped page, encoded on the device (dvd_amd/csrc/jpeg.hip; format: DESIGN.md 4.5) ----------------------------
-JPEG_SUBSAMPLINGS = {"420": lib.JPEG_420, "444": lib.JPEG_444}
+JPEG_SUBSAMPLINGS = dict(zip(run_options.JPEG_SUBSAMPLINGS, (lib.JPEG_420, lib.JPEG_444)))
 
 
 def jpeg_settings(quality, subsampling, name="jpeg_encode"):
     """(quality, the library's subsampling flag), or ValueError: quality an integer 1..100, subsampling '420' | '444'."""
-    if isinstance(quality, bool) or not isinstance(quality, (int, np.integer)) or not 1 <= quality <= 100:
+    if not run_options.is_jpeg_quality(quality):
         raise ValueError(f"{name}: quality must be an integer 1..100, got {quality!r}")
     if subsampling not in JPEG_SUBSAMPLINGS:
-        raise ValueError(f"{name}: subsampling must be '420' or '444', got {subsampling!r}")
+        raise ValueError(f"{name}: subsampling must be {either(JPEG_SUBSAMPLINGS)}, got {subsampling!r}")
     return int(quality), JPEG_SUBSAMPLINGS[subsampling]
 
 
@@ -570,18 +569,46 @@ def jpeg_encode_to_file(img_hwc_u8: torch.Tensor, path: str, quality: int = 90, 
     return _device_bytes_to_file(jpeg_encode(img_hwc_u8, quality, subsampling), path)
 
 
-# ---- JPEG decoder for the input photograph (dvd_amd/csrc/jpegdec.hip; definition: DESIGN.md 4.6) ------------------------------
-class JpegUnsupported(ValueError):
-    """The device decoder hands the file back: a refusal of the host-side header check (progressive, 4 components, ...), or
-    NOSYNC / DATA after the entropy decoder ran.  `code` is the name of the library's DVD_E_JPEG_* code.  A normal outcome:
-    decode_image falls back to PIL."""
+# ---- decoders for the input photograph and the ground-truth scans: JPEG (dvd_amd/csrc/jpegdec.hip; definition: DESIGN.md 4.6) and
+# ---- PNG (dvd_amd/csrc/pngdec.hip; definition: DESIGN.md 4.9) ---------------------------------------------------------------
+PNG_SIGNATURE = lib.PNG_SIGNATURE
+
+
+class DecodeUnsupported(ValueError):
+    """A device decoder hands the file back.  `code` is the name of the library's code.  A normal outcome: decode_image falls
+    back to PIL."""
 
     def __init__(self, code: str, message: str):
         super().__init__(f"{code}: {message}")
         self.code = code
 
 
-def _jpeg_file(data, name):
+class JpegUnsupported(DecodeUnsupported):
+    """A refusal of the host-side header check (progressive, 4 components, ...), or NOSYNC / DATA after the entropy decoder
+    ran.  `code` names a DVD_E_JPEG_* code."""
+
+
+class PngUnsupported(DecodeUnsupported):
+    """A refusal of the host-side chunk check (interlace, palette, tRNS, ...), or DATA / NOSPLIT after the inflate ran.
+    `code` names a DVD_E_PNG_* code."""
+
+
+class _Codec(NamedTuple):
+    """What tells the two decoders apart: the probe's struct (its name in lib), the library's entry points, the codes that
+    mean 'handed back' and their exception, and the probe's fields that give the decoded image's height and width."""
+    info: str
+    probe: str
+    decode: str
+    codes: dict
+    unsupported: type
+    dims: tuple
+
+
+_JPEG = _Codec("JpegDecInfo", "dvd_jpegdec_probe", "dvd_jpeg_decode_rgb8", lib.JPEG_DECODE_CODES, JpegUnsupported, ("out_h", "out_w"))
+_PNG = _Codec("PngDecInfo", "dvd_pngdec_probe", "dvd_png_decode_rgb8", lib.PNG_DECODE_CODES, PngUnsupported, ("h", "w"))
+
+
+def _image_file(data, name):
     """The file as (host uint8 array, the caller's device tensor or None)."""
     if torch.is_tensor(data):
         if data.dtype != torch.uint8 or data.dim() != 1 or not data.is_contiguous():
@@ -599,27 +626,57 @@ def _jpeg_file(data, name):
     return host, dev
 
 
-def _jpeg_status(name, rc):
+def _decode_status(codec, name, rc):
     if rc == 0:
         return
     message = lib.raw().dvd_last_error().decode()
-    if rc in lib.JPEG_DECODE_CODES:
-        raise JpegUnsupported(lib.JPEG_DECODE_CODES[rc], message)
+    if rc in codec.codes:
+        raise codec.unsupported(codec.codes[rc], message)
     raise lib.DvdError(f"{name} failed ({rc}): {message}")
 
 
-def _jpeg_probe(host, name):
-    info = lib.JpegDecInfo()
-    _jpeg_status(name, lib.raw().dvd_jpegdec_probe(C.c_void_p(host.ctypes.data), host.size, C.byref(info)))
+def _probe(codec, host, name):
+    info = getattr(lib, codec.info)()
+    _decode_status(codec, name, getattr(lib.raw(), codec.probe)(C.c_void_p(host.ctypes.data), host.size, C.byref(info)))
     return info
+
+
+def _fields(struct) -> dict:
+    return {k: int(getattr(struct, k)) for k, _ in struct._fields_}
+
+
+def _decode(codec, name, data, device, cap, cap_name, result, scratch, out):
+    """What jpeg_decode and png_decode share: the file argument, the check of the cap (a positive integer or None), the probe,
+    the file on the device, the scratch and `out` checks, the library call - which fills `result`, a ctypes object - and the
+    [H,W,3] view of `out`."""
+    host, dev_file = _image_file(data, name)
+    if cap is not None and (isinstance(cap, bool) or not isinstance(cap, (int, np.integer)) or cap < 1):
+        raise ValueError(f"{name}: {cap_name} must be a positive integer or None, got {cap!r}")
+    info = _probe(codec, host, name)
+    if dev_file is None:
+        dev_file = torch.from_numpy(host).to(torch.device("cuda") if device is None else device)
+    elif device is not None and torch.device(device) != dev_file.device:
+        dev_file = dev_file.to(device)
+    dev = dev_file.device
+    _chk(dev_file, torch.uint8, "file")
+    need, numel = int(info.scratch_bytes), 3 * info.h * info.w
+    scratch = _scratch(scratch, need, dev, name)
+    if out is None:
+        out = torch.empty(numel, dtype=torch.uint8, device=dev)
+    elif out.dtype != torch.uint8 or not out.is_contiguous() or out.numel() < numel or out.device != dev:
+        raise ValueError(f"{name}: out must be a contiguous uint8 tensor of >= {numel} elements on {dev}")
+    with torch.cuda.device(dev):
+        rc = getattr(lib.raw(), codec.decode)(C.c_void_p(host.ctypes.data), ptr(dev_file), host.size, ptr(out), out.numel(),
+                                              0 if cap is None else int(cap), C.byref(result), ptr(scratch), stream_ptr())
+    _decode_status(codec, codec.decode, rc)
+    return out.view(-1)[:numel].view(*(getattr(info, k) for k in codec.dims), 3)
 
 
 def jpeg_probe(data) -> dict:
     """What the decoder reads from the header of a JPEG file (bytes or a 1-D uint8 tensor), on the host: h, w, out_h, out_w
     (after the EXIF orientation), components, hs, vs, orientation, restart_interval, scan_offset, scan_bytes, blocks,
     scratch_bytes.  Raises JpegUnsupported for a file the device decoder refuses."""
-    info = _jpeg_probe(_jpeg_file(data, "jpeg_probe")[0], "jpeg_probe")
-    return {k: int(getattr(info, k)) for k, _ in lib.JpegDecInfo._fields_}
+    return _fields(_probe(_JPEG, _image_file(data, "jpeg_probe")[0], "jpeg_probe"))
 
 
 def jpeg_decode(data, device=None, max_iters: int = None, scratch: torch.Tensor = None, out: torch.Tensor = None,
@@ -632,28 +689,8 @@ def jpeg_decode(data, device=None, max_iters: int = None, scratch: torch.Tensor 
     return_iters: also return how many iterations ran.  Raises JpegUnsupported (a ValueError) for a file the decoder
     refuses, for 'NOSYNC' (max_iters reached) and for 'DATA' (the scan does not hold the header's blocks).  The call
     synchronises its stream (dvd_hip.h: every 16 iterations and once after the count pass)."""
-    host, dev_file = _jpeg_file(data, "jpeg_decode")
-    if max_iters is not None and (isinstance(max_iters, bool) or not isinstance(max_iters, (int, np.integer)) or max_iters < 1):
-        raise ValueError(f"jpeg_decode: max_iters must be a positive integer or None, got {max_iters!r}")
-    info = _jpeg_probe(host, "jpeg_decode")
-    if dev_file is None:
-        dev_file = torch.from_numpy(host).to(torch.device("cuda") if device is None else device)
-    elif device is not None and torch.device(device) != dev_file.device:
-        dev_file = dev_file.to(device)
-    dev = dev_file.device
-    _chk(dev_file, torch.uint8, "file")
-    need, numel = int(info.scratch_bytes), 3 * info.h * info.w
-    scratch = _scratch(scratch, need, dev, "jpeg_decode")
-    if out is None:
-        out = torch.empty(numel, dtype=torch.uint8, device=dev)
-    elif out.dtype != torch.uint8 or not out.is_contiguous() or out.numel() < numel or out.device != dev:
-        raise ValueError(f"jpeg_decode: out must be a contiguous uint8 tensor of >= {numel} elements on {dev}")
     iters = C.c_int(0)
-    with torch.cuda.device(dev):
-        rc = lib.raw().dvd_jpeg_decode_rgb8(C.c_void_p(host.ctypes.data), ptr(dev_file), host.size, ptr(out), out.numel(),
-                                            0 if max_iters is None else int(max_iters), C.byref(iters), ptr(scratch), stream_ptr())
-    _jpeg_status("dvd_jpeg_decode_rgb8", rc)
-    img = out.view(-1)[:numel].view(info.out_h, info.out_w, 3)
+    img = _decode(_JPEG, "jpeg_decode", data, device, max_iters, "max_iters", iters, scratch, out)
     return (img, int(iters.value)) if return_iters else img
 
 
@@ -672,40 +709,10 @@ def pil_decode_rgb8(path_or_bytes) -> np.ndarray:
     return np.array(im.convert("RGB"), dtype=np.uint8)       # a writable, contiguous copy
 
 
-# ---- PNG decoder for input photographs and ground-truth scans (dvd_amd/csrc/pngdec.hip; definition: DESIGN.md 4.9) ------------
-PNG_SIGNATURE = lib.PNG_SIGNATURE
-
-
-class PngUnsupported(ValueError):
-    """The device decoder hands the file back: a refusal of the host-side chunk check (interlace, palette, tRNS, ...), or
-    DATA / NOSPLIT after the inflate ran.  `code` is the name of the library's DVD_E_PNG_* code.  A normal outcome:
-    decode_image(png=True) falls back to PIL."""
-
-    def __init__(self, code: str, message: str):
-        super().__init__(f"{code}: {message}")
-        self.code = code
-
-
-def _png_status(name, rc):
-    if rc == 0:
-        return
-    message = lib.raw().dvd_last_error().decode()
-    if rc in lib.PNG_DECODE_CODES:
-        raise PngUnsupported(lib.PNG_DECODE_CODES[rc], message)
-    raise lib.DvdError(f"{name} failed ({rc}): {message}")
-
-
-def _png_probe(host, name):
-    info = lib.PngDecInfo()
-    _png_status(name, lib.raw().dvd_pngdec_probe(C.c_void_p(host.ctypes.data), host.size, C.byref(info)))
-    return info
-
-
 def png_probe(data) -> dict:
     """What the decoder reads from the chunks of a PNG file (bytes or a 1-D uint8 tensor), on the host: h, w, colour_type,
     bpp, idat_chunks, payload_bytes, scratch_bytes.  Raises PngUnsupported for a file the device decoder refuses."""
-    info = _png_probe(_jpeg_file(data, "png_probe")[0], "png_probe")
-    return {k: int(getattr(info, k)) for k, _ in lib.PngDecInfo._fields_}
+    return _fields(_probe(_PNG, _image_file(data, "png_probe")[0], "png_probe"))
 
 
 def png_decode(data, device=None, max_work: int = None, scratch: torch.Tensor = None, out: torch.Tensor = None,
@@ -718,31 +725,9 @@ def png_decode(data, device=None, max_work: int = None, scratch: torch.Tensor = 
     return_stats: also return {'candidates', 'segments', 'rounds', 'bands'}.  Raises PngUnsupported (a ValueError) for a
     file the decoder refuses, for 'DATA' (damaged data, a checksum mismatch) and for 'NOSPLIT' (max_work reached); `out` is
     untouched then.  The call synchronises its stream (dvd_hip.h says where)."""
-    host, dev_file = _jpeg_file(data, "png_decode")
-    if max_work is not None and (isinstance(max_work, bool) or not isinstance(max_work, (int, np.integer)) or max_work < 1):
-        raise ValueError(f"png_decode: max_work must be a positive integer or None, got {max_work!r}")
-    info = _png_probe(host, "png_decode")
-    if dev_file is None:
-        dev_file = torch.from_numpy(host).to(torch.device("cuda") if device is None else device)
-    elif device is not None and torch.device(device) != dev_file.device:
-        dev_file = dev_file.to(device)
-    dev = dev_file.device
-    _chk(dev_file, torch.uint8, "file")
-    need, numel = int(info.scratch_bytes), 3 * info.h * info.w
-    scratch = _scratch(scratch, need, dev, "png_decode")
-    if out is None:
-        out = torch.empty(numel, dtype=torch.uint8, device=dev)
-    elif out.dtype != torch.uint8 or not out.is_contiguous() or out.numel() < numel or out.device != dev:
-        raise ValueError(f"png_decode: out must be a contiguous uint8 tensor of >= {numel} elements on {dev}")
     stats = lib.PngDecStats()
-    with torch.cuda.device(dev):
-        rc = lib.raw().dvd_png_decode_rgb8(C.c_void_p(host.ctypes.data), ptr(dev_file), host.size, ptr(out), out.numel(),
-                                           0 if max_work is None else int(max_work), C.byref(stats), ptr(scratch), stream_ptr())
-    _png_status("dvd_png_decode_rgb8", rc)
-    img = out.view(-1)[:numel].view(info.h, info.w, 3)
-    if return_stats:
-        return img, {k: int(getattr(stats, k)) for k, _ in lib.PngDecStats._fields_}
-    return img
+    img = _decode(_PNG, "png_decode", data, device, max_work, "max_work", stats, scratch, out)
+    return (img, _fields(stats)) if return_stats else img
 
 
 def png_decode_from_file(path: str, device=None, max_work: int = None) -> torch.Tensor:
@@ -1021,7 +1006,7 @@ def ad_u8(pred_hwc_u8: torch.Tensor, gt_hwc_u8: torch.Tensor, area: int = MSSSIM
     return float(aligned_distortion(y, x, **params)[0][0])
 
 
-GT_METRIC_NAMES = ("ms_ssim", "ld", "ad")
+GT_METRIC_NAMES = run_options.GT_METRICS + ("ad",)
 
 
 def gt_metrics_u8(pred_hwc_u8: torch.Tensor, gt_hwc_u8: torch.Tensor, metrics, preset: str = "docunet",

@@ -10,7 +10,7 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
-from . import dist_util, logger, synth
+from . import dist_util, logger, run_options, synth
 from .evaluation import npz_documents, run_evaluation_docunet, synthetic_documents
 from .script_util import args_to_dict, create_model_and_diffusion, model_and_diffusion_defaults
 
@@ -23,7 +23,7 @@ def get_parameter_number(net):
 def _want_synthetic_weights(env):
     """Synthetic stand-in weights are for the synthetic benchmark only: a mistyped checkpoint path on a real dataset
     must fail, not write plausible-looking garbage where the reference writes its results."""
-    flag = getattr(env, "synthetic_weights_if_missing", None)
+    flag = run_options.read(env, "synthetic_weights_if_missing")
     return env.eval_dataset_name == "synthetic" if flag is None else bool(flag)
 
 
@@ -46,7 +46,7 @@ def run(settings):
                 logger.log(f"Model loaded with {env.model_path}")
             elif _want_synthetic_weights(env):
                 sd = synth.synth_state_dict(env.grid_size, seed=7)
-                model.load_state_dict({k: torch.from_numpy(np.asarray(v)) for k, v in sd.items()}, strict=True)
+                model.load_state_dict(_tensors(sd), strict=True)
                 logger.log(f"{env.model_path} not found: using deterministic synthetic weights (seed 7)")
             else:
                 raise FileNotFoundError(f"{env.model_path} (set env.synthetic_weights_if_missing=True to sample with "
@@ -79,11 +79,11 @@ def run(settings):
         # the workers only decode (PIL); uint8 CHW crosses PCIe (the reference ships float32: get_float=True), the
         # resize to 512 x 512 and everything after it runs on the GPU.  Unshuffled: rank r owns files r, r+world, ...
         test_set = datasets.Doc_benchmark(env.eval_dataset, ArrayToTensor(get_float=False),
-                                          decode=getattr(env, "image_decoder", "pil"),
-                                          decode_png=getattr(env, "png_decoder", "pil"))
+                                          decode=run_options.read(env, "image_decoder"),
+                                          decode_png=run_options.read(env, "png_decoder"))
         mine = dist_util.shard_documents(len(test_set))
         documents = DataLoader(Subset(test_set, list(mine)), batch_size=1, shuffle=False, drop_last=False,
-                               num_workers=int(getattr(env, "num_workers", 0)))
+                               num_workers=int(run_options.read(env, "num_workers")))
     logger.info(f"rank {dist_util.rank()}/{dist_util.world_size()}: {len(mine)} documents")
     logger.info("Starting sampling")
     dewarp, seg, line = pre if pre is not None else (None, None, None)
@@ -100,7 +100,7 @@ def load_prestage(env):
     """The pre-stage models of a run as (dewarp, seg, line) or None: the three nets under env.use_prestage_nets; under
     env.use_init_flow also GeoTr inside the dewarp model (with the other nets off: the dewarp model alone).  COLLECTIVE:
     a failure on rank 0 raises on every rank."""
-    use_nets, use_init_flow = bool(getattr(env, "use_prestage_nets", False)), bool(getattr(env, "use_init_flow", False))
+    use_nets, use_init_flow = bool(run_options.read(env, "use_prestage_nets")), bool(env.use_init_flow)
     if not (use_nets or use_init_flow):
         return None
     pre, failure = None, None
@@ -118,7 +118,7 @@ def blob_models(model, pre, env):
     """The models of the one flat weight broadcast, in order: the denoiser, the loaded pre-stage nets, then - only under
     env.use_init_flow - GeoTr (once)."""
     out = [model] + [m for m in (pre or ()) if m is not None]
-    if getattr(env, "use_init_flow", False):
+    if env.use_init_flow:
         out.append(pre[0].GeoTr)
     return out
 
@@ -130,37 +130,34 @@ def load_prestage_models(env):
     from .prestage import GeoTr_Seg_Inf, Seg, UNet, reload_segmodel
     dewarp, line, seg = GeoTr_Seg_Inf(), UNet(n_channels=3, n_classes=1), Seg()
     if dist_util.rank() == 0:
-        def tt(sd):
-            return {k: torch.from_numpy(np.asarray(v)) for k, v in sd.items()}
-        jobs = ((env.seg_model_path, lambda p: reload_segmodel(dewarp.msk, p),
-                 lambda: dewarp.msk.load_state_dict(tt(synth.synth_convnet_state_dict("u2netp", 11)), strict=True)),
-                (env.line_seg_model_path,
-                 lambda p: line.load_state_dict(dist_util.load_state_dict(p, map_location="cpu")["model"], strict=True),
-                 lambda: line.load_state_dict(tt(synth.synth_convnet_state_dict("unet", 13)), strict=True)),
-                (env.new_seg_model_path,
-                 lambda p: seg.load_state_dict(dist_util.load_state_dict(p, map_location="cpu")["model"], strict=True),
-                 lambda: seg.load_state_dict(tt(synth.synth_convnet_state_dict("u2netp", 22, prefix="msk.")), strict=True)))
-        for path, from_file, synthetic in jobs:
-            if os.path.exists(path):
-                from_file(path)
-                logger.log(f"loaded {path}")
-            elif _want_synthetic_weights(env):
-                synthetic()
-                logger.log(f"{path} not found: using deterministic synthetic weights")
-            else:
-                raise FileNotFoundError(path)
+        _load_or_synthesize(dewarp.msk, env.seg_model_path, reload_segmodel, lambda: synth.synth_convnet_state_dict("u2netp", 11), env)
+        _load_or_synthesize(line, env.line_seg_model_path, _load_model_entry, lambda: synth.synth_convnet_state_dict("unet", 13), env)
+        _load_or_synthesize(seg, env.new_seg_model_path, _load_model_entry,
+                            lambda: synth.synth_convnet_state_dict("u2netp", 22, prefix="msk."), env)
     for m in (dewarp, seg, line):
         m.to(dist_util.dev())
         m.eval()
     return dewarp, seg, line
 
 
-def _load_or_synthesize(path, from_file, synthetic, env):
+def _tensors(state_dict):
+    """A synthetic state dict (NumPy arrays) as tensors."""
+    return {k: torch.from_numpy(np.asarray(v)) for k, v in state_dict.items()}
+
+
+def _load_model_entry(net, path):
+    """A {'model': state_dict} checkpoint, strictly (val_TDiff.py:64-75)."""
+    net.load_state_dict(dist_util.load_state_dict(path, map_location="cpu")["model"], strict=True)
+
+
+def _load_or_synthesize(net, path, from_file, synthetic, env):
+    """net's weights: from_file(net, path) when the checkpoint exists; else, where synthetic weights are allowed, the state
+    dict synthetic() makes, strictly; else FileNotFoundError."""
     if os.path.exists(path):
-        from_file(path)
+        from_file(net, path)
         logger.log(f"loaded {path}")
     elif _want_synthetic_weights(env):
-        synthetic()
+        net.load_state_dict(_tensors(synthetic()), strict=True)
         logger.log(f"{path} not found: using deterministic synthetic weights")
     else:
         raise FileNotFoundError(path)
@@ -172,10 +169,7 @@ def load_dewarp_model(env):
     from .prestage import GeoTr_Seg_Inf, reload_segmodel
     dewarp = GeoTr_Seg_Inf()
     if dist_util.rank() == 0:
-        _load_or_synthesize(env.seg_model_path, lambda p: reload_segmodel(dewarp.msk, p),
-                            lambda: dewarp.msk.load_state_dict(
-                                {k: torch.from_numpy(np.asarray(v)) for k, v in synth.synth_convnet_state_dict("u2netp", 11).items()},
-                                strict=True), env)
+        _load_or_synthesize(dewarp.msk, env.seg_model_path, reload_segmodel, lambda: synth.synth_convnet_state_dict("u2netp", 11), env)
     dewarp.to(dist_util.dev())
     dewarp.eval()
     return dewarp
@@ -188,11 +182,8 @@ def load_geotr(dewarp, env):
     from .prestage import reload_model
     geo = dewarp.GeoTr
     if dist_util.rank() == 0:
-        path = getattr(env, "dewarping_model_path", "") or ""
-        _load_or_synthesize(path, lambda p: reload_model(geo, p),
-                            lambda: geo.load_state_dict({k: torch.from_numpy(np.asarray(v))
-                                                         for k, v in synth.synth_geotr_state_dict(31).items()}, strict=True),
-                            env)
+        _load_or_synthesize(geo, run_options.read(env, "dewarping_model_path") or "", reload_model,
+                            lambda: synth.synth_geotr_state_dict(31), env)
     geo.to(dist_util.dev())
     geo.eval()
     return geo

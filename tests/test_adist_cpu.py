@@ -318,23 +318,3 @@ def test_ops_argument_checks_need_no_gpu():
     for call in (lambda: ops.ad_fit(f), lambda: ops.ad_align(p, c), lambda: ops.ad_weighted(p[:1], f), lambda: ops.aligned_distortion(x, x)):
         with pytest.raises(lib.DvdError, match="device tensor"):              # good arguments on the host: there is no CPU path
             call()
-
-
-def test_gt_ad_setting(tmp_path, monkeypatch):
-    import admin.settings as ws
-    from dvd_amd import logger
-    from train_settings.dvd.evaluation import run_evaluation_docunet
-    assert ws.Settings().env.gt_ad is False                                  # the default: what a run scored before
-    monkeypatch.chdir(tmp_path)
-
-    def loader():
-        raise AssertionError("the loader was read")
-        yield
-
-    s = ws.Settings()
-    s.name = "pytest_adist"
-    for bad in ("yes", 1, 0, None, "ad", ("ad",)):
-        s.env.gt_ad = bad
-        with pytest.raises(ValueError, match="env.gt_ad"):                    # before the first document, with or without gt_dir
-            run_evaluation_docunet(s, logger, loader(), None, torch.nn.Linear(1, 1), None)
-    assert list(tmp_path.iterdir()) == []

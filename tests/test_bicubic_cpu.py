@@ -75,21 +75,3 @@ def test_ops_refuse_an_unknown_mode_before_any_launch():
             ops.unwarp_u8_batch(flow, img[None], mode=bad)
         with pytest.raises(ValueError, match="'bilinear' or 'bicubic'"):
             ops.unwarp_u8_ragged(flow, [img], mode=bad)
-
-
-def test_run_evaluation_docunet_refuses_a_bad_unwarp_mode(tmp_path, monkeypatch):
-    """env.unwarp_mode is validated once, before the loader is touched and before anything is written."""
-    import admin.settings as ws
-    from dvd_amd import logger
-    from train_settings.dvd.evaluation import run_evaluation_docunet
-    monkeypatch.chdir(tmp_path)
-    s = ws.Settings()
-    assert s.env.unwarp_mode == "bilinear"
-    s.name, s.env.unwarp_mode = "pytest_bicubic", "nearest"
-
-    def loader():
-        raise AssertionError("the loader was read")
-        yield
-    with pytest.raises(ValueError, match="'bilinear' or 'bicubic'"):
-        run_evaluation_docunet(s, logger, loader(), None, torch.nn.Linear(1, 1), None)
-    assert list(tmp_path.iterdir()) == []

@@ -211,33 +211,6 @@ def test_fidelity_and_size_against_pil(pages, kind, quality, subsampling):
 
 
 # ---- 6. settings --------------------------------------------------------------------------------------------------------------
-def _loader():
-    raise AssertionError("the loader was read")
-    yield
-
-
-@pytest.mark.parametrize("key,value,text", [("page_format", "tiff", "env.page_format"), ("jpeg_quality", 0, "env.jpeg_quality"),
-                                            ("jpeg_quality", 101, "env.jpeg_quality"), ("jpeg_subsampling", "422", "env.jpeg_subsampling")],
-                         ids=lambda v: str(v))
-def test_env_validation(tmp_path, monkeypatch, key, value, text):
-    """Refused before the loader is touched and before anything is written - by run_evaluation_docunet and by
-    visualize_dewarping itself - with the setting's name in the message."""
-    import admin.settings as ws
-    from dvd_amd import logger
-    from train_settings.dvd.evaluation import run_evaluation_docunet
-    from utils_flow.visualization_utils import visualize_dewarping
-    monkeypatch.chdir(tmp_path)
-    s = ws.Settings()
-    assert (s.env.page_format, s.env.jpeg_quality, s.env.jpeg_subsampling) == ("png", 90, "420")
-    s.name, s.env.page_format = "pytest_jpeg", "jpeg"
-    setattr(s.env, key, value)
-    with pytest.raises(ValueError, match=text):
-        run_evaluation_docunet(s, logger, _loader(), None, torch.nn.Linear(1, 1), None)
-    with pytest.raises(ValueError, match=text):
-        visualize_dewarping(s, None, None, 0, None, ["a.png"], warped_u8=np.zeros((2, 2, 3), np.uint8))
-    assert list(tmp_path.iterdir()) == []
-
-
 def test_defaults_write_the_same_png_as_before(tmp_path, monkeypatch):
     """page_format 'png' is the code as it was: warped_<stem>.png holds Image.save's bytes and nothing else is written."""
     import admin.settings as ws

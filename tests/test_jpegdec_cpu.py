@@ -305,24 +305,12 @@ def test_argument_checks_need_no_gpu():
 
 
 # ---- 4. the setting and the loader --------------------------------------------------------------------------------------------
-def _loader():
-    raise AssertionError("the loader was read")
-    yield
-
-
-def test_env_validation(tmp_path, monkeypatch):
+def test_env_validation(tmp_path):
+    """The loader's own check of `decode` (the run's check of env.image_decoder: tests/test_run_options_cpu.py)."""
     import admin.settings as ws
-    from dvd_amd import logger
-    from train_settings.dvd.evaluation import run_evaluation_docunet
     import datasets
-    monkeypatch.chdir(tmp_path)
-    s = ws.Settings()
-    assert s.env.image_decoder == "pil"
-    s.name = "pytest_jpegdec"
+    assert ws.Settings().env.image_decoder == "pil"
     for bad in ("cuda", "", None, "HIP"):
-        s.env.image_decoder = bad
-        with pytest.raises(ValueError, match="env.image_decoder"):
-            run_evaluation_docunet(s, logger, _loader(), None, torch.nn.Linear(1, 1), None)
         with pytest.raises(ValueError, match="decode"):
             datasets.Doc_benchmark(str(tmp_path), None, decode=bad)
     assert list(tmp_path.iterdir()) == []

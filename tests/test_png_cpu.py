@@ -109,28 +109,6 @@ def test_ops_png_encode_rejects_bad_input_with_valueerror():
     assert ops.png_bound(4, 5) == P.bound(4, 5, S)
 
 
-def test_env_default_and_validation(tmp_path, monkeypatch):
-    """env.png_encoder defaults to 'pil'; any other value than 'pil' / 'hip' is refused before the loader is touched and before
-    anything is written - by run_evaluation_docunet and by visualize_dewarping itself."""
-    import admin.settings as ws
-    from dvd_amd import logger
-    from train_settings.dvd.evaluation import run_evaluation_docunet
-    from utils_flow.visualization_utils import visualize_dewarping
-    monkeypatch.chdir(tmp_path)
-    s = ws.Settings()
-    assert s.env.png_encoder == "pil"
-    s.name, s.env.png_encoder = "pytest_png", "zlib"
-
-    def loader():
-        raise AssertionError("the loader was read")
-        yield
-    with pytest.raises(ValueError, match="'pil' or 'hip'"):
-        run_evaluation_docunet(s, logger, loader(), None, torch.nn.Linear(1, 1), None)
-    with pytest.raises(ValueError, match="'pil' or 'hip'"):
-        visualize_dewarping(s, None, None, 0, None, ["a.png"], warped_u8=np.zeros((2, 2, 3), np.uint8))
-    assert list(tmp_path.iterdir()) == []
-
-
 def test_pil_route_writes_image_save_bytes(tmp_path, monkeypatch):
     """'pil' is the code as it was: the file holds Image.save's bytes."""
     import io

@@ -248,25 +248,3 @@ def test_bad_huffman_is_refused_without_a_gpu():
         with pytest.raises(ValueError, match="'fixed' or 'dynamic'"):
             ops.png_encode_to_file(good, "never_written.png", huffman=bad)
     assert not os.path.exists("never_written.png")
-
-
-def test_env_png_huffman_default_and_validation(tmp_path, monkeypatch):
-    """env.png_huffman defaults to 'fixed'; any other value than 'fixed' / 'dynamic' is refused before the loader is touched
-    and before anything is written - by run_evaluation_docunet and by visualize_dewarping itself."""
-    import admin.settings as ws
-    from dvd_amd import logger
-    from train_settings.dvd.evaluation import run_evaluation_docunet
-    from utils_flow.visualization_utils import visualize_dewarping
-    monkeypatch.chdir(tmp_path)
-    s = ws.Settings()
-    assert s.env.png_huffman == "fixed"
-    s.name, s.env.png_encoder, s.env.png_huffman = "pytest_png_dyn", "hip", "optimal"
-
-    def loader():
-        raise AssertionError("the loader was read")
-        yield
-    with pytest.raises(ValueError, match="env.png_huffman must be 'fixed' or 'dynamic'"):
-        run_evaluation_docunet(s, logger, loader(), None, torch.nn.Linear(1, 1), None)
-    with pytest.raises(ValueError, match="env.png_huffman must be 'fixed' or 'dynamic'"):
-        visualize_dewarping(s, None, None, 0, None, ["a.png"], warped_u8=np.zeros((2, 2, 3), np.uint8))
-    assert list(tmp_path.iterdir()) == []

@@ -183,24 +183,12 @@ def test_probe_and_argument_checks():
 
 
 # ---- 4. the setting and the loader --------------------------------------------------------------------------------------------
-def _loader():
-    raise AssertionError("the loader was read")
-    yield
-
-
-def test_env_validation(tmp_path, monkeypatch):
+def test_env_validation(tmp_path):
+    """The loader's own check of `decode_png` (the run's check of env.png_decoder: tests/test_run_options_cpu.py)."""
     import admin.settings as ws
     import datasets
-    from dvd_amd import logger
-    from train_settings.dvd.evaluation import run_evaluation_docunet
-    monkeypatch.chdir(tmp_path)
-    s = ws.Settings()
-    assert s.env.png_decoder == "pil"
-    s.name = "pytest_pngdec"
+    assert ws.Settings().env.png_decoder == "pil"
     for bad in ("cuda", "", None, "HIP"):
-        s.env.png_decoder = bad
-        with pytest.raises(ValueError, match="env.png_decoder"):
-            run_evaluation_docunet(s, logger, _loader(), None, torch.nn.Linear(1, 1), None)
         with pytest.raises(ValueError, match="decode_png"):
             datasets.Doc_benchmark(str(tmp_path), None, decode_png=bad)
     assert list(tmp_path.iterdir()) == []

@@ -241,27 +241,14 @@ def test_ops_argument_checks_need_no_gpu():
     assert {f: getattr(pr, f) for f in M.FIELDS} == M.DEFAULTS
 
 
-def test_gt_metrics_setting(tmp_path, monkeypatch):
+def test_gt_metrics_setting():
+    """parse_gt_metrics itself (the run's check of env.gt_metrics: tests/test_run_options_cpu.py)."""
     import admin.settings as ws
-    from dvd_amd import logger
     from dvd_amd.evaluation import parse_gt_metrics
-    from train_settings.dvd.evaluation import run_evaluation_docunet
     assert ws.Settings().env.gt_metrics == "ms_ssim"                         # the default: what a run scored before
     assert parse_gt_metrics("ms_ssim") == ("ms_ssim",)
     assert parse_gt_metrics("ms_ssim,ld") == parse_gt_metrics("ld, ms_ssim") == ("ms_ssim", "ld")
     assert parse_gt_metrics("ld") == ("ld",)
-    monkeypatch.chdir(tmp_path)
-
-    def loader():
-        raise AssertionError("the loader was read")
-        yield
-
-    s = ws.Settings()
-    s.name = "pytest_sflow"
     for bad in ("", "ssim", "ms_ssim,ad", "ld,ld", "ms_ssim;ld", None, ("ld",)):
         with pytest.raises(ValueError, match="env.gt_metrics"):
             parse_gt_metrics(bad)
-        s.env.gt_metrics = bad
-        with pytest.raises(ValueError, match="env.gt_metrics"):                # before the first document, with or without gt_dir
-            run_evaluation_docunet(s, logger, loader(), None, torch.nn.Linear(1, 1), None)
-    assert list(tmp_path.iterdir()) == []

@@ -11,14 +11,9 @@ on the drop-in HIP kernel (32 B/px).  `dvd_amd.evaluation.run_evaluation_docunet
 fused tail kernel (`dvd_unwarp_u8[_batch]`, 6 B/px: up-sampling, base grid, affine, gather and truncation in one launch) already
 produced from the COARSE flow - bit-identical to the long way (tests/test_gpu_ops.py::test_unwarp_golden, golden G5).
 
-`settings.env.png_encoder` chooses who writes the PNG: 'pil' (default, the reference's Image.save on a host copy of the page) or
-'hip' (`dvd_amd.ops.png_encode_to_file`: filtered and compressed where the page lies, only the file crosses to the host - the
-same pixels in a file of other bytes).  With 'hip', `settings.env.png_huffman` = 'fixed' (default) | 'dynamic' chooses
-the encoder's deflate blocks: 'dynamic' writes per segment the smaller of a dynamic-Huffman and the fixed block.
-
-`settings.env.page_format = 'jpeg'` (default 'png': all of the above, unchanged) writes `warped_<stem>.jpg` instead: baseline
-JFIF at `env.jpeg_quality` (1..100, default 90) and `env.jpeg_subsampling` ('420' default | '444'), encoded on the device by
-`dvd_amd.ops.jpeg_encode_to_file`; `png_encoder` is not consulted."""
+Who writes the page - PIL on a host copy (the default, the reference's Image.save), `dvd_amd.ops.png_encode_to_file` or, as
+`warped_<stem>.jpg`, `dvd_amd.ops.jpeg_encode_to_file` - is `PageOptions.page_writer`: the switches `png_encoder`, `png_huffman`,
+`page_format`, `jpeg_quality` and `jpeg_subsampling` of dvd_amd/run_options.py, checked here on every call."""
 from __future__ import annotations
 
 import os
@@ -27,34 +22,20 @@ import numpy as np
 from PIL import Image
 
 from datasets.utils.warping import register_model2
+from dvd_amd import run_options
+from dvd_amd.run_options import PageOptions
 
 reg_model_bilin = register_model2((512, 512), "bilinear")
-PNG_ENCODERS = ("pil", "hip")
-PNG_HUFFMAN = ("fixed", "dynamic")
-PAGE_FORMATS = ("png", "jpeg")
-JPEG_SUBSAMPLINGS = ("420", "444")
 
 
 def page_settings(env):
     """(page_format, jpeg_quality, jpeg_subsampling) of `env`, each checked: ValueError names the setting."""
-    fmt = getattr(env, "page_format", "png")
-    quality = getattr(env, "jpeg_quality", 90)
-    subsampling = getattr(env, "jpeg_subsampling", "420")
-    if fmt not in PAGE_FORMATS:
-        raise ValueError(f"env.page_format must be 'png' or 'jpeg', got {fmt!r}")
-    if isinstance(quality, bool) or not isinstance(quality, (int, np.integer)) or not 1 <= quality <= 100:
-        raise ValueError(f"env.jpeg_quality must be an integer 1..100, got {quality!r}")
-    if subsampling not in JPEG_SUBSAMPLINGS:
-        raise ValueError(f"env.jpeg_subsampling must be '420' or '444', got {subsampling!r}")
-    return fmt, int(quality), subsampling
+    return tuple(run_options.check(env, name) for name in ("page_format", "jpeg_quality", "jpeg_subsampling"))
 
 
 def png_huffman_setting(env):
     """env.png_huffman, checked: ValueError names the setting."""
-    huffman = getattr(env, "png_huffman", "fixed")
-    if not isinstance(huffman, str) or huffman not in PNG_HUFFMAN:
-        raise ValueError(f"env.png_huffman must be 'fixed' or 'dynamic', got {huffman!r}")
-    return huffman
+    return run_options.check(env, "png_huffman")
 
 
 def _stem(data_path):
@@ -65,13 +46,8 @@ def _stem(data_path):
 def visualize_dewarping(settings, sample, data, i, source_vis, data_path, ref_flow=None, *, warped_u8=None):
     """Returns the uint8 [H,W,3] image it wrote (the reference returns None): a NumPy array with png_encoder 'pil', the
     DEVICE tensor with 'hip' and with page_format 'jpeg' (the page is never copied to the host there)."""
-    encoder = getattr(settings.env, "png_encoder", "pil")
-    if encoder not in PNG_ENCODERS:
-        raise ValueError(f"env.png_encoder must be 'pil' or 'hip', got {encoder!r}")
-    huffman = png_huffman_setting(settings.env)
-    page_format, quality, subsampling = page_settings(settings.env)
-    if page_format == "jpeg":
-        encoder = "jpeg"                             # the device route below; png_encoder is not consulted
+    opts = PageOptions.from_env(settings.env)
+    encoder = opts.page_writer                   # 'pil' | 'hip' | 'jpeg'
     out_dir = f"vis_hp/{settings.env.eval_dataset_name}/{settings.name}"
     os.makedirs(f"{out_dir}/pred_flow", exist_ok=True)
     os.makedirs(f"{out_dir}/dewarped_pred", exist_ok=True)
@@ -87,9 +63,10 @@ def visualize_dewarping(settings, sample, data, i, source_vis, data_path, ref_fl
             warped_u8 = warped_u8.to(sample.device if sample is not None else "cuda")
         warped_u8 = warped_u8.detach().contiguous()
         if encoder == "jpeg":
-            ops.jpeg_encode_to_file(warped_u8, f"{out_dir}/dewarped_pred/warped_{_stem(data_path)}.jpg", quality, subsampling)
+            ops.jpeg_encode_to_file(warped_u8, f"{out_dir}/dewarped_pred/warped_{_stem(data_path)}.jpg", opts.jpeg_quality,
+                                    opts.jpeg_subsampling)
         else:
-            ops.png_encode_to_file(warped_u8, f"{out_dir}/dewarped_pred/warped_{_stem(data_path)}.png", huffman)
+            ops.png_encode_to_file(warped_u8, f"{out_dir}/dewarped_pred/warped_{_stem(data_path)}.png", opts.png_huffman)
     elif warped_u8 is None:
         warped = reg_model_bilin([source_vis.to(sample.device).float(), sample])
         warped_u8 = warped[0].permute(1, 2, 0).detach().cpu().numpy().astype(np.uint8)
