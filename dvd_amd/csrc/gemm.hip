@@ -2107,31 +2107,50 @@ __global__ void __launch_bounds__(512, 2) gemm_nt_split128_kernel(GemmArgs p) {
 
 using namespace dvd;
 
-#ifdef DVD_LAB
-static unsigned long long* g_gemm_stamps = nullptr;
-// lab builds only (DVD_GEMM_DEBUG=3): where the per-wave s_memtime stamps of the large-tile kernel go
-extern "C" int dvd_gemm_debug_stamps(void* dev_u64) { g_gemm_stamps = (unsigned long long*)dev_u64; return DVD_OK; }
-#endif
-
 namespace {
-// Every kernel dvd_gemm_nt can launch (the lab build's experiments included).
-enum class GemmKernel { split128, split256, t384, big, f32_narrow, ring256, ring128, plain, lab_ring, lab_big16, lab_big2, lab_w8 };
+// THE instance table of this file: the name, the LDS set-up and the launch all come from here (gemm_nt_t384_kernel's
+// instances: gemm_t384_instance; the lab build's experiments: kGemmLab, benchmarks/lab/csrc/gemm_lab.inc).
+enum { SPLIT128 /* + (B_lo != 0) */, SPLIT256 = 2, BIG, F32_NARROW /* + (N > 32) */, RING256 = 6, RING128, PLAIN /* + f32 */, CONV_F32 = 10 };
+const GemmKernel kGemm[] = {
+    // 3 stages x 32 KiB, rounded up to the epilogue's 8 x 16 KiB
+    GEMM_INSTANCE(512, 8 * 16384, 256, 128, true, "gemm_nt(128-wide)", gemm_nt_split128_kernel<false>),
+    GEMM_INSTANCE(512, 8 * 16384, 256, 128, true, "gemm_nt(128-wide)", gemm_nt_split128_kernel<true>),
+    GEMM_INSTANCE(512, 3 * 3 * 256 * 64, 256, 256, true, "gemm_nt(split)", gemm_nt_split_kernel<true>),
+    GEMM_INSTANCE(512, 2 * 2 * 256 * 128, 256, 256, true, "gemm_nt(big)", gemm_nt_big_kernel<0>),
+    GEMM_INSTANCE(256, 0, 128, 64, false, "gemm_nt(f32 narrow)", gemm_f32_narrow_kernel<1>),   // one column tile: N <= 64
+    GEMM_INSTANCE(256, 0, 128, 64, false, "gemm_nt(f32 narrow)", gemm_f32_narrow_kernel<2>),
+    GEMM_INSTANCE(512, 6 * (128 + 256) * 64, 128, 256, false, "gemm_nt(ring256)", gemm_nt_ring256_kernel),
+    GEMM_INSTANCE(256, 5 * 2 * 128 * 128, 128, 128, false, "gemm_nt(ring128)", gemm_nt_ring128_kernel),
+    GEMM_INSTANCE(256, 0, 128, 128, false, "gemm_nt", gemm_nt_kernel<false, 2, false>),
+    GEMM_INSTANCE(256, 0, 128, 128, false, "gemm_nt", gemm_nt_kernel<true, 2, false>),
+    GEMM_INSTANCE(256, 0, 128, 128, false, "gemm_conv_f32", gemm_nt_kernel<true, 2, true>),
+};
+static_assert(sizeof(kGemm) / sizeof(kGemm[0]) == CONV_F32 + 1, "kGemm and its index enum must agree");
 
-// What dvd_gemm_nt launches for a descriptor: the kernel and the template arguments of its instance.  gemm_select is the ONE
-// place of the selection rules: dvd_gemm_nt launches what it returns, dvd_gemm_kernel_name names it.
+// What bends the selection rules in the lab build (its DVD_GEMM_* switches, read in gemm_lab.inc).  The defaults are the product's
+// behaviour, and the product passes nothing else.
+struct GemmKnobs {
+  bool scalar_epilogue = false, v1 = false, twopass = false;
+  bool no_t384 = false;      // DVD_GEMM_NO_T384, or DVD_GEMM_DEBUG
+  int debug = 0;             // GemmArgs::debug
+  bool ring128 = true;
+  int ring256 = 1;           // 0: off; 2: also below RING256_MIN_TILES (tests, A/B runs)
+  int t384_dbg = 0;          // the <DBG, , , X16> of the gemm_nt_t384_kernel instances
+  bool t384_x16 = T384_X16 != 0;
+};
+
+// What dvd_gemm_nt launches for a descriptor: the instance and the GemmArgs fields that depend on the choice.  gemm_select is the
+// ONE place of the selection rules: dvd_gemm_nt launches what it returns, dvd_gemm_kernel_name names it.
 struct GemmChoice {
-  GemmKernel kernel = GemmKernel::plain;
-  int vec_epilogue = 0;    // GemmArgs::vec_epilogue
-  int variant = 0;         // split128: <B_lo>; big: <variant>; f32_narrow: <variant>; plain: <F32, PD = variant>
-  int dbg = 0, fl = 0;     // t384 <DBG, FL, FULL, X16>
-  bool full = false, x16 = false;
-  int debug = 0;           // GemmArgs::debug (lab: DVD_GEMM_DEBUG)
+  const GemmKernel* k = nullptr;
+  int vec_epilogue = 0, debug = 0, stagger = 0, walk = 0;
 };
 }  // namespace
 
-// Validation and kernel choice: host-only (no device call), a function of the descriptor alone in the product build (the lab
-// build also reads its A/B switches).  Returns DVD_E_ARG, with the reason in dvd_last_error, for a descriptor it refuses.
-static int gemm_select(const dvd_gemm_desc* d, GemmChoice& c) {
+// Validation and kernel choice: host-only (no device call), a function of the descriptor alone in the product build, whose
+// knobs are the defaults (the lab build fills them from its A/B switches).  Returns DVD_E_ARG, with the reason in
+// dvd_last_error, for a descriptor it refuses.
+static inline int gemm_select(const dvd_gemm_desc* d, const GemmKnobs& kn, GemmChoice& c) {
   DVD_REQUIRE(d && d->A && d->B && (d->C32 || d->C16), "gemm: null pointer");
   DVD_REQUIRE(d->dtype == 0 || d->dtype == 1, "gemm: dtype must be 0 (f16) or 1 (f32)");
   const int bk = d->dtype == 1 ? 16 : 64, esz = d->dtype == 1 ? 4 : 2;
@@ -2149,20 +2168,10 @@ static int gemm_select(const dvd_gemm_desc* d, GemmChoice& c) {
                   (d->dtype == 0 && ((uintptr_t)d->B_lo % 16) == 0 && ((uintptr_t)d->A_lo % 16) == 0),
               "gemm: split operands need dtype f16, 16-byte aligned");
   c = GemmChoice();
-
-  // The product library has no switches: the kernel is a function of the descriptor alone.  The lab build
-  // (-DDVD_LAB, benchmarks/lab/libdvd_hip_lab.so) keeps the A/B switches of the experiments that were measured.
-#ifdef DVD_LAB
-  { const char* dbg = getenv("DVD_GEMM_DEBUG"); c.debug = dbg ? atoi(dbg) : 0; }
-  const bool lab_scalar_epi = getenv("DVD_GEMM_SCALAR_EPILOGUE"), lab_v1 = getenv("DVD_GEMM_V1"),
-             lab_twopass = getenv("DVD_GEMM_TWOPASS"), lab_spread = getenv("DVD_GEMM_SPREAD"),
-             lab_no_t384 = getenv("DVD_GEMM_NO_T384") || c.debug;
-#else
-  constexpr bool lab_scalar_epi = false, lab_v1 = false, lab_twopass = false, lab_no_t384 = false;
-#endif
+  c.debug = kn.debug;
   {
     auto al = [](const void* q, size_t a) { return ((uintptr_t)q % a) == 0; };
-    bool ok = d->N % 8 == 0 && !lab_scalar_epi;
+    bool ok = d->N % 8 == 0 && !kn.scalar_epilogue;
     if (d->C32) ok = ok && d->ldc % 4 == 0 && d->strideC32 % 4 == 0 && al(d->C32, 16);
     if (d->C16) ok = ok && d->ldc16 % 8 == 0 && d->strideC16 % 8 == 0 && al(d->C16, 16);
     if (d->bias && !d->bias_row) ok = ok && al(d->bias, 16) && d->strideBias % 4 == 0;
@@ -2186,145 +2195,115 @@ static int gemm_select(const dvd_gemm_desc* d, GemmChoice& c) {
   // document still gets the same bits alone (small_tiles 1) and in a large batch (tests/test_gpu_gemm.py) - everything else
   // stays on the 128x128 kernel.
   const bool small = d->small_tiles == 1, small_many = d->small_tiles == 2;
-  const bool big = d->dtype == 0 && d->N % 256 == 0 && !lab_v1 && !small;
+  const bool big = d->dtype == 0 && d->N % 256 == 0 && !kn.v1 && !small;
   if (d->dtype == 0 && d->N % 128 == 0 && d->N % 256 != 0 && !d->A_lo && (!d->B_lo || d->lo_scale == 1.f) &&
-      d->K % 32 == 0 && !lab_twopass && !lab_v1 && !small && !small_many) {
+      d->K % 32 == 0 && !kn.twopass && !kn.v1 && !small && !small_many) {
     // 256 x 128 tiles for the DiT block's 384-wide GEMMs: (hi, lo) in one pass, or ONE (dithered) weight tensor
-    c.kernel = GemmKernel::split128;
-    c.variant = d->B_lo ? 1 : 0;
+    c.k = &kGemm[SPLIT128 + (d->B_lo ? 1 : 0)];
     return DVD_OK;
   }
-  if (big && d->B_lo && !d->A_lo && d->lo_scale == 1.f && d->K % 32 == 0 && !lab_twopass && !small_many) {
-    c.kernel = GemmKernel::split256;
+  if (big && d->B_lo && !d->A_lo && d->lo_scale == 1.f && d->K % 32 == 0 && !kn.twopass && !small_many) {
+    c.k = &kGemm[SPLIT256];
     return DVD_OK;
   }
-#ifdef DVD_LAB
-  if (big && !d->B_lo && !d->A_lo && d->K % 32 == 0 && getenv("DVD_GEMM_RING")) {
-    // lab: the split kernel's 3-stage skewed pipeline on one weight tensor, for A/B runs against gemm_nt_big_kernel
-    c.kernel = GemmKernel::lab_ring;
-    return DVD_OK;
-  }
-  if (big && !d->B_lo && !d->A_lo && c.vec_epilogue && !d->pos && !d->gate && getenv("DVD_GEMM_M16")) {
-    // lab: the 16x16x32-MFMA variant of the 256 x 256 kernel (measured 1-7 % slower, see gemm_nt_big16_kernel)
-    c.kernel = GemmKernel::lab_big16;
-    return DVD_OK;
-  }
-  if (big && !d->B_lo && !d->A_lo && d->K % 32 == 0 && c.vec_epilogue && !d->pos && !d->gate && !(d->bias && d->bias_row) &&
-      getenv("DVD_GEMM_BIG2")) {
-    c.kernel = GemmKernel::lab_big2;
-    return DVD_OK;
-  }
-#endif
   if (big && !d->B_lo && !d->A_lo && !small_many && c.vec_epilogue && !d->pos && !d->gate && !(d->bias && d->bias_row) &&
-      !(d->res && d->act == 1) && d->K % 128 == 0 && d->K >= 256 && !lab_no_t384) {
+      !(d->res && d->act == 1) && d->K % 128 == 0 && d->K >= 256 && !kn.no_t384) {
     // 384 x 256 tiles, 4-slot half-slab ring, generated K loop.  Since round 6 (16x16x32 MFMAs) its bits differ from
     // gemm_nt_big_kernel's: a descriptor that loses vec_epilogue (an unaligned C / residual pointer or leading dimension)
     // falls through to a kernel with DIFFERENT bits - the engine's workspace layout keeps its call sites aligned
     // (tests/test_gemm_dispatch.py).
-    c.kernel = GemmKernel::t384;
     // the epilogue flavour is a function of the descriptor (never of the data): see gemm_nt_t384_kernel
-    c.fl = (d->C16 && !d->C32 && !d->res) ? 0 : (d->C32 && !d->C16 && d->act != 1) ? (d->res ? 2 : 1) : (d->res ? 4 : 3);
-    c.full = d->M % 384 == 0;
-#ifdef DVD_LAB
-    int tdbg = 0;
-    if (const char* e = getenv("DVD_GEMM_T384_DBG")) tdbg = atoi(e);
-    c.x16 = getenv("DVD_GEMM_T384_M32") ? false : (getenv("DVD_GEMM_T384_X16") ? true : (T384_X16 != 0));
-    c.dbg = c.x16 ? (tdbg == 5 ? 5 : 0) : (tdbg >= 1 && tdbg <= 6 ? tdbg : 0);
-#else
-    c.x16 = T384_X16 != 0;
-#endif
+    const int fl = (d->C16 && !d->C32 && !d->res) ? 0 : (d->C32 && !d->C16 && d->act != 1) ? (d->res ? 2 : 1) : (d->res ? 4 : 3);
+    c.k = gemm_t384_instance(kn.t384_dbg, fl, d->M % 384 == 0, kn.t384_x16);
+    c.stagger = T384_STAGGER;
+    c.walk = T384_WALK;
     return DVD_OK;
   }
   if (big) {
-    c.kernel = GemmKernel::big;
-#ifdef DVD_LAB
-    const int dv = c.debug;
-    c.variant = (dv == 1 || dv == 2 || dv == 3 || dv == 5 || dv == 6 || dv == 7) ? dv : lab_spread ? 4 : 0;
-#endif
+    c.k = &kGemm[BIG];
     return DVD_OK;
   }
   if (d->dtype == 1 && d->N <= 64 && d->C32 && !d->C16 && !d->pos && !d->gate && !d->res && !d->bias_row &&
       (d->act == 0 || d->act == 2) && !d->A_lo && !d->B_lo) {
-    c.kernel = GemmKernel::f32_narrow;
-    c.variant = d->N <= 32 ? 1 : 2;
+    c.k = &kGemm[F32_NARROW + (d->N <= 32 ? 0 : 1)];
     return DVD_OK;
   }
   {
     // f16 problems with few 128 x 128 tiles: the LDS-DMA ring kernel (same bits; see gemm_nt_ring128_kernel)
     const long ntm = cdiv(d->M, 128), ntn = cdiv(d->N, 128);
     auto al16 = [](const void* q) { return ((uintptr_t)q % 16) == 0; };
-    bool ring = d->dtype != 1 && d->K % 64 == 0 && d->K >= 128 && d->lda % 8 == 0 && d->ldb % 8 == 0 && d->strideA % 8 == 0 &&
-                d->strideB % 8 == 0 && al16(d->A) && al16(d->B) && al16(d->A_lo) && al16(d->B_lo) &&
-                ntm * ntn <= RING128_MAX_TILES && (long)d->M * d->lda < (1l << 30) && (long)d->N * d->ldb < (1l << 30);
-#ifdef DVD_LAB
-    if (const char* e = getenv("DVD_GEMM_RING128")) ring = ring && atoi(e) != 0;
-#endif
+    const bool ring = d->dtype != 1 && d->K % 64 == 0 && d->K >= 128 && d->lda % 8 == 0 && d->ldb % 8 == 0 && d->strideA % 8 == 0 &&
+                      d->strideB % 8 == 0 && al16(d->A) && al16(d->B) && al16(d->A_lo) && al16(d->B_lo) &&
+                      ntm * ntn <= RING128_MAX_TILES && (long)d->M * d->lda < (1l << 30) && (long)d->N * d->ldb < (1l << 30) &&
+                      kn.ring128;
     bool ring256 = d->dtype != 1 && d->N % 256 == 0 && d->K % 32 == 0 && d->K >= 128 && d->lda % 8 == 0 && d->ldb % 8 == 0 &&
                    d->strideA % 8 == 0 && d->strideB % 8 == 0 && al16(d->A) && al16(d->B) && al16(d->A_lo) && al16(d->B_lo) &&
                    ntm * (d->N / 256) <= RING256_MAX_TILES && ntm * (d->N / 256) >= RING256_MIN_TILES &&
                    (long)d->M * d->lda < (1l << 30) &&
-                   (long)d->N * d->ldb < (1l << 30);
-#ifdef DVD_LAB
-    if (const char* e = getenv("DVD_GEMM_RING256")) {       // 0: off; 2: also below RING256_MIN_TILES (tests, A/B runs)
-      if (atoi(e) == 0) ring256 = false;
-      if (atoi(e) == 2) ring256 = d->dtype != 1 && d->N % 256 == 0 && d->K >= 128 && d->lda % 8 == 0 && d->ldb % 8 == 0 && d->strideA % 8 == 0 &&
-                                  d->strideB % 8 == 0 && al16(d->A) && al16(d->B) && al16(d->A_lo) && al16(d->B_lo) &&
-                                  ntm * (d->N / 256) <= RING256_MAX_TILES;
+                   (long)d->N * d->ldb < (1l << 30) && kn.ring256 != 0;
+    if (kn.ring256 == 2)
+      ring256 = d->dtype != 1 && d->N % 256 == 0 && d->K >= 128 && d->lda % 8 == 0 && d->ldb % 8 == 0 && d->strideA % 8 == 0 &&
+                d->strideB % 8 == 0 && al16(d->A) && al16(d->B) && al16(d->A_lo) && al16(d->B_lo) &&
+                ntm * (d->N / 256) <= RING256_MAX_TILES;
+    if (ring256 || ring) {
+      c.k = &kGemm[ring256 ? RING256 : RING128];
+      return DVD_OK;
     }
-#endif
-    if (ring256) { c.kernel = GemmKernel::ring256; return DVD_OK; }
-    if (ring) { c.kernel = GemmKernel::ring128; return DVD_OK; }
   }
-#ifdef DVD_LAB
-  if (const char* e = getenv("DVD_GEMM_W8"); e && atoi(e) != 0 && d->dtype != 1) {   // lab: two waves per SIMD on each tile
-    c.kernel = GemmKernel::lab_w8;
-    return DVD_OK;
-  }
-  if (getenv("DVD_GEMM_PD4")) {       // lab: register prefetch four tiles deep (measured: no gain, see gemm_nt_kernel)
-    c.kernel = GemmKernel::plain;
-    c.variant = 4;
-    return DVD_OK;
-  }
-#endif
-  c.kernel = GemmKernel::plain;
-  c.variant = 2;
+  c.k = &kGemm[PLAIN + (d->dtype == 1 ? 1 : 0)];
   return DVD_OK;
 }
+
+// The product library has no switches: the kernel is a function of the descriptor alone.  The lab build (-DDVD_LAB,
+// benchmarks/lab/libdvd_hip_lab.so) keeps the A/B switches of the experiments that were measured: its gemm_choose reads them,
+// runs gemm_select under them and then puts its own instances (kGemmLab) in; its gemm_tweak applies the argument and grid switches.
+#ifdef DVD_LAB
+#include "../../benchmarks/lab/csrc/gemm_lab.inc"
+#else
+static int gemm_choose(const dvd_gemm_desc* d, GemmChoice& c) { return gemm_select(d, GemmKnobs(), c); }
+static void gemm_tweak(const GemmChoice&, GemmArgs&, int&) {}
+#endif
 
 // The demangled (rocprofv3) name of the instance dvd_gemm_nt launches for *d, "" for a descriptor it refuses.
 extern "C" const char* dvd_gemm_kernel_name(const dvd_gemm_desc* d) {
   GemmChoice c;
-  if (gemm_select(d, c) != DVD_OK) return "";
-  static thread_local char name[64];
-  const char* tf[2] = {"false", "true"};
-  switch (c.kernel) {
-    case GemmKernel::split128: snprintf(name, sizeof(name), "gemm_nt_split128_kernel<%s>", tf[c.variant]); break;
-    case GemmKernel::split256: return "gemm_nt_split_kernel<true>";
-    case GemmKernel::t384:
-      snprintf(name, sizeof(name), "gemm_nt_t384_kernel<%d, %d, %s, %s>", c.dbg, c.fl, tf[c.full], tf[c.x16]);
-      break;
-    case GemmKernel::big: snprintf(name, sizeof(name), "gemm_nt_big_kernel<%d>", c.variant); break;
-    case GemmKernel::f32_narrow: snprintf(name, sizeof(name), "gemm_f32_narrow_kernel<%d>", c.variant); break;
-    case GemmKernel::ring256: return "gemm_nt_ring256_kernel";
-    case GemmKernel::ring128: return "gemm_nt_ring128_kernel";
-    case GemmKernel::plain:
-      snprintf(name, sizeof(name), "gemm_nt_kernel<%s, %d, false>", tf[d->dtype == 1], c.variant);
-      break;
+  return gemm_choose(d, c) == DVD_OK ? c.k->name : "";
+}
+
+static void allow_lds(const GemmKernel* k, int n) {
+  for (int i = 0; i < n; ++i)
+    if (k[i].lds) (void)hipFuncSetAttribute((const void*)k[i].fn, hipFuncAttributeMaxDynamicSharedMemorySize, k[i].lds);
+}
+
+// THE launch of the family: p.M / p.N tiled as the instance says, at most max_wg workgroups where it is persistent.
+static int gemm_launch(const GemmKernel& k, GemmArgs& p, int batch, int max_wg, void* stream) {
+  if (k.lds) {
+    // hipFuncSetAttribute is per DEVICE: on a device's first launch every instance gets its dynamic LDS allowed (one bit per
+    // device, lock-free: the call is idempotent, so two threads racing here both make it and both are right)
+    static DeviceOnce once;
+    if (const auto bit = DeviceOnce::current_bit(); once.need(bit)) {
+      allow_lds(kGemm, CONV_F32 + 1);
+      const GemmKernel* t384;
+      const int n = gemm_t384_instances(&t384);
+      allow_lds(t384, n);
 #ifdef DVD_LAB
-    case GemmKernel::lab_ring: return "gemm_nt_split_kernel<false>";
-    case GemmKernel::lab_big16: return "gemm_nt_big16_kernel";
-    case GemmKernel::lab_big2: return "gemm_nt_big2_kernel";
-    case GemmKernel::lab_w8: return "gemm_nt_w8_kernel";
+      allow_lds(kGemmLab, sizeof(kGemmLab) / sizeof(kGemmLab[0]));
 #endif
-    default: return "";
+      once.done(bit);
+    }
   }
-  return name;
+  p.ntm = cdiv(p.M, k.tile_m);
+  p.ntn = cdiv(p.N, k.tile_n);
+  int nwg = p.ntm * p.ntn;
+  if (k.persistent && nwg > max_wg) nwg = max_wg;
+  k.fn<<<dim3(nwg, batch), k.threads, k.lds, (hipStream_t)stream>>>(p);
+  return check_launch(k.what);
 }
 
 extern "C" int dvd_gemm_nt(const dvd_gemm_desc* d, void* stream) {
   GemmChoice c;
-  if (const int rc = gemm_select(d, c); rc != DVD_OK) return rc;
-  GemmArgs p;
+  if (const int rc = gemm_choose(d, c); rc != DVD_OK) return rc;
+  GemmArgs p{};
   p.Blo = d->B_lo; p.Alo = d->A_lo; p.lo_scale = d->lo_scale;
   p.A = d->A; p.B = d->B; p.C32 = d->C32; p.C16 = (_Float16*)d->C16;
   p.bias = d->bias; p.res = d->res; p.gate = d->gate; p.pos = d->pos;
@@ -2335,188 +2314,10 @@ extern "C" int dvd_gemm_nt(const dvd_gemm_desc* d, void* stream) {
   p.ldgate = d->ldgate; p.ldpos = d->ldpos;
   p.gate_rows = d->gate_rows; p.pos_rows = d->pos_rows;
   p.act = d->act; p.bias_row = d->bias_row;
-  p.cv_b = nullptr; p.cv_ca = p.cv_cb = p.cv_h = p.cv_w = p.cv_ks = p.cv_dil = 0;
-  p.vec_epilogue = c.vec_epilogue;
-  p.debug = c.debug;
-#ifdef DVD_LAB
-  { const char* sg = getenv("DVD_GEMM_STAGGER"); p.stagger = sg ? atoi(sg) : 0; }   // measured: no effect
-  p.stamps = g_gemm_stamps;
-  p.walk = 0;
-  const bool lab_nonpersistent = getenv("DVD_GEMM_NONPERSISTENT");
-#else
-  p.stagger = 0; p.stamps = nullptr; p.walk = 0;
-  constexpr bool lab_nonpersistent = false;
-#endif
-  const hipStream_t st = (hipStream_t)stream;
-  switch (c.kernel) {
-    case GemmKernel::split128: {
-      p.ntm = cdiv(d->M, 256); p.ntn = d->N / 128;
-      constexpr int LDS = 8 * 16384;                    // 3 stages x 32 KiB, rounded up to the epilogue's 8 x 16 KiB
-      static DeviceOnce once_s1;
-      if (const auto bit = DeviceOnce::current_bit(); once_s1.need(bit)) {
-        (void)hipFuncSetAttribute((const void*)gemm_nt_split128_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-        (void)hipFuncSetAttribute((const void*)gemm_nt_split128_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-        once_s1.done(bit);
-      }
-      int nblk = p.ntm * p.ntn;
-      if (nblk > 256) nblk = 256;
-      if (c.variant) gemm_nt_split128_kernel<true><<<dim3(nblk, d->batch), 512, LDS, st>>>(p);
-      else gemm_nt_split128_kernel<false><<<dim3(nblk, d->batch), 512, LDS, st>>>(p);
-      return check_launch("gemm_nt(128-wide)");
-    }
-    case GemmKernel::split256: {
-      p.ntm = cdiv(d->M, 256); p.ntn = d->N / 256;
-      constexpr int LDS = 3 * 3 * 256 * 64;
-      static DeviceOnce once_s;
-      if (const auto bit = DeviceOnce::current_bit(); once_s.need(bit)) {
-        (void)hipFuncSetAttribute((const void*)gemm_nt_split_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-        once_s.done(bit);
-      }
-      int nblk = p.ntm * p.ntn;
-      if (nblk > 256) nblk = 256;
-      gemm_nt_split_kernel<true><<<dim3(nblk, d->batch), 512, LDS, st>>>(p);
-      return check_launch("gemm_nt(split)");
-    }
-#ifdef DVD_LAB
-    case GemmKernel::lab_ring: {
-      p.ntm = cdiv(d->M, 256); p.ntn = d->N / 256;
-      constexpr int LDS = 3 * 3 * 256 * 64;
-      static DeviceOnce once_r;
-      if (const auto bit = DeviceOnce::current_bit(); once_r.need(bit)) {
-        (void)hipFuncSetAttribute((const void*)gemm_nt_split_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-        once_r.done(bit);
-      }
-      int nblk = p.ntm * p.ntn;
-      if (nblk > 256) nblk = 256;
-      gemm_nt_split_kernel<false><<<dim3(nblk, d->batch), 512, LDS, st>>>(p);
-      return check_launch("gemm_nt(ring, lab)");
-    }
-    case GemmKernel::lab_big16: {
-      p.ntm = cdiv(d->M, 256); p.ntn = d->N / 256;
-      constexpr int LDS = 2 * 2 * 256 * 128;
-      static DeviceOnce once16;
-      if (const auto bit = DeviceOnce::current_bit(); once16.need(bit)) {
-        (void)hipFuncSetAttribute((const void*)gemm_nt_big16_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-        once16.done(bit);
-      }
-      int nblk = p.ntm * p.ntn;
-      if (nblk > 256) nblk = 256;
-      gemm_nt_big16_kernel<<<dim3(nblk, d->batch), 512, LDS, st>>>(p);
-      return check_launch("gemm_nt(big16)");
-    }
-    case GemmKernel::lab_big2: {
-      p.ntm = cdiv(d->M, 256); p.ntn = d->N / 256;
-      constexpr int LDS = big2::NBUF * big2::HALF;
-      static DeviceOnce once2;
-      if (const auto bit = DeviceOnce::current_bit(); once2.need(bit)) {
-        (void)hipFuncSetAttribute((const void*)gemm_nt_big2_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-        once2.done(bit);
-      }
-      int nblk = p.ntm * p.ntn;
-      if (nblk > 256) nblk = 256;
-      gemm_nt_big2_kernel<<<dim3(nblk, d->batch), 256, LDS, st>>>(p);
-      return check_launch("gemm_nt(big2)");
-    }
-#endif
-    case GemmKernel::t384: {
-      p.ntm = cdiv(d->M, 384); p.ntn = d->N / 256;
-      p.stagger = T384_STAGGER;
-      p.walk = T384_WALK;
-#ifdef DVD_LAB
-      if (const char* e = getenv("DVD_GEMM_T384_STAGGER")) p.stagger = atoi(e);
-      if (getenv("DVD_GEMM_T384_PRIO")) p.debug |= 0x100;
-      if (const char* e = getenv("DVD_GEMM_T384_WALK")) p.walk = atoi(e);
-      if (getenv("DVD_GEMM_T384_NT")) p.debug |= 0x200;
-      if (getenv("DVD_GEMM_T384_RES_PHASED")) p.debug |= 0x400;
-      if (getenv("DVD_GEMM_T384_NOSTORE")) p.debug |= 0x800;
-#endif
-      return launch_gemm_t384(p, d->batch, c.dbg, c.fl, c.full, c.x16, stream);
-    }
-    case GemmKernel::big: {
-      p.ntm = cdiv(d->M, 256); p.ntn = d->N / 256;
-      constexpr int LDS = 2 * 2 * 256 * 128;
-      static DeviceOnce once;
-      if (const auto bit = DeviceOnce::current_bit(); once.need(bit)) {
-        (void)hipFuncSetAttribute((const void*)gemm_nt_big_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-#ifdef DVD_LAB
-        (void)hipFuncSetAttribute((const void*)gemm_nt_big_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-        (void)hipFuncSetAttribute((const void*)gemm_nt_big_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-        (void)hipFuncSetAttribute((const void*)gemm_nt_big_kernel<3>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-        (void)hipFuncSetAttribute((const void*)gemm_nt_big_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-        (void)hipFuncSetAttribute((const void*)gemm_nt_big_kernel<5>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-        (void)hipFuncSetAttribute((const void*)gemm_nt_big_kernel<6>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-        (void)hipFuncSetAttribute((const void*)gemm_nt_big_kernel<7>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-#endif
-        once.done(bit);
-      }
-      int nblk = p.ntm * p.ntn;
-      if (nblk > 256 && !lab_nonpersistent) nblk = 256;
-      dim3 gridb(nblk, d->batch);
-#ifdef DVD_LAB
-      if (c.variant == 1) gemm_nt_big_kernel<1><<<gridb, 512, LDS, st>>>(p);
-      else if (c.variant == 2) gemm_nt_big_kernel<2><<<gridb, 512, LDS, st>>>(p);
-      else if (c.variant == 3) gemm_nt_big_kernel<3><<<gridb, 512, LDS, st>>>(p);
-      else if (c.variant == 5) gemm_nt_big_kernel<5><<<gridb, 512, LDS, st>>>(p);
-      else if (c.variant == 6) gemm_nt_big_kernel<6><<<gridb, 512, LDS, st>>>(p);
-      else if (c.variant == 7) gemm_nt_big_kernel<7><<<gridb, 512, LDS, st>>>(p);
-      else if (c.variant == 4) gemm_nt_big_kernel<4><<<gridb, 512, LDS, st>>>(p);
-      else
-#endif
-      gemm_nt_big_kernel<0><<<gridb, 512, LDS, st>>>(p);
-      return check_launch("gemm_nt(big)");
-    }
-    case GemmKernel::f32_narrow: {
-      const dim3 grd(cdiv(d->M, 128), d->batch);
-      if (c.variant == 1) gemm_f32_narrow_kernel<1><<<grd, 256, 0, st>>>(p);
-      else gemm_f32_narrow_kernel<2><<<grd, 256, 0, st>>>(p);
-      return check_launch("gemm_nt(f32 narrow)");
-    }
-    default: break;
-  }
-  // the 128 x 128-tile family
-  p.ntm = cdiv(d->M, 128); p.ntn = cdiv(d->N, 128);
-  dim3 grid(p.ntm * p.ntn, d->batch);
-  switch (c.kernel) {
-    case GemmKernel::ring256: {
-      constexpr int LDS = 6 * (128 + 256) * 64;
-      static DeviceOnce once_r256;
-      if (const auto bit = DeviceOnce::current_bit(); once_r256.need(bit)) {
-        (void)hipFuncSetAttribute((const void*)gemm_nt_ring256_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-        once_r256.done(bit);
-      }
-      p.ntn = d->N / 256;
-      gemm_nt_ring256_kernel<<<dim3(p.ntm * p.ntn, d->batch), 512, LDS, st>>>(p);
-      return check_launch("gemm_nt(ring256)");
-    }
-    case GemmKernel::ring128: {
-      constexpr int LDS = 5 * 2 * 128 * 128;
-      static DeviceOnce once_r128;
-      if (const auto bit = DeviceOnce::current_bit(); once_r128.need(bit)) {
-        (void)hipFuncSetAttribute((const void*)gemm_nt_ring128_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-        once_r128.done(bit);
-      }
-      gemm_nt_ring128_kernel<<<grid, 256, LDS, st>>>(p);
-      return check_launch("gemm_nt(ring128)");
-    }
-#ifdef DVD_LAB
-    case GemmKernel::lab_w8:
-      gemm_nt_w8_kernel<<<grid, 512, 0, st>>>(p);
-      return check_launch("gemm_nt(w8, lab)");
-    case GemmKernel::plain:
-      if (c.variant == 4) {
-        if (d->dtype == 1) gemm_nt_kernel<true, 4><<<grid, 256, 0, st>>>(p);
-        else gemm_nt_kernel<false, 4><<<grid, 256, 0, st>>>(p);
-        return check_launch("gemm_nt(pd4, lab)");
-      }
-      break;
-#endif
-    default: break;
-  }
-  if (d->dtype == 1)
-    gemm_nt_kernel<true, 2><<<grid, 256, 0, st>>>(p);
-  else
-    gemm_nt_kernel<false, 2><<<grid, 256, 0, st>>>(p);
-  return check_launch("gemm_nt");
+  p.vec_epilogue = c.vec_epilogue; p.debug = c.debug; p.stagger = c.stagger; p.walk = c.walk;
+  int max_wg = 256;
+  gemm_tweak(c, p, max_wg);
+  return gemm_launch(*c.k, p, d->batch, max_wg, stream);
 }
 
 int dvd::launch_gemm_conv_f32(const float* a, int ca, const float* b, int cb, int h, int w, int ks, int dil, long rows,
@@ -2528,13 +2329,10 @@ int dvd::launch_gemm_conv_f32(const float* a, int ca, const float* b, int cb, in
               "gemm_conv_f32: bad map (%d x %d, %ld rows)", h, w, rows);
   DVD_REQUIRE(((uintptr_t)a % 16) == 0 && ((uintptr_t)b % 16) == 0 && ((uintptr_t)wgt % 16) == 0,
               "gemm_conv_f32: operands must be 16-byte aligned");
-  GemmArgs p;
-  memset(&p, 0, sizeof(p));
+  GemmArgs p{};
   p.A = a; p.cv_b = b; p.cv_ca = ca; p.cv_cb = cb; p.cv_h = h; p.cv_w = w; p.cv_ks = ks; p.cv_dil = dil;
   p.B = wgt; p.ldb = kp; p.C32 = out; p.ldc = cout; p.bias = bias; p.act = act; p.lo_scale = 1.f;
   p.M = (int)rows; p.N = cout; p.K = kp;
   p.vec_epilogue = (cout % 8 == 0 && ((uintptr_t)out % 16) == 0 && ((uintptr_t)bias % 16) == 0) ? 1 : 0;
-  p.ntm = cdiv(p.M, 128); p.ntn = cdiv(p.N, 128);
-  gemm_nt_kernel<true, 2, true><<<dim3(p.ntm * p.ntn, 1), 256, 0, (hipStream_t)stream>>>(p);
-  return check_launch("gemm_conv_f32");
+  return gemm_launch(kGemm[CONV_F32], p, 1, 256, stream);
 }

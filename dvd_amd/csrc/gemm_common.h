@@ -114,8 +114,23 @@ __device__ __forceinline__ float gelu_tanh(float x) {
   return x < -10.5f ? -0.f : y;
 }
 
-// gemm_t384.hip: the 384 x 256 kernel, instance gemm_nt_t384_kernel<dbg, fl, full, x16> (lab builds: dbg selects a timing
-// ablation / the stamp build, x16 the K loop; the product build has dbg 0 and x16 = T384_X16)
-int launch_gemm_t384(const GemmArgs& p, int batch, int dbg, int fl, bool full, bool x16, void* stream);
+// One instance of the GEMM family: what dvd_gemm_kernel_name reports and everything dvd_gemm_nt's one launch needs.
+struct GemmKernel {
+  const char* name;        // as rocprofv3 prints it
+  void (*fn)(GemmArgs);
+  int threads, lds;        // workgroup size, dynamic LDS bytes
+  int tile_m, tile_n;      // ntm = cdiv(M, tile_m), ntn = cdiv(N, tile_n)
+  bool persistent;         // min(ntm * ntn, 256) workgroups walk the tiles; otherwise one workgroup per tile
+  const char* what;        // check_launch label
+};
+// name and entry point from the same tokens: the two cannot drift
+#define GEMM_INSTANCE(threads, lds, tile_m, tile_n, persistent, what, ...) \
+  {#__VA_ARGS__, __VA_ARGS__, threads, lds, tile_m, tile_n, persistent, what}
+
+// gemm_t384.hip (the template can only be instantiated there) hands its instances to gemm.hip's launch: instance
+// gemm_nt_t384_kernel<dbg, fl, full, x16> - the product has dbg 0 and x16 = T384_X16 only; the lab build also dbg = a timing
+// ablation / the stamp build and the other K loop - or nullptr; gemm_t384_instances: all of them (the per-device LDS set-up)
+const GemmKernel* gemm_t384_instance(int dbg, int fl, bool full, bool x16);
+int gemm_t384_instances(const GemmKernel** first);
 
 }  // namespace dvd

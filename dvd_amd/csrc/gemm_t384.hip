@@ -716,66 +716,58 @@ __global__ void __launch_bounds__(512, 2) gemm_nt_t384_kernel(GemmArgs p) {
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
-template <int DBG, bool X16>
-static void launch_fl(const GemmArgs& p, int fl, bool full, dim3 grid, hipStream_t st) {
-#define T384_GO(FL_, FULL_) gemm_nt_t384_kernel<DBG, FL_, FULL_, X16><<<grid, 512, t384::LDS_BYTES, st>>>(p)
-  if (full) {
-    switch (fl) { case 0: T384_GO(0, true); break; case 1: T384_GO(1, true); break; case 2: T384_GO(2, true); break;
-                  case 3: T384_GO(3, true); break; default: T384_GO(4, true); }
-  } else {
-    switch (fl) { case 0: T384_GO(0, false); break; case 1: T384_GO(1, false); break; case 2: T384_GO(2, false); break;
-                  case 3: T384_GO(3, false); break; default: T384_GO(4, false); }
+// The instances by (DBG, X16) family: entry points [FL][FULL].  The name of an instance is formatted from the very values that
+// index its entry point (t384_table, below).
+namespace {
+struct T384Family {
+  int dbg;
+  bool x16;
+  void (*fn[5][2])(GemmArgs);
+};
+#define T384_FL(DBG, FL, X16) {gemm_nt_t384_kernel<DBG, FL, false, (X16)>, gemm_nt_t384_kernel<DBG, FL, true, (X16)>}
+#define T384_FAMILY(DBG, X16) \
+  {DBG, (X16), {T384_FL(DBG, 0, X16), T384_FL(DBG, 1, X16), T384_FL(DBG, 2, X16), T384_FL(DBG, 3, X16), T384_FL(DBG, 4, X16)}}
+// T384_X16 (gemm_common.h): the product's K loop.  The lab build carries both loops, the timing ablations of the old one
+// (6: the 16x16x32 PRICING ablation, garbage math) and the stamp build of each.
+const T384Family kFamilies[] = {
+    T384_FAMILY(0, T384_X16 != 0),
+#ifdef DVD_LAB
+    T384_FAMILY(0, T384_X16 == 0), T384_FAMILY(5, true),  T384_FAMILY(1, false), T384_FAMILY(2, false),
+    T384_FAMILY(3, false),         T384_FAMILY(4, false), T384_FAMILY(5, false), T384_FAMILY(6, false),
+#endif
+};
+#undef T384_FAMILY
+#undef T384_FL
+constexpr int NFAM = sizeof(kFamilies) / sizeof(kFamilies[0]);
+
+struct T384Table {
+  GemmKernel k[NFAM][5][2];
+  char name[NFAM][5][2][48];
+  T384Table() {
+    for (int f = 0; f < NFAM; ++f)
+      for (int fl = 0; fl < 5; ++fl)
+        for (int full = 0; full < 2; ++full) {
+          snprintf(name[f][fl][full], sizeof(name[f][fl][full]), "gemm_nt_t384_kernel<%d, %d, %s, %s>", kFamilies[f].dbg, fl,
+                   full ? "true" : "false", kFamilies[f].x16 ? "true" : "false");
+          k[f][fl][full] = {name[f][fl][full], kFamilies[f].fn[fl][full], 512, t384::LDS_BYTES, 384, 256, true, "gemm_nt(t384)"};
+        }
   }
-#undef T384_GO
+};
+const T384Table& t384_table() {
+  static const T384Table t;
+  return t;
 }
-template <int DBG, bool X16>
-static void allow_lds() {
-#define T384_AL(FL_, FULL_) (void)hipFuncSetAttribute((const void*)gemm_nt_t384_kernel<DBG, FL_, FULL_, X16>, hipFuncAttributeMaxDynamicSharedMemorySize, t384::LDS_BYTES)
-  T384_AL(0, true); T384_AL(1, true); T384_AL(2, true); T384_AL(3, true); T384_AL(4, true);
-  T384_AL(0, false); T384_AL(1, false); T384_AL(2, false); T384_AL(3, false); T384_AL(4, false);
-#undef T384_AL
+}  // namespace
+
+const GemmKernel* gemm_t384_instance(int dbg, int fl, bool full, bool x16) {
+  for (int f = 0; f < NFAM; ++f)
+    if (kFamilies[f].dbg == dbg && kFamilies[f].x16 == x16) return &t384_table().k[f][fl][full];
+  return nullptr;
 }
 
-// T384_X16 (gemm_common.h): the product's K loop.  The lab build carries both loops and the timing ablations of the old one.
-int launch_gemm_t384(const GemmArgs& p, int batch, int dbg, int fl, bool full, bool x16, void* stream) {
-  static DeviceOnce once_t;
-  if (const auto bit = DeviceOnce::current_bit(); once_t.need(bit)) {
-    allow_lds<0, T384_X16 != 0>();
-#ifdef DVD_LAB
-    allow_lds<0, T384_X16 == 0>();
-    allow_lds<1, false>(); allow_lds<2, false>(); allow_lds<3, false>(); allow_lds<4, false>(); allow_lds<5, false>(); allow_lds<6, false>();
-    allow_lds<5, true>();
-#endif
-    once_t.done(bit);
-  }
-  int nblk = p.ntm * p.ntn;
-  if (nblk > 256) nblk = 256;
-#ifdef DVD_LAB
-  if (const char* e = getenv("DVD_GEMM_T384_NBLK")) nblk = atoi(e) < nblk ? atoi(e) : nblk;   // lab: fewer persistent workgroups
-#endif
-  const dim3 grid(nblk, batch);
-  hipStream_t st = (hipStream_t)stream;
-  // (dbg, fl, full, x16): the instance gemm_select (gemm.hip) chose
-#ifdef DVD_LAB
-  if (x16) {
-    if (dbg == 5) launch_fl<5, true>(p, fl, full, grid, st);
-    else launch_fl<0, true>(p, fl, full, grid, st);
-    return check_launch("gemm_nt(t384 x16)");
-  }
-  switch (dbg) {
-    case 1: launch_fl<1, false>(p, fl, full, grid, st); break;
-    case 2: launch_fl<2, false>(p, fl, full, grid, st); break;
-    case 3: launch_fl<3, false>(p, fl, full, grid, st); break;
-    case 4: launch_fl<4, false>(p, fl, full, grid, st); break;
-    case 5: launch_fl<5, false>(p, fl, full, grid, st); break;
-    case 6: launch_fl<6, false>(p, fl, full, grid, st); break;      // round 6: the 16x16x32 PRICING ablation (garbage math)
-    default: launch_fl<0, false>(p, fl, full, grid, st);
-  }
-#else
-  (void)dbg; (void)x16;
-  launch_fl<0, T384_X16 != 0>(p, fl, full, grid, st);
-#endif
-  return check_launch("gemm_nt(t384)");
+int gemm_t384_instances(const GemmKernel** first) {
+  *first = &t384_table().k[0][0][0];
+  return NFAM * 5 * 2;
 }
 
 }  // namespace dvd

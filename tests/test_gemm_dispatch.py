@@ -181,6 +181,91 @@ def test_unaligned_output_leaves_t384_so_the_engine_requires_alignment():
         lib.raw().dvd_engine_destroy(h)
 
 
+# ---- the lab build's DVD_GEMM_* switches: each still chooses what it chose before the instance table ----
+# tests/golden/gemm_lab_names.json is the recording: lab_names() below, run in record mode (`python tests/test_gemm_dispatch.py
+# --record LIB`) on the lab library of the commit before the instance table.
+LAB_RECORDING = os.path.join(ROOT, "tests", "golden", "gemm_lab_names.json")
+RINGS_OFF = {"RING128": "0", "RING256": "0"}
+LAB_SWITCHES = [{}, {"V1": "1"}, {"TWOPASS": "1"}, {"SCALAR_EPILOGUE": "1"}, {"SPREAD": "1"}, {"NO_T384": "1"},
+                {"NO_T384": "1", "SPREAD": "1"}, {"DEBUG": "1"}, {"DEBUG": "3"}, {"DEBUG": "7"}, {"RING": "1"}, {"M16": "1"},
+                {"BIG2": "1"}, {"RING128": "0"}, {"RING256": "0"}, {"RING256": "2"}, {"W8": "1", **RINGS_OFF},
+                {"PD4": "1", **RINGS_OFF}, {"T384_M32": "1"}, {"T384_X16": "1"}, {"T384_DBG": "5"},
+                *({"T384_M32": "1", "T384_DBG": str(n)} for n in range(1, 7))]
+CODE = "0123456789abcdefghijklmnopqrstuvwxyzABCDEFGHIJKLMNOPQRSTUVWXYZ"     # one character per distinct name
+
+
+def switch_id(switches):
+    return "+".join(f"{k}={v}" for k, v in switches.items()) or "none"
+
+
+def hand_made(dtype=0, N=256, **fields):
+    """A descriptor the engine never builds: 4096 x N x 256, f32 output, every pointer 256-byte aligned unless `fields` says so."""
+    d = lib.GemmDesc()
+    d.dtype, d.M, d.N, d.K, d.batch = dtype, 4096, N, 256, 1
+    d.A, d.B, d.C32, d.lda, d.ldb, d.ldc, d.lo_scale = 1 << 40, 1 << 41, 1 << 42, 256, 256, N, 1.0
+    for k, v in fields.items():
+        setattr(d, k, v)
+    return d
+
+
+def lab_descriptors():
+    """(label, descriptor): the engine's call sites at three grids, alone and in a large batch, then what the engine never reaches."""
+    for G in (16, 72, 288):
+        for s in (2, 32):
+            addr = fake_address({})
+            for i, c in enumerate(CS.calls(G, s, 1)):
+                yield f"G={G} s={s} #{i} {c.site}", CS.descriptor(c, addr)
+    lo = 1 << 43
+    yield "B_lo", hand_made(B_lo=lo)                                   # gemm_nt_split_kernel<true>
+    yield "B_lo, lo_scale 0.5", hand_made(B_lo=lo, lo_scale=0.5)
+    yield "A_lo", hand_made(A_lo=lo)
+    yield "N=384", hand_made(N=384)                                    # gemm_nt_split128_kernel<false>
+    for st in (1, 2):
+        yield f"small_tiles {st}", hand_made(small_tiles=st)
+        yield f"small_tiles {st}, B_lo", hand_made(small_tiles=st, B_lo=lo)
+    yield "C + 4 bytes", hand_made(C32=(1 << 42) + 4)
+    yield "N=100", hand_made(N=100)
+    yield "f32 N=32", hand_made(dtype=1, N=32)                         # gemm_f32_narrow_kernel<1>
+    yield "f32 N=64", hand_made(dtype=1, N=64)                         # gemm_f32_narrow_kernel<2>
+    yield "f32 N=128", hand_made(dtype=1, N=128)
+
+
+def lab_names():
+    return [(label, lib.gemm_kernel_name(d)) for label, d in lab_descriptors()]
+
+
+@pytest.mark.parametrize("switches", LAB_SWITCHES, ids=switch_id)
+def test_lab_switches_choose_what_they_chose_before(lab, monkeypatch, switches):
+    """For every descriptor, under every switch set, the lab library names the kernel that the recording holds."""
+    import json
+    for k in [k for k in os.environ if k.startswith("DVD_GEMM_")]:
+        monkeypatch.delenv(k)
+    for k, v in switches.items():
+        monkeypatch.setenv("DVD_GEMM_" + k, v)
+    rec = json.load(open(LAB_RECORDING))
+    want = [rec["names"][CODE.index(ch)] for ch in rec["cases"][switch_id(switches)]]
+    got = lab_names()
+    assert len(got) == len(want)
+    for (label, name), w in zip(got, want):
+        assert name == w, (switch_id(switches), label, name, w)
+
+
+def test_lab_recording_covers_every_instance():
+    """The recording is worth something: it reaches every product instance dvd_gemm_nt has, both t384 K loops with their
+    ablations, and every experiment kernel of the lab."""
+    import json
+    names = set(json.load(open(LAB_RECORDING))["names"])
+    assert "" not in names
+    for must in ("gemm_nt_split128_kernel<true>", "gemm_nt_split128_kernel<false>", "gemm_nt_split_kernel<true>", "gemm_nt_big_kernel<0>",
+                 "gemm_f32_narrow_kernel<1>", "gemm_f32_narrow_kernel<2>", "gemm_nt_ring256_kernel", "gemm_nt_ring128_kernel",
+                 "gemm_nt_kernel<false, 2, false>", "gemm_nt_kernel<true, 2, false>", "gemm_nt_split_kernel<false>",
+                 "gemm_nt_big16_kernel", "gemm_nt_big2_kernel", "gemm_nt_w8_kernel", "gemm_nt_kernel<false, 4, false>",
+                 "gemm_nt_kernel<true, 4, false>", "gemm_nt_big_kernel<1>", "gemm_nt_big_kernel<3>", "gemm_nt_big_kernel<4>",
+                 "gemm_nt_big_kernel<7>", "gemm_nt_t384_kernel<5, 0, true, true>", "gemm_nt_t384_kernel<0, 0, true, false>",
+                 *(f"gemm_nt_t384_kernel<{n}, 0, true, false>" for n in range(1, 7))):
+        assert must in names, must
+
+
 def test_kernel_name_refuses_what_dispatch_refuses():
     d = lib.GemmDesc()
     assert lib.gemm_kernel_name(d) == ""                          # null pointers
@@ -189,3 +274,26 @@ def test_kernel_name_refuses_what_dispatch_refuses():
     assert lib.gemm_kernel_name(d) == ""
     d.K = 128
     assert lib.gemm_kernel_name(d) != ""
+
+
+if __name__ == "__main__":       # record mode: python tests/test_gemm_dispatch.py --record path/to/libdvd_hip_lab.so
+    import json
+    import sys
+    assert len(sys.argv) == 3 and sys.argv[1] == "--record", "usage: test_gemm_dispatch.py --record LAB_LIBRARY"
+    lib.use_library(sys.argv[2])
+    names, cases = [], {}
+    for switches in LAB_SWITCHES:
+        for k in [k for k in os.environ if k.startswith("DVD_GEMM_")]:
+            del os.environ[k]
+        os.environ.update({"DVD_GEMM_" + k: v for k, v in switches.items()})
+        row = []
+        for _, name in lab_names():
+            if name not in names:
+                names.append(name)
+            row.append(CODE[names.index(name)])
+        cases[switch_id(switches)] = "".join(row)
+    header = ("dvd_gemm_kernel_name of the LAB library built from the commit before the GEMM instance table, per switch set "
+              "(DVD_GEMM_ + key) and descriptor of tests/test_gemm_dispatch.py::lab_descriptors, recorded by that file's record "
+              "mode; cases[switch set][i] is the position in CODE of descriptor i's name in `names`")
+    json.dump({"header": header, "names": names, "cases": cases}, open(LAB_RECORDING, "w"), indent=1)
+    print(len(cases), "switch sets x", len(row), "descriptors,", len(names), "distinct names")
