@@ -78,12 +78,42 @@ def decode_documents(batch, device, log=None, png=False):
             d["image_u8"], d["decode_route"] = ops.decode_image(d.pop("file_bytes"), device, log=log, png=png)
 
 
-def prepare_conditioning(batch, device, grid, prestage_models, use_init_flow=False, decode_png=False):
+def corruption_of(settings):
+    """(number, severity) of the run's corruption from `settings.corruption_number` and `settings.severity` (the launcher's
+    --corruption rounds), or None when nothing is corrupted: severity 0, whatever the number, or an absent attribute.  A bad
+    value is a ValueError that names the attribute; a kind without a kernel is ops.CorruptionUnsupported."""
+    severity = ops.corruption_severity(getattr(settings, "severity", 0), "settings.severity")
+    if severity == 0:
+        return None
+    number = ops.corruption_number(getattr(settings, "corruption_number", 0), "settings.corruption_number")
+    if not ops.corruption_supported(number):
+        raise ops.CorruptionUnsupported(number)
+    return number, severity
+
+
+def corrupt_documents(batch, device, kind, severity, seed):
+    """The corruption stage, between ingest and the pre-stage nets: every document's 512 x 512 network input
+    y512 = k / 255 is replaced by the corrupted bytes k' / 255, in one launch for the batch, keyed per document by
+    (seed, path).  `src_u8`, the photograph the page is unwarped from, stays clean.  A document that arrives with ready
+    conditioning tensors cannot be corrupted consistently (its nets saw the clean image): a ValueError that names it."""
+    for d in batch:
+        if "y512" not in d or any(k in d for k in ("mask_cat", "mask_y512", "line_msk")):
+            raise ValueError(f"{d.get('path')}: a document with ready conditioning tensors cannot be corrupted (its pre-stage "
+                             "nets ran on the clean image): give the image, or run with settings.severity = 0")
+    y = th.stack([_on_device(d["y512"], device).float() for d in batch]).contiguous()
+    keys = [ops.corruption_key(seed, d["path"]) for d in batch]
+    y = ops.rgb8_to_unit(ops.corrupt_rgb8(ops.unit_to_rgb8(y), kind, severity, keys))
+    for j, d in enumerate(batch):
+        d["y512"] = y[j]
+
+
+def prepare_conditioning(batch, device, grid, prestage_models, use_init_flow=False, decode_png=False, *, corrupt=None):
     """Documents given as decoded images: ingest (cv2.resize to 512^2, / 255; doc_benchmark.py:84-88) and the pre-stage
     nets (evaluation.py:162-216) fill in y512 / mask_cat / mask_y512 / line_msk / src_u8 as DEVICE tensors.  Documents
     that already carry their conditioning tensors (synthetic ones with env.use_prestage_nets=False, .npz files of
     env.conditioning_dir) pass through untouched and need no pre-stage nets.  use_init_flow: every document also gets
-    `init_flow` [2,G,G] from GeoTr (evaluation.py:172-178), in the same pre-stage pass when that runs."""
+    `init_flow` [2,G,G] from GeoTr (evaluation.py:172-178), in the same pre-stage pass when that runs.  corrupt: None, or
+    (kind, severity, seed): `corrupt_documents` runs between ingest and the nets."""
     from . import prestage
     decode_documents(batch, device, png=decode_png)
     need_ingest = [d for d in batch if "image_u8" in d and "y512" not in d]
@@ -96,7 +126,9 @@ def prepare_conditioning(batch, device, grid, prestage_models, use_init_flow=Fal
     else:                                                   # one image, or images of one size: per image, as before
         for d, img in zip(need_ingest, imgs):
             d["y512"], d["src_u8"] = ops.ingest_u8(img, swap_rb=False, out_size=512, want_rgb=True)
-    todo = [d for d in batch if any(k not in d for k in ("mask_cat", "mask_y512", "line_msk"))]
+    if corrupt is not None:
+        corrupt_documents(batch, device, *corrupt)
+    todo =[d for d in batch if any(k not in d for k in ("mask_cat", "mask_y512", "line_msk"))]
     if use_init_flow and (prestage_models is None or prestage_models[0] is None):
         raise RuntimeError("env.use_init_flow needs the GeoTr_Seg_Inf model (pretrained_dewarp_model)")
     if use_init_flow:
@@ -327,6 +359,11 @@ def run_evaluation_docunet(settings, logger, val_loader, diffusion, model, pretr
     touched and before anything is written.  The pre-stage models may all be None when every document carries ready
     conditioning tensors.  Returns [(path, uint8 [H,W,3] device tensor)] (the reference returns None)."""
     opts = RunOptions.from_env(settings.env)
+    corruption = corruption_of(settings)
+    stage = {}                                  # nothing corrupted: prepare_conditioning is called exactly as it always was
+    if corruption is not None:
+        logger.info(f"corruption {corruption[0]} ({ops.CORRUPTIONS[corruption[0]]}) severity {corruption[1]}")
+        stage["corrupt"] = (*corruption, getattr(settings, "seed", 0))
     device = next(model.parameters()).device
     nets = (pretrained_dewarp_model, pretrained_seg_model, pretrained_line_seg_model)
     prestage_models = None if all(m is None for m in nets) else nets
@@ -337,7 +374,7 @@ def run_evaluation_docunet(settings, logger, val_loader, diffusion, model, pretr
     for batch in batches_of(val_loader, opts.batch_docs):
         adopt_reference_items(batch, device)
         prepare_conditioning(batch, device, opts.grid_size, prestage_models, bool(settings.env.use_init_flow),
-                             decode_png=opts.png_decoder == "hip")
+                             decode_png=opts.png_decoder == "hip", **stage)
         t0 = time.time()
         flow = sample_batch(settings, logger, diffusion, model, batch, opts.grid_size, device)
         th.cuda.synchronize()

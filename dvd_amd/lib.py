@@ -134,7 +134,7 @@ NON_STATUS = {"dvd_last_error", "dvd_version", "dvd_engine_workspace_bytes", "dv
               "dvd_ingest_scratch_bytes", "dvd_ingest_ragged_scratch_bytes", "dvd_resize_gray_scratch_bytes",
               "dvd_msssim_workspace_bytes", "dvd_png_bound", "dvd_png_scratch_bytes", "dvd_png_scratch_bytes_huff", "dvd_jpeg_bound",
               "dvd_jpeg_scratch_bytes", "dvd_sflow_level_workspace_bytes", "dvd_sflow_workspace_bytes",
-              "dvd_adist_workspace_bytes"}
+              "dvd_adist_workspace_bytes", "dvd_corrupt_supported", "dvd_corrupt_table"}
 
 # name -> argtypes; kept in one table so tests can check every symbol of include/dvd_hip.h
 SIGNATURES = {
@@ -213,6 +213,11 @@ SIGNATURES = {
     "dvd_adist_workspace_bytes": [C.c_int, C.c_int, C.POINTER(SflowParams)],
     "dvd_adist": [c_void, c_void, C.c_int, C.c_int, C.c_int, C.POINTER(SflowParams), c_void, c_void, c_void, c_void, c_void, c_void,
                   c_void, c_void, c_void],
+    "dvd_corrupt_supported": [C.c_int],
+    "dvd_corrupt_table": [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint32), C.c_int],
+    "dvd_corrupt_rgb8": [c_void, c_void, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_void, c_void],
+    "dvd_unit_to_rgb8": [c_void, c_void, C.c_int, C.c_int, C.c_int, c_void],
+    "dvd_rgb8_to_unit": [c_void, c_void, C.c_int, C.c_int, C.c_int, c_void],
     "dvd_png_bound": [C.c_int, C.c_int],
     "dvd_png_scratch_bytes": [C.c_int, C.c_int],
     "dvd_png_encode_rgb8": [c_void, C.c_int, C.c_int, c_void, C.c_long, c_void, c_void, c_void],

@@ -1034,3 +1034,116 @@ def gt_metrics_u8(pred_hwc_u8: torch.Tensor, gt_hwc_u8: torch.Tensor, metrics, p
     elif "ld" in metrics:
         out["ld"] = float(local_distortion(y, x, **params)[0])
     return {m: out[m] for m in GT_METRIC_NAMES if m in out}
+
+
+# ---- common corruptions of the network input (dvd_amd/csrc/corrupt.hip; definition: DESIGN.md 4.10, tests/corrupt_model.py) -----
+CORRUPTIONS = ("gaussian_noise", "shot_noise", "impulse_noise", "defocus_blur", "glass_blur", "motion_blur", "zoom_blur", "snow",
+               "frost", "fog", "brightness", "contrast", "elastic_transform", "pixelate", "jpeg_compression", "speckle_noise",
+               "gaussian_blur", "spatter", "saturate")
+CORRUPT_JPEG = CORRUPTIONS.index("jpeg_compression")
+CORRUPT_JPEG_QUALITY = (25, 18, 15, 10, 7)
+CORRUPT_MIN_SIDE, CORRUPT_MAX_SIDE = 32, 16384
+
+
+class CorruptionUnsupported(ValueError):
+    """A corruption of the benchmark's list that has no device kernel here.  `kind` is its number, `name` its name."""
+
+    def __init__(self, kind):
+        self.kind, self.name = kind, CORRUPTIONS[kind]
+        super().__init__(f"corruption {kind} ({self.name}): no device kernel")
+
+
+def _is_int(v):
+    return isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
+
+
+def corruption_number(kind, name="corruption_number") -> int:
+    """The number 0..18 of a corruption given by number or by name, or ValueError naming `name`."""
+    if isinstance(kind, str):
+        if kind not in CORRUPTIONS:
+            raise ValueError(f"{name} must be one of {', '.join(CORRUPTIONS)}, got {kind!r}")
+        return CORRUPTIONS.index(kind)
+    if not _is_int(kind) or not 0 <= kind < len(CORRUPTIONS):
+        raise ValueError(f"{name} must be an integer 0..{len(CORRUPTIONS) - 1} or a corruption's name, got {kind!r}")
+    return int(kind)
+
+
+def corruption_severity(severity, name="severity") -> int:
+    """The severity 0..5 (0: nothing is corrupted), or ValueError naming `name`."""
+    if not _is_int(severity) or not 0 <= severity <= 5:
+        raise ValueError(f"{name} must be an integer 0..5, got {severity!r}")
+    return int(severity)
+
+
+def corruption_supported(kind) -> bool:
+    """Whether corrupt_rgb8 delivers the kind (number or name)."""
+    return lib.raw().dvd_corrupt_supported(corruption_number(kind, "kind")) != 0
+
+
+def corruption_key(seed, path):
+    """The 64-bit key of one document's corruption: (seed & 0xffffffff, crc32(path)).  It names the document, not its place in
+    a batch."""
+    import zlib
+    if not _is_int(seed):
+        raise ValueError(f"corruption_key: seed must be an integer, got {seed!r}")
+    return int(seed) & 0xffffffff, zlib.crc32(str(path).encode())
+
+
+def unit_to_rgb8(y_nchw: torch.Tensor) -> torch.Tensor:
+    """The network input y [B,3,h,w] f32 = k / 255 -> its bytes [B,h,w,3] uint8: clamp(rint(255 y), 0, 255)."""
+    if not torch.is_tensor(y_nchw) or y_nchw.dim() != 4 or y_nchw.shape[1] != 3:
+        raise ValueError(f"unit_to_rgb8: expected a [B,3,h,w] tensor, got {tuple(y_nchw.shape) if torch.is_tensor(y_nchw) else type(y_nchw)}")
+    _chk(y_nchw, torch.float32, "y")
+    n, _, h, w = (int(v) for v in y_nchw.shape)
+    out = torch.empty(n, h, w, 3, dtype=torch.uint8, device=y_nchw.device)
+    lib.call("dvd_unit_to_rgb8", ptr(y_nchw), ptr(out), n, h, w, stream_ptr())
+    return out
+
+
+def rgb8_to_unit(img_nhwc_u8: torch.Tensor) -> torch.Tensor:
+    """Bytes [B,h,w,3] uint8 -> y [B,3,h,w] f32 = k / 255, the correctly rounded division of ingest_u8."""
+    if not torch.is_tensor(img_nhwc_u8) or img_nhwc_u8.dim() != 4 or img_nhwc_u8.shape[3] != 3:
+        raise ValueError("rgb8_to_unit: expected a [B,h,w,3] tensor, got "
+                         f"{tuple(img_nhwc_u8.shape) if torch.is_tensor(img_nhwc_u8) else type(img_nhwc_u8)}")
+    _chk(img_nhwc_u8, torch.uint8, "img")
+    n, h, w, _ = (int(v) for v in img_nhwc_u8.shape)
+    out = torch.empty(n, 3, h, w, dtype=torch.float32, device=img_nhwc_u8.device)
+    lib.call("dvd_rgb8_to_unit", ptr(img_nhwc_u8), ptr(out), n, h, w, stream_ptr())
+    return out
+
+
+def corrupt_rgb8(img_u8: torch.Tensor, kind, severity, key) -> torch.Tensor:
+    """[h,w,3] or [B,h,w,3] uint8 on the device -> the corrupted image(s), a new tensor of the same shape.  kind: a number 0..18
+    or a name of CORRUPTIONS; severity 1..5; key: (k0, k1) of 32 bits each for one image, a sequence of B such pairs for a
+    batch (corruption_key).  The result is a function of (bytes, kind, severity, key) only: an image in a batch gives what it
+    gives alone.  One launch; jpeg_compression goes through jpeg_encode / jpeg_decode per image.  Every argument is checked
+    before anything is launched; a kind without a kernel raises CorruptionUnsupported."""
+    kind = corruption_number(kind, "corrupt_rgb8: kind")
+    if not _is_int(severity) or not 1 <= severity <= 5:
+        raise ValueError(f"corrupt_rgb8: severity must be an integer 1..5, got {severity!r}")
+    if not corruption_supported(kind):
+        raise CorruptionUnsupported(kind)
+    if not torch.is_tensor(img_u8) or img_u8.dim() not in (3, 4) or img_u8.shape[-1] != 3:
+        raise ValueError("corrupt_rgb8: expected a [h,w,3] or [B,h,w,3] tensor, got "
+                         f"{tuple(img_u8.shape) if torch.is_tensor(img_u8) else type(img_u8)}")
+    if img_u8.dtype != torch.uint8 or not img_u8.is_contiguous():
+        raise ValueError(f"corrupt_rgb8: expected contiguous uint8, got {img_u8.dtype} contiguous={img_u8.is_contiguous()}")
+    single = img_u8.dim() == 3
+    batch = img_u8[None] if single else img_u8
+    n, h, w = (int(v) for v in batch.shape[:3])
+    if not (CORRUPT_MIN_SIDE <= min(h, w) and max(h, w) <= CORRUPT_MAX_SIDE):
+        raise ValueError(f"corrupt_rgb8: image {h}x{w}: every side must be {CORRUPT_MIN_SIDE}..{CORRUPT_MAX_SIDE}")
+    if not 1 <= n <= 65535:
+        raise ValueError(f"corrupt_rgb8: a batch of {n} images (1..65535)")
+    keys = np.asarray([key] if single else key)
+    if keys.shape != (n, 2) or keys.dtype.kind not in "iu" or keys.min() < 0 or keys.max() > 0xffffffff:
+        raise ValueError(f"corrupt_rgb8: key must be {'a pair' if single else f'{n} pairs'} of integers below 2^32, got {key!r}")
+    _chk(img_u8, torch.uint8, "img")
+    if kind == CORRUPT_JPEG:
+        quality = CORRUPT_JPEG_QUALITY[severity - 1]
+        out = torch.stack([jpeg_decode(jpeg_encode(im, quality, "420")) for im in batch])
+    else:
+        out = torch.empty_like(batch)
+        keys_dev = torch.from_numpy(keys.astype(np.uint32).view(np.int32)).to(img_u8.device)
+        lib.call("dvd_corrupt_rgb8", ptr(batch), ptr(out), n, h, w, kind, int(severity), ptr(keys_dev), stream_ptr())
+    return out[0] if single else out

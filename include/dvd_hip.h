@@ -743,6 +743,35 @@ long dvd_adist_workspace_bytes(int h, int w, const dvd_sflow_params* params);
 int dvd_adist(const float* a, const float* b, int n, int h, int w, const dvd_sflow_params* params, void* workspace, double* ld,
               double* ad, int16_t* flow1, int64_t* sums, int32_t* coef, float* aligned, int16_t* flow2, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Common corruptions of the network input (run_sampling.py --corruption): the benchmark numbering of Hendrycks & Dietterich,
+ * 0 gaussian_noise .. 14 jpeg_compression, 15 speckle_noise .. 18 saturate, severities 1..5.  The definitions are this
+ * project's own, in integer arithmetic (tests/corrupt_model.py states every kind byte for byte); parity with
+ * the `imagecorruptions` package is UNPINNED.  A corrupted image is a function of (bytes, kind, severity, key) only.  No
+ * scratch memory, no atomics, no host read-back.
+ * ---------------------------------------------------------------------------------------- */
+#define DVD_E_CORRUPT_KIND (-47)     /* a kind outside 0..18, or one without a kernel (4, 7, 8, 9, 12, 17, 18; 14 = the JPEG codec) */
+#define DVD_E_CORRUPT_SEVERITY (-48) /* a severity outside 1..5 */
+#define DVD_E_CORRUPT_SIZE (-49)     /* a side outside 32..16384 */
+/* 1: dvd_corrupt_rgb8 has a kernel for the kind; 2: the kind is delivered by other entry points (14: dvd_jpeg_encode_rgb8 with
+ * 4:2:0 at quality 25 18 15 10 7, then dvd_jpeg_decode_rgb8); 0: refused, or no kind at all.  Host-only. */
+int dvd_corrupt_supported(int kind);
+/* The real-valued tables, built on the host in double and quantised once; host-only, `out` is HOST memory (null: only count).
+ * Kind 1: [256][c] thresholds floor(CDF_Poisson(x c / 255)(j) 2^32) saturated to 2^32 - 1, c = 60 25 12 5 3.  Kinds 3, 5, 16:
+ * [side][side] Q16 weights that sum to exactly 65536; `angle` (kind 5 only) in degrees, -45..45.  Returns the number of
+ * entries (cap below it with a non-null out is DVD_E_ARG) or a DVD_E_CORRUPT_* code. */
+int dvd_corrupt_table(int kind, int severity, int angle, uint32_t* out, int cap);
+/* in, out [n,h,w,3] u8 (out must not be in), keys [n,2] u32 on the device: image i is corrupted with the Philox4x32-10 key
+ * (keys[2i], keys[2i+1]).  n 1..65535, sides 32..16384.  One launch; the first call on a device that needs a table (kinds 1,
+ * 3, 5, 16) also copies the tables there and waits for that copy.  Every argument is checked before anything is launched. */
+int dvd_corrupt_rgb8(const uint8_t* in, uint8_t* out, int n, int h, int w, int kind, int severity, const uint32_t* keys,
+                     void* stream);
+/* The two ends of the stage in the document loop.  y [n,3,h,w] f32 in 0..1 (the network input: k / 255) -> bytes [n,h,w,3] =
+ * clamp(rint(255 y), 0, 255), ties to even, NaN -> 0; and bytes -> y = k / 255, the correctly rounded division of dvd_ingest_u8.
+ * 3 n h w below 2^31. */
+int dvd_unit_to_rgb8(const float* y_nchw, uint8_t* out_nhwc, int n, int h, int w, void* stream);
+int dvd_rgb8_to_unit(const uint8_t* in_nhwc, float* y_nchw, int n, int h, int w, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -3,7 +3,11 @@
 
     python run_sampling.py --train_module dvd --train_name val_TDiff --name <run>
 
-dispatches to train_settings/<module>/<name>.run(settings)."""
+dispatches to train_settings/<module>/<name>.run(settings).
+
+--corruption runs the reference's fifteen rounds (severity 5, corruption numbers 0..14 of the common-corruptions benchmark); here
+each round corrupts the network input on the device, writes under <name>/cNN_<kind>_s<severity> and the run
+ends with one table: kind -> mean of every metric of env.gt_dir.  --severity N and --corruption_number K choose one round."""
 import argparse
 import importlib
 import os
@@ -17,7 +21,36 @@ import torch
 import admin.settings as ws_settings
 
 
-def run_sampling(train_module, train_name, seed, name, cudnn_benchmark=True, corruption=False):
+def corruption_rounds(corruption=False, severity=None, corruption_number=None):
+    """[(severity, number)] of the rounds to run: the reference's fifteen under --corruption, one chosen round when --severity
+    or --corruption_number is given (5 and 0 where only the other one is), else the one clean round."""
+    if severity is None and corruption_number is None:
+        return [(5, c) for c in range(15)] if corruption else [(0, 0)]
+    return [(5 if severity is None else severity, 0 if corruption_number is None else corruption_number)]
+
+
+def round_name(name, severity, number):
+    """The run name of one corrupted round: its pictures and score files get a directory of their own."""
+    from dvd_amd import ops
+    return f"{name}/c{number:02d}_{ops.CORRUPTIONS[number]}_s{severity}"
+
+
+def write_corruption_table(path, rows, metrics):
+    """rows [(number, kind, severity, {metric: mean})] -> the table as text, printed and written to `path`."""
+    lines = ["no kind severity " + " ".join(metrics)]
+    for number, kind, severity, means in rows:
+        lines.append(f"{number} {kind} {severity} " + " ".join(f"{means[m]:.6f}" if m in means else "-" for m in metrics))
+    text = "\n".join(lines) + "\n"
+    print(text, end="")
+    os.makedirs(os.path.dirname(path), exist_ok=True)
+    with open(path, "w") as f:
+        f.write(text)
+    return text
+
+
+def run_sampling(train_module, train_name, seed, name, cudnn_benchmark=True, corruption=False, severity=None,
+                 corruption_number=None):
+    from dvd_amd import ops
     print(f"Sampling:  {train_module}  {train_name}\nDate: {date.today().strftime('%d/%m/%Y')}")
     settings = ws_settings.Settings()
     settings.module_name, settings.script_name = train_module, train_name
@@ -28,10 +61,30 @@ def run_sampling(train_module, train_name, seed, name, cudnn_benchmark=True, cor
     shutil.copyfile(settings.project_path + ".py", os.path.join(save_dir, settings.script_name + ".py"))
     module = importlib.import_module(f"train_settings.{train_module.replace('/', '.')}.{train_name.replace('/', '.')}")
     run = getattr(module, "run")
-    rounds = [(5, c) for c in range(15)] if corruption else [(0, 0)]
-    for severity, number in rounds:
-        settings.severity, settings.corruption_number = severity, number
+    rows = []
+    for sev, number in corruption_rounds(corruption, severity, corruption_number):
+        sev = ops.corruption_severity(sev, "--severity")
+        if sev == 0:                                          # the clean round, as ever
+            settings.severity, settings.corruption_number, settings.name = sev, number, name
+            run(settings)
+            continue
+        number = ops.corruption_number(number, "--corruption_number")
+        kind = ops.CORRUPTIONS[number]
+        if not ops.corruption_supported(number):
+            print(f"corruption {number} ({kind}): no device kernel, round skipped")
+            continue
+        settings.severity, settings.corruption_number, settings.name = sev, number, round_name(name, sev, number)
+        for metric in ops.GT_METRIC_NAMES:                    # a round's scores are its own
+            if hasattr(settings, metric):
+                delattr(settings, metric)
         run(settings)
+        means = {m: sum(v for _, v in getattr(settings, m)) / len(getattr(settings, m))
+                 for m in ops.GT_METRIC_NAMES if getattr(settings, m, None)}
+        rows.append((number, kind, sev, means))
+    settings.name = name
+    if rows:
+        metrics = [m for m in ops.GT_METRIC_NAMES if any(m in r[3] for r in rows)]
+        write_corruption_table(os.path.join("vis_hp", str(settings.env.eval_dataset_name), name, "corruption_table.txt"), rows, metrics)
 
 
 def main():
@@ -42,13 +95,15 @@ def main():
     p.add_argument("--seed", type=int, default=1992)
     p.add_argument("--name", type=str, default="Default")
     p.add_argument("--corruption", action="store_true")
+    p.add_argument("--severity", type=int, default=None, help="one chosen round: its severity 0..5 (5 if only --corruption_number is given)")
+    p.add_argument("--corruption_number", type=int, default=None, help="one chosen round: its corruption 0..18 (0 if only --severity is given)")
     a = p.parse_args()
     a.seed = torch.initial_seed() & (2 ** 32 - 1)      # as the reference: the CLI value is overwritten (:77-78)
     print(f"Seed is {a.seed}")
     random.seed(int(a.seed))
     np.random.seed(a.seed)
     run_sampling(a.train_module, a.train_name, seed=a.seed, name=a.name, cudnn_benchmark=a.cudnn_benchmark,
-                 corruption=a.corruption)
+                 corruption=a.corruption, severity=a.severity, corruption_number=a.corruption_number)
 
 
 if __name__ == "__main__":
