@@ -11,6 +11,7 @@
 #include "../../include/dvd_hip.h"
 
 #include "hd.h"
+#include "philox.h"
 
 namespace dvd {
 namespace cr {
@@ -82,25 +83,10 @@ inline Params params_for(int kind, int severity) {
   return p;
 }
 
-// ---- Philox4x32-10 (Salmon et al. 2011): counter (c0..c3), key (k0, k1) -> four 32-bit words ----------------------------
-// The counter of this project: c0 = the element's index in its image, c1 = the draw, c2 = the kind, c3 = 0 for an element's
+// ---- Philox4x32-10 (philox.h): counter (c0..c3), key (k0, k1) -> four 32-bit words ---------------------------------------
+// The counter of the corruptions: c0 = the element's index in its image, c1 = the draw, c2 = the kind, c3 = 0 for an element's
 // noise and 1 for a parameter of the whole image.
-DVD_HD void philox(uint32_t k0, uint32_t k1, uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t* out) {
-  for (int r = 0; r < 10; ++r) {
-    const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
-    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
-    c1 = (uint32_t)p1;
-    c3 = (uint32_t)p0;
-    c0 = n0;
-    c2 = n2;
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
-  out[0] = c0;
-  out[1] = c1;
-  out[2] = c2;
-  out[3] = c3;
-}
+using dvd::philox;
 
 DVD_HD int clamp255(int64_t v) { return v < 0 ? 0 : (v > 255 ? 255 : (int)v); }
 

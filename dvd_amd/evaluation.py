@@ -20,12 +20,13 @@ from .run_options import GT_METRICS, RunOptions, parse_gt_metrics  # noqa: F401 
 
 
 def run_sample_lr_dewarping(settings, logger, diffusion, model, radius, source, feature_size, raw_corr, init_flow, c20,
-                            source_64, pyramid, doc_mask, seg_map_all=None, textline_map=None, init_feat=None):
+                            source_64, pyramid, doc_mask, seg_map_all=None, textline_map=None, init_feat=None, *, noise_keys=None):
     """One batch of documents through the sampler, with the reference's positional signature (evaluation.py:80-138; call
     site :247-265): returns the clamped flow [B,2,G,G].  `radius`, `raw_corr`, `source_64` and `pyramid` are dead in the
     reference's body as well (the correlation code is commented out, the conv pyramid belongs to the denoiser); `c20` is
     the reference's `src_feat`, None on the live configuration (train_VGG=True, :219-221).  B = source.shape[0] documents
-    are sampled in one engine batch (the reference: B = 1)."""
+    are sampled in one engine batch (the reference: B = 1).  noise_keys (keyword only, an extension): one (k0, k1) pair per
+    document, handed to the loop in sampling_kwargs - the sampler's noise is then keyed per document."""
     kw = {"init_flow": init_flow, "src_feat": c20, "src_64": None, "y512": source, "tmode": settings.env.train_mode,
           "mask_cat": doc_mask, "init_feat": init_feat, "iter": settings.env.iter}
     if not settings.env.use_gt_mask:
@@ -38,9 +39,12 @@ def run_sample_lr_dewarping(settings, logger, diffusion, model, radius, source, 
     sampler = run_options.read(settings.env, "sampler")
     if sampler != "ddim":
         extra["sampler_kind"] = sampler                       # engine-side extension (BASELINE configs[3]: 'ddpm')
+    sampling_kwargs = {"src_img": source}
+    if noise_keys is not None:
+        sampling_kwargs["noise_keys"] = list(noise_keys)
     sample, _ = diffusion.ddim_sample_loop(
         model, (B, 2, feature_size, feature_size), noise=None, clip_denoised=settings.env.clip_denoised,
-        model_kwargs=kw, eta=0.0, progress=True, denoised_fn=None, sampling_kwargs={"src_img": source}, logger=logger,
+        model_kwargs=kw, eta=0.0, progress=True, denoised_fn=None, sampling_kwargs=sampling_kwargs, logger=logger,
         n_batch=settings.env.n_batch, time_variant=settings.env.time_variant, pyramid=pyramid, **extra)
     return th.clamp(sample, min=-1, max=1)
 
@@ -282,13 +286,47 @@ def adopt_reference_items(batch, device):
                 raise ValueError(f"{d['path']}: no 'source_image' and a non-integer 'source_image_ori' to make it from")
 
 
-def sample_batch(settings, logger, diffusion, model, batch, grid, device):
-    """The conditioned documents of one batch through `run_sample_lr_dewarping` (evaluation.py:247-265): the flow [B,2,G,G]."""
+def keyed_noise_of(settings):
+    """`settings.keyed_noise` (run_sampling.py --keyed_noise): absent means False; anything but a bool is a ValueError that names
+    the attribute."""
+    flag = getattr(settings, "keyed_noise", False)
+    if not isinstance(flag, (bool, np.bool_)):
+        raise ValueError(f"settings.keyed_noise must be True or False, got {flag!r}")
+    return bool(flag)
+
+
+def sample_batch(settings, logger, diffusion, model, batch, grid, device, *, keyed_noise=None):
+    """The conditioned documents of one batch through `run_sample_lr_dewarping` (evaluation.py:247-265): the flow [B,2,G,G].
+    keyed_noise (None: settings.keyed_noise): the sampler's noise is keyed per document by (settings.seed, path), the
+    corruption stage's key; False calls the sampler exactly as ever."""
     nb = len(batch)
     src, msk, seg, line = (_stack(batch, k, device) for k in ("y512", "mask_cat", "mask_y512", "line_msk"))
     init_flow = _stack(batch, "init_flow", device) if settings.env.use_init_flow else th.zeros(nb, 2, grid, grid, device=device)  # :176-181
+    extra = {}
+    if keyed_noise_of(settings) if keyed_noise is None else keyed_noise:
+        extra["noise_keys"] = [ops.corruption_key(getattr(settings, "seed", 0), d["path"]) for d in batch]
     return run_sample_lr_dewarping(settings, logger, diffusion, model, 4, src, grid, None, init_flow, None, None, None, msk,
-                                   seg, line, th.zeros(nb, 256, grid, grid, device=device))
+                                   seg, line, th.zeros(nb, 256, grid, grid, device=device), **extra)
+
+
+def score_map_deviation(settings, logger, batch, flow, clean):
+    """settings.keyed_noise, after a batch is sampled.  A document that has a reference map in
+    `settings.map_ref` is scored against it: ops.map_deviation, one log line, an entry of `settings.map_dev`.  A document
+    without one leaves its map there when the round is clean, and gets one log line and no score when it is corrupted."""
+    have = [j for j, d in enumerate(batch) if d["path"] in settings.map_ref]
+    if have:
+        ref = th.stack([settings.map_ref[batch[j]["path"]] for j in have]).to(flow.device).contiguous()
+        got = (flow if len(have) == len(batch) else flow[have]).float().contiguous()
+        for j, value in zip(have, ops.map_deviation(ref, got)):
+            logger.info(f"{batch[j]['path']} map_dev {value:.6f}")
+            settings.map_dev.append((batch[j]["path"], value))
+    for j, d in enumerate(batch):
+        if j in have:
+            continue
+        if clean:
+            settings.map_ref[d["path"]] = flow[j].cpu()
+        else:
+            logger.info(f"{d['path']} map_dev skipped: no clean round has left a reference map")
 
 
 def unwarp_tail(batch, flow, mode, device):
@@ -350,16 +388,32 @@ def summarize(settings, logger, opts, times, results):
             logger.info(f"mean {name}: no document of {len(results)} has a ground truth in {opts.gt_dir}")
 
 
+def summarize_map_deviation(settings, logger, documents):
+    """The end of a scored round under settings.keyed_noise: map_dev.txt beside the round's other score files, and the mean."""
+    scores = settings.map_dev
+    with open(f"vis_hp/{settings.env.eval_dataset_name}/{settings.name}/map_dev.txt", "w") as f:
+        for path, value in scores:
+            f.write(f"{path} {value:.6f}\n")
+    if scores:
+        mean = sum(v for _, v in scores) / len(scores)
+        logger.info(f"mean map_dev {mean:.6f} over {len(scores)} of {documents} documents")
+    else:
+        logger.info(f"mean map_dev: no document of {documents} has a reference map from a clean round")
+
+
 def run_evaluation_docunet(settings, logger, val_loader, diffusion, model, pretrained_dewarp_model,
                            pretrained_line_seg_model=None, pretrained_seg_model=None):
     """Document loop with the reference's positional signature (evaluation.py:142-327; call site val_TDiff.py:103-104).
     `val_loader` yields the reference's dicts or this package's documents (`documents_of`); env.batch_docs of them go through
     each pass (the reference: 1): adopt, ingest + pre-stage nets (:162-216), the sampler (:247-265), the unwarp tail, then the
     picture and the scores.  The engine-side switches (dvd_amd/run_options.py) are read and checked once, before the loader is
-    touched and before anything is written.  The pre-stage models may all be None when every document carries ready
+    touched and before anything is written; so are settings.severity / corruption_number and settings.keyed_noise
+    (4.11: the sampler's noise keyed per document, reference maps kept and later rounds scored with map_dev).  The pre-stage models
+    may all be None when every document carries ready
     conditioning tensors.  Returns [(path, uint8 [H,W,3] device tensor)] (the reference returns None)."""
     opts = RunOptions.from_env(settings.env)
     corruption = corruption_of(settings)
+    keyed = {"keyed_noise": True} if keyed_noise_of(settings) else {}    # absent or False: sample_batch is called as it always was
     stage = {}                                  # nothing corrupted: prepare_conditioning is called exactly as it always was
     if corruption is not None:
         logger.info(f"corruption {corruption[0]} ({ops.CORRUPTIONS[corruption[0]]}) severity {corruption[1]}")
@@ -370,16 +424,24 @@ def run_evaluation_docunet(settings, logger, val_loader, diffusion, model, pretr
     os.makedirs(f"vis_hp/{settings.env.eval_dataset_name}/{settings.name}", exist_ok=True)
     for name in opts.gt_metrics if opts.gt_dir else ():
         setattr(settings, name, [])
+    if keyed:
+        settings.map_dev = []                   # a round's scores are its own; the reference maps outlive the round
+        if not isinstance(getattr(settings, "map_ref", None), dict):
+            settings.map_ref = {}
     times, results = [], []
     for batch in batches_of(val_loader, opts.batch_docs):
         adopt_reference_items(batch, device)
         prepare_conditioning(batch, device, opts.grid_size, prestage_models, bool(settings.env.use_init_flow),
                              decode_png=opts.png_decoder == "hip", **stage)
         t0 = time.time()
-        flow = sample_batch(settings, logger, diffusion, model, batch, opts.grid_size, device)
+        flow = sample_batch(settings, logger, diffusion, model, batch, opts.grid_size, device, **keyed)
         th.cuda.synchronize()
         times.append((time.time() - t0) / len(batch))
+        if keyed:
+            score_map_deviation(settings, logger, batch, flow, clean=corruption is None)
         outs = unwarp_tail(batch, flow, opts.unwarp_mode, device)
         emit(settings, logger, batch, outs, results, opts, device)
     summarize(settings, logger, opts, times, results)
+    if keyed and (corruption is not None or settings.map_dev):
+        summarize_map_deviation(settings, logger, len(results))
     return results

@@ -105,25 +105,38 @@ class GaussianDiffusion:
         (one document per call); B > 1 samples B documents x n_batch hypotheses in one engine batch
         (model_kwargs tensors then carry B rows).  Returns (sample [B,2,G,G], final dict).
         clip_denoised / denoised_fn are process_xstart (:380-385) at every step: see sampler.sample.
-        model_kwargs['iter'] other than True is the loop's second branch (:579-594): no feedback of the prediction."""
+        model_kwargs['iter'] other than True is the loop's second branch (:579-594): no feedback of the prediction.
+        sampling_kwargs['noise_keys'] (an extension; the reference reads nothing of sampling_kwargs): B pairs (k0, k1), one per
+        document (ops.corruption_key).  All noise then comes from ops.randn_keyed - x_T is slot 0 unless `noise` is given, the
+        noise of step index i slot 1 + i - and nothing is drawn from torch's generator: a document's noise no longer depends on
+        the batch, on the order of the documents or on what was sampled before it."""
         if not time_variant:
             raise NotImplementedError("time_variant=False is a different network (three streams, d = 1152): only "
                                       "time_variant=True is mirrored")
         iterate = bool(model_kwargs.get("iter", True) == True)  # noqa: E712  (the reference's `iter_flag != True`, :579)
         B, C, G, G2 = shape
         assert C == 2 and G == G2
+        keys = (sampling_kwargs or {}).get("noise_keys")
+        if keys is not None:
+            keys = ops.noise_keys(keys, B, "sampling_kwargs['noise_keys']")      # refused before the engine is touched
         dev = device or next(model.parameters()).device
         eng = model.engine(G, B, n_batch)
         kw = model_kwargs
         eng.prepare(*[kw[k].to(dev, th.float32).contiguous() for k in ("y512", "mask_cat", "mask_y512", "line_msk")])
+        if keys is not None:
+            keys = ops.noise_keys_tensor(keys, dev)
         if noise is not None:
             x_T = noise.to(dev, th.float32).contiguous()
             assert tuple(x_T.shape) == (B * n_batch, 2, G, G)
+        elif keys is not None:
+            x_T = ops.randn_keyed(keys, n_batch, G, 0)
         else:
             _ = th.randn(*shape, device=dev)                     # the reference draws and discards this (:562)
             x_T = th.randn((B * n_batch, 2, G, G), device=dev)    # (:569)
         noise_fn = None
-        if sampler_kind == "ddpm" or eta != 0.0:
+        if (sampler_kind == "ddpm" or eta != 0.0) and keys is not None:
+            noise_fn = lambda i: ops.randn_keyed(keys, n_batch, G, 1 + i)      # noqa: E731
+        elif sampler_kind == "ddpm" or eta != 0.0:
             noise_fn = lambda i: th.randn((B * n_batch, 2, G, G), device=dev)  # noqa: E731
         sample = sampler.sample(eng, self.tables, x_T, sampler=sampler_kind, eta=eta, noise_fn=noise_fn,
                                 clip_denoised=bool(clip_denoised), denoised_fn=denoised_fn, iterate=iterate,

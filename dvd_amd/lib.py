@@ -134,7 +134,7 @@ NON_STATUS = {"dvd_last_error", "dvd_version", "dvd_engine_workspace_bytes", "dv
               "dvd_ingest_scratch_bytes", "dvd_ingest_ragged_scratch_bytes", "dvd_resize_gray_scratch_bytes",
               "dvd_msssim_workspace_bytes", "dvd_png_bound", "dvd_png_scratch_bytes", "dvd_png_scratch_bytes_huff", "dvd_jpeg_bound",
               "dvd_jpeg_scratch_bytes", "dvd_sflow_level_workspace_bytes", "dvd_sflow_workspace_bytes",
-              "dvd_adist_workspace_bytes", "dvd_corrupt_supported", "dvd_corrupt_table"}
+              "dvd_adist_workspace_bytes", "dvd_corrupt_supported", "dvd_corrupt_table", "dvd_map_deviation_workspace_bytes"}
 
 # name -> argtypes; kept in one table so tests can check every symbol of include/dvd_hip.h
 SIGNATURES = {
@@ -218,6 +218,9 @@ SIGNATURES = {
     "dvd_corrupt_rgb8": [c_void, c_void, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_void, c_void],
     "dvd_unit_to_rgb8": [c_void, c_void, C.c_int, C.c_int, C.c_int, c_void],
     "dvd_rgb8_to_unit": [c_void, c_void, C.c_int, C.c_int, C.c_int, c_void],
+    "dvd_randn_keyed": [c_void, C.c_int, C.c_int, C.c_int, C.c_uint32, c_void, c_void],
+    "dvd_map_deviation_workspace_bytes": [C.c_int, C.c_int],
+    "dvd_map_deviation": [c_void, c_void, C.c_int, C.c_int, c_void, c_void, c_void],
     "dvd_png_bound": [C.c_int, C.c_int],
     "dvd_png_scratch_bytes": [C.c_int, C.c_int],
     "dvd_png_encode_rgb8": [c_void, C.c_int, C.c_int, c_void, C.c_long, c_void, c_void, c_void],
@@ -252,7 +255,7 @@ SIGNATURES = {
 RESTYPES = {"dvd_gemm_kernel_name": C.c_char_p, "dvd_ingest_ragged_scratch_bytes": C.c_long,
             "dvd_resize_gray_scratch_bytes": C.c_long, "dvd_msssim_workspace_bytes": C.c_long,
             "dvd_sflow_level_workspace_bytes": C.c_long, "dvd_sflow_workspace_bytes": C.c_long,
-            "dvd_adist_workspace_bytes": C.c_long,
+            "dvd_adist_workspace_bytes": C.c_long, "dvd_map_deviation_workspace_bytes": C.c_long,
             "dvd_png_bound": C.c_long, "dvd_png_scratch_bytes": C.c_long, "dvd_png_scratch_bytes_huff": C.c_long,
             "dvd_jpeg_bound": C.c_long, "dvd_jpeg_scratch_bytes": C.c_long}
 

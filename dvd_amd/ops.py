@@ -1147,3 +1147,93 @@ def corrupt_rgb8(img_u8: torch.Tensor, kind, severity, key) -> torch.Tensor:
         keys_dev = torch.from_numpy(keys.astype(np.uint32).view(np.int32)).to(img_u8.device)
         lib.call("dvd_corrupt_rgb8", ptr(batch), ptr(out), n, h, w, kind, int(severity), ptr(keys_dev), stream_ptr())
     return out[0] if single else out
+
+
+# ---- keyed sampler noise and the map deviation (dvd_amd/csrc/noise.hip; definition: DESIGN.md 4.11, tests/noise_model.py) --------
+NOISE_MIN_GRID, NOISE_MAX_GRID = 2, 8192
+MAP_DEV_PX = 0.987 * 511          # pixels of the 512 x 512 network input per unit of flow
+
+
+def noise_keys(keys, docs=None, name="noise_keys"):
+    """A sequence of (k0, k1) pairs of 32-bit integers (corruption_key) as an int64 array [docs, 2], or ValueError naming
+    `name`: not a sequence of pairs, a value outside 0 .. 2^32 - 1, or - where `docs` is given - another length."""
+    try:
+        arr = np.asarray(list(keys))
+    except (TypeError, ValueError):                # no sequence, or pairs of different lengths
+        arr = np.asarray(None)
+    if arr.ndim == 1 and arr.size == 0:            # no document
+        arr = np.zeros((0, 2), np.int64)
+    if arr.ndim != 2 or arr.shape[1] != 2 or arr.dtype.kind not in "iu" or (arr.size and (arr.min() < 0 or arr.max() > 0xffffffff)):
+        raise ValueError(f"{name} must be a sequence of (k0, k1) pairs of integers below 2^32, got {keys!r}")
+    if docs is not None and arr.shape[0] != docs:
+        raise ValueError(f"{name} must hold one (k0, k1) pair per document: {docs}, got {arr.shape[0]}")
+    return arr.astype(np.int64)
+
+
+def noise_keys_tensor(keys, device, docs=None, name="noise_keys") -> torch.Tensor:
+    """The keys on the device as randn_keyed takes them ([docs, 2] int32 holding the 32-bit patterns): one small copy, so a
+    sampling loop uploads its keys once."""
+    arr = noise_keys(keys, docs, name)
+    return torch.from_numpy(arr.astype(np.uint32).view(np.int32)).to(device)
+
+
+def randn_keyed(keys, n_hyp: int, g: int, slot: int, device=None, out: torch.Tensor = None) -> torch.Tensor:
+    """Standard normals [docs*n_hyp, 2, g, g] f32 keyed per document: sample doc * n_hyp + h is a function of (keys[doc], h, slot,
+    element) only - not of the batch, of the order of the documents or of torch's generator.  keys: a sequence of (k0, k1) pairs
+    (corruption_key), or what noise_keys_tensor made of one.  slot 0 is x_T, slot 1 + i the noise of step index i.  out: a
+    contiguous f32 device tensor of that shape, filled in place and returned.  One launch."""
+    if not _is_int(n_hyp) or not 0 <= n_hyp <= 65535:
+        raise ValueError(f"randn_keyed: n_hyp must be an integer 0..65535, got {n_hyp!r}")
+    if not _is_int(g) or not NOISE_MIN_GRID <= g <= NOISE_MAX_GRID:
+        raise ValueError(f"randn_keyed: g must be an integer {NOISE_MIN_GRID}..{NOISE_MAX_GRID}, got {g!r}")
+    if not _is_int(slot) or not 0 <= slot <= 0xffffffff:
+        raise ValueError(f"randn_keyed: slot must be an integer 0..2^32-1, got {slot!r}")
+    if torch.is_tensor(keys):
+        if keys.dim() != 2 or keys.shape[1] != 2 or keys.dtype != torch.int32 or not keys.is_contiguous():
+            raise ValueError(f"randn_keyed: a key tensor must be contiguous [docs, 2] int32 (noise_keys_tensor), got {tuple(keys.shape)} {keys.dtype}")
+        keys_dev = keys
+        device = keys.device if device is None else torch.device(device)
+    else:
+        arr = noise_keys(keys, name="randn_keyed: keys")
+        device = torch.device("cuda" if device is None else device)
+        keys_dev = torch.from_numpy(arr.astype(np.uint32).view(np.int32)).to(device)
+    docs = int(keys_dev.shape[0])
+    if docs > 65535 or docs * int(n_hyp) * ((2 * g * g + 3) // 4) > 1 << 38:
+        raise ValueError(f"randn_keyed: {docs} documents x {n_hyp} hypotheses at g = {g} (65535 documents and 2^38 quads at most)")
+    shape = (docs * int(n_hyp), 2, int(g), int(g))
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=device)
+    elif not torch.is_tensor(out) or tuple(out.shape) != shape:
+        raise ValueError(f"randn_keyed: out must be a tensor of shape {shape}, got {tuple(out.shape) if torch.is_tensor(out) else type(out)}")
+    if out.numel() == 0:
+        return out
+    _chk(keys_dev, torch.int32, "keys")
+    _chk(out, torch.float32, "out")
+    if out.device != keys_dev.device:
+        raise ValueError(f"randn_keyed: out is on {out.device}, the keys on {keys_dev.device}")
+    lib.call("dvd_randn_keyed", ptr(keys_dev), docs, int(n_hyp), int(g), int(slot), ptr(out), stream_ptr())
+    return out
+
+
+def map_deviation(a: torch.Tensor, b: torch.Tensor) -> list:
+    """Two stacks of maps [docs,2,g,g] f32 on the device -> per document MAP_DEV_PX * mean over the g^2 grid points of
+    sqrt(dx^2 + dy^2): how far, in pixels of the 512 x 512 network input, b samples from where a does.  f32 distances, an f64
+    sum in a fixed order: equal maps give exactly 0.0, and a document in a batch gives what it gives alone.  One read-back."""
+    for t, name in ((a, "a"), (b, "b")):
+        if not torch.is_tensor(t) or t.dim() != 4 or t.shape[1] != 2 or t.shape[2] != t.shape[3]:
+            raise ValueError(f"map_deviation: {name} must be a [docs,2,g,g] tensor, got {tuple(t.shape) if torch.is_tensor(t) else type(t)}")
+    if a.shape != b.shape:
+        raise ValueError(f"map_deviation: a is {tuple(a.shape)}, b is {tuple(b.shape)}")
+    docs, g = int(a.shape[0]), int(a.shape[2])
+    if docs > 65535 or not NOISE_MIN_GRID <= g <= NOISE_MAX_GRID:
+        raise ValueError(f"map_deviation: {docs} documents at g = {g} (65535 documents at most, g {NOISE_MIN_GRID}..{NOISE_MAX_GRID})")
+    if docs == 0:
+        return []
+    _chk(a, torch.float32, "a")
+    _chk(b, torch.float32, "b")
+    if a.device != b.device:
+        raise ValueError(f"map_deviation: a is on {a.device}, b on {b.device}")
+    ws = torch.empty(_size_query("dvd_map_deviation_workspace_bytes", docs, g) // 8, dtype=torch.float64, device=a.device)
+    out = torch.empty(docs, dtype=torch.float64, device=a.device)
+    lib.call("dvd_map_deviation", ptr(a), ptr(b), docs, g, ptr(out), ptr(ws), stream_ptr())
+    return [float(v) for v in out.cpu()]

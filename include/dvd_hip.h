@@ -772,6 +772,23 @@ int dvd_corrupt_rgb8(const uint8_t* in, uint8_t* out, int n, int h, int w, int k
 int dvd_unit_to_rgb8(const float* y_nchw, uint8_t* out_nhwc, int n, int h, int w, void* stream);
 int dvd_rgb8_to_unit(const uint8_t* in_nhwc, float* y_nchw, int n, int h, int w, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Keyed sampler noise and the map deviation (tests/noise_model.py states both bit for bit).
+ * ---------------------------------------------------------------------------------------- */
+/* keys [docs,2] u32 on the device -> out [docs*n_hyp,2,g,g] f32 standard normals.  Element e = (ch g + i) g + j of sample
+ * doc n_hyp + h is lane e & 3 of Box-Muller on Philox4x32-10(key (keys[2 doc], keys[2 doc + 1]), counter (e >> 2, slot, h, 2)):
+ * a function of the document's key, h, slot and e only.  slot 0 is x_T, slot 1 + i the noise of step index i.  The logarithm,
+ * cosine and sine are written out in separately rounded f32 operations (no library call).  docs and n_hyp 0..65535 (a product
+ * of 0 is a no-op), g 2..8192, at most 2^38 quads.  One launch; every argument is checked before it. */
+int dvd_randn_keyed(const uint32_t* keys, int docs, int n_hyp, int g, uint32_t slot, float* out, void* stream);
+/* a, b [docs,2,g,g] f32 on the device -> out [docs] f64 (device) = 0.987 * 511 * mean_j sqrt(dx_j^2 + dy_j^2) over the g^2 grid
+ * points: how far, in pixels of the 512 x 512 network input, map b samples from where map a does.  The distances are f32
+ * (separately rounded), their sum is f64 in a fixed order (no atomics), so equal maps give exactly 0.  ws: device,
+ * dvd_map_deviation_workspace_bytes(docs, g) bytes (8 per 1024 grid points of a document, rounded up), 8-byte aligned; that
+ * query returns DVD_E_ARG for a bad shape.  docs 0..65535 (0 is a no-op), g 2..8192.  Two launches. */
+long dvd_map_deviation_workspace_bytes(int docs, int g);
+int dvd_map_deviation(const float* a, const float* b, int docs, int g, double* out, void* ws, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -7,7 +7,11 @@ dispatches to train_settings/<module>/<name>.run(settings).
 
 --corruption runs the reference's fifteen rounds (severity 5, corruption numbers 0..14 of the common-corruptions benchmark); here
 each round corrupts the network input on the device, writes under <name>/cNN_<kind>_s<severity> and the run
-ends with one table: kind -> mean of every metric of env.gt_dir.  --severity N and --corruption_number K choose one round."""
+ends with one table: kind -> mean of every metric of env.gt_dir.  --severity N and --corruption_number K choose one round.
+
+--keyed_noise keys the sampler's noise per document (settings.keyed_noise).  With corrupted rounds it runs the
+clean round first, under <name>, and the table gains the column map_dev: the mean distance, in pixels of the network input,
+between the map predicted from the corrupted input and the one predicted from the clean input - a number that needs no scan."""
 import argparse
 import importlib
 import os
@@ -21,12 +25,15 @@ import torch
 import admin.settings as ws_settings
 
 
-def corruption_rounds(corruption=False, severity=None, corruption_number=None):
+def corruption_rounds(corruption=False, severity=None, corruption_number=None, *, baseline=False):
     """[(severity, number)] of the rounds to run: the reference's fifteen under --corruption, one chosen round when --severity
-    or --corruption_number is given (5 and 0 where only the other one is), else the one clean round."""
+    or --corruption_number is given (5 and 0 where only the other one is), else the one clean round.  baseline: the clean round
+    (0, 0) comes first wherever a round corrupts."""
     if severity is None and corruption_number is None:
-        return [(5, c) for c in range(15)] if corruption else [(0, 0)]
-    return [(5 if severity is None else severity, 0 if corruption_number is None else corruption_number)]
+        rounds = [(5, c) for c in range(15)] if corruption else [(0, 0)]
+    else:
+        rounds = [(5 if severity is None else severity, 0 if corruption_number is None else corruption_number)]
+    return [(0, 0)] + rounds if baseline and any(sev != 0 for sev, _ in rounds) else rounds
 
 
 def round_name(name, severity, number):
@@ -48,21 +55,31 @@ def write_corruption_table(path, rows, metrics):
     return text
 
 
+MAP_DEV = "map_dev"        # the table's column under --keyed_noise, after the env.gt_dir metrics
+
+
 def run_sampling(train_module, train_name, seed, name, cudnn_benchmark=True, corruption=False, severity=None,
-                 corruption_number=None):
+                 corruption_number=None, *, keyed_noise=False):
     from dvd_amd import ops
     print(f"Sampling:  {train_module}  {train_name}\nDate: {date.today().strftime('%d/%m/%Y')}")
     settings = ws_settings.Settings()
     settings.module_name, settings.script_name = train_module, train_name
     settings.project_path = f"train_settings/{train_module}/{train_name}"
     settings.seed, settings.name = seed, name
+    if keyed_noise:                                           # absent without the flag: the run is what it always was
+        settings.keyed_noise = True
     save_dir = os.path.join(settings.env.workspace_dir, settings.project_path)
     os.makedirs(save_dir, exist_ok=True)
     shutil.copyfile(settings.project_path + ".py", os.path.join(save_dir, settings.script_name + ".py"))
     module = importlib.import_module(f"train_settings.{train_module.replace('/', '.')}.{train_name.replace('/', '.')}")
     run = getattr(module, "run")
     rows = []
-    for sev, number in corruption_rounds(corruption, severity, corruption_number):
+    rounds = corruption_rounds(corruption, severity, corruption_number, baseline=bool(keyed_noise))
+    if keyed_noise:                                           # a bad round is refused before the clean round runs for it
+        for sev, number in rounds:
+            if ops.corruption_severity(sev, "--severity"):
+                ops.corruption_number(number, "--corruption_number")
+    for sev, number in rounds:
         sev = ops.corruption_severity(sev, "--severity")
         if sev == 0:                                          # the clean round, as ever
             settings.severity, settings.corruption_number, settings.name = sev, number, name
@@ -74,16 +91,16 @@ def run_sampling(train_module, train_name, seed, name, cudnn_benchmark=True, cor
             print(f"corruption {number} ({kind}): no device kernel, round skipped")
             continue
         settings.severity, settings.corruption_number, settings.name = sev, number, round_name(name, sev, number)
-        for metric in ops.GT_METRIC_NAMES:                    # a round's scores are its own
+        for metric in ops.GT_METRIC_NAMES + (MAP_DEV,):         # a round's scores are its own
             if hasattr(settings, metric):
                 delattr(settings, metric)
         run(settings)
         means = {m: sum(v for _, v in getattr(settings, m)) / len(getattr(settings, m))
-                 for m in ops.GT_METRIC_NAMES if getattr(settings, m, None)}
+                 for m in ops.GT_METRIC_NAMES + ((MAP_DEV,) if keyed_noise else ()) if getattr(settings, m, None)}
         rows.append((number, kind, sev, means))
     settings.name = name
     if rows:
-        metrics = [m for m in ops.GT_METRIC_NAMES if any(m in r[3] for r in rows)]
+        metrics = [m for m in ops.GT_METRIC_NAMES if any(m in r[3] for r in rows)] + ([MAP_DEV] if keyed_noise else [])
         write_corruption_table(os.path.join("vis_hp", str(settings.env.eval_dataset_name), name, "corruption_table.txt"), rows, metrics)
 
 
@@ -97,13 +114,15 @@ def main():
     p.add_argument("--corruption", action="store_true")
     p.add_argument("--severity", type=int, default=None, help="one chosen round: its severity 0..5 (5 if only --corruption_number is given)")
     p.add_argument("--corruption_number", type=int, default=None, help="one chosen round: its corruption 0..18 (0 if only --severity is given)")
+    p.add_argument("--keyed_noise", action="store_true", help="key the sampler's noise per document; with corrupted rounds: the clean "
+                   "round first, then the column map_dev in the table")
     a = p.parse_args()
     a.seed = torch.initial_seed() & (2 ** 32 - 1)      # as the reference: the CLI value is overwritten (:77-78)
     print(f"Seed is {a.seed}")
     random.seed(int(a.seed))
     np.random.seed(a.seed)
     run_sampling(a.train_module, a.train_name, seed=a.seed, name=a.name, cudnn_benchmark=a.cudnn_benchmark,
-                 corruption=a.corruption, severity=a.severity, corruption_number=a.corruption_number)
+                 corruption=a.corruption, severity=a.severity, corruption_number=a.corruption_number, keyed_noise=a.keyed_noise)
 
 
 if __name__ == "__main__":
