@@ -14,6 +14,17 @@ __device__ __forceinline__ T wave_sum(T v) {
   return v;
 }
 
+// Maximum over the 64 lanes of a wave, valid in lane 0, in the same order; for values that hold no NaN.
+template <typename T>
+__device__ __forceinline__ T wave_max(T v) {
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) {
+    const T o = __shfl_down(v, d, 64);
+    v = o > v ? o : v;
+  }
+  return v;
+}
+
 // Inclusive Hillis-Steele scan of one value per thread of a 256-thread workgroup in lds[256]: returns the thread's
 // join(v_0, .., v_tid) and *total = that of thread 255.  join(earlier, later) need not commute; join(identity, x) stands for
 // "nothing in front of x".  Two barriers per step; the caller puts a barrier between the return and the next write of lds.

@@ -10,6 +10,7 @@
 // streams; the 1-pixel-per-lane-x-4-rows scalar kernels (kept below for win < 2, unaligned widths and > 4 GiB planes)
 // reach 3.5 TB/s.
 #include "common.h"
+#include "interp_core.h"
 #include "mfma.h"
 #include "ragged.h"
 
@@ -472,28 +473,8 @@ struct UpParams {
   int small;        // h + w <= 128: torch's CPU dispatch takes its channels-last kernel, whose sum has another order (below)
 };
 
-// One axis of F.interpolate(bilinear, align_corners=True) as ATen's CPU kernel computes it (UpSampleKernel.cpp,
-// compute_source_index_and_lambda): src = scale * dst; i0 = min(floor(src), in - 1); l1 = clamp(src - i0, 0, 1); l0 = 1 - l1.
-__device__ __forceinline__ void interp_axis(float scale, int dst, int in, int& i0, int& i1, float& l0, float& l1) {
-  const float s = __fmul_rn(scale, (float)dst);
-  i0 = min((int)s, in - 1);
-  i1 = min(i0 + 1, in - 1);
-  l1 = fminf(fmaxf(__fsub_rn(s, (float)i0), 0.f), 1.f);
-  l0 = __fsub_rn(1.f, l1);
-}
-// ... and its four-value sum.  torch picks one of two CPU kernels by the OUTPUT size (UpSampleKernel.cpp,
-// _use_vectorized_kernel_cond_2d; both orders found by bit-exact probing, oracle/aten_order.py restates them):
-//   h + w > 128   separable: t = fma(left, lx0, right * lx1) per row, then fma(t_upper, ly0, t_lower * ly1)
-//   h + w <= 128  channels-last kernel: weights w_rc = l_y(r) * l_x(c), sum fma(d, w11, fma(c, w10, fma(a, w00, b * w01)))
-__device__ __forceinline__ float interp_sum(float a, float b, float c, float d, float lx0, float lx1, float ly0, float ly1,
-                                            int small) {
-  if (small) {
-    const float w00 = __fmul_rn(ly0, lx0), w01 = __fmul_rn(ly0, lx1), w10 = __fmul_rn(ly1, lx0), w11 = __fmul_rn(ly1, lx1);
-    return fmaf(d, w11, fmaf(c, w10, fmaf(a, w00, __fmul_rn(b, w01))));
-  }
-  const float t0 = fmaf(a, lx0, __fmul_rn(b, lx1)), t1 = fmaf(c, lx0, __fmul_rn(d, lx1));
-  return fmaf(t0, ly0, __fmul_rn(t1, ly1));
-}
+// interp_axis and interp_sum, one axis of F.interpolate(bilinear, align_corners=True) and its four-value sum in the order of
+// ATen's CPU kernels, are interp_core.h's: the flow pictures (flowviz.hip) upsample the same map with the same arithmetic.
 
 // The per-AXIS terms of one output coordinate: the flow's and the 512-grid base's source indices and lambdas, and the base
 // grid's two values k / 511 (an IEEE division each).  They depend on the column (or the row) alone, so a kernel that walks

@@ -359,10 +359,48 @@ def unwarp_tail(batch, flow, mode, device):
     return outs
 
 
-def emit(settings, logger, batch, outs, results, opts, device):
-    """The pages of one batch into `results`; the picture if env.visualize, the scores if env.gt_dir."""
-    for d, out in zip(batch, outs):
+FLOW_OUTPUTS = ("png", "flo", "npy")     # what settings.flow_outputs may name
+
+
+def flow_outputs_of(settings):
+    """`settings.flow_outputs` (run_sampling.py --flow_outputs): a comma-separated list of FLOW_OUTPUTS names without repeats ->
+    the names, in the order of FLOW_OUTPUTS.  Absent or "" means none; anything else is a ValueError that names the attribute."""
+    value = getattr(settings, "flow_outputs", "")
+    if isinstance(value, str) and value == "":
+        return ()
+    names = [n.strip() for n in value.split(",")] if isinstance(value, str) else None
+    if not names or any(n not in FLOW_OUTPUTS for n in names) or len(set(names)) != len(names):
+        raise ValueError(f"settings.flow_outputs must be a comma-separated list of {FLOW_OUTPUTS} without repeats, got {value!r}")
+    return tuple(n for n in FLOW_OUTPUTS if n in names)
+
+
+def write_flow_outputs(settings, logger, d, flow, h, w, outputs, huffman="fixed"):
+    """The predicted map of one document (`flow` [2,G,G], what the unwarp tail consumed) under pred_flow/ (DESIGN.md 4.12):
+    'png' flow_<stem>.png, the colour-wheel picture of its displacement at the page's size h x w with norm 'max', and one log
+    line with the largest radius; 'flo' flow_<stem>.flo, that displacement; 'npy' flow_<stem>.npy, the coarse map itself -
+    what ops.unwarp_u8 needs to redo the page."""
+    from utils_flow.visualization_utils import _stem
+    out_dir = f"vis_hp/{settings.env.eval_dataset_name}/{settings.name}/pred_flow"
+    os.makedirs(out_dir, exist_ok=True)
+    name = d["path"] if os.path.splitext(d["path"])[1] else d["path"] + ".png"
+    base = f"{out_dir}/flow_{_stem([name])}"
+    flow = flow.detach().float().contiguous()
+    if "png" in outputs:
+        _, largest = ops.flow_picture_to_file(flow, h, w, base + ".png", norm="max", huffman=huffman, return_radius=True)
+        logger.info(f"{d['path']} flow_rad_max {largest:.6f}")
+    if "flo" in outputs:
+        ops.flow_write_flo(flow, h, w, base + ".flo")
+    if "npy" in outputs:
+        np.save(base + ".npy", flow.cpu().numpy())
+
+
+def emit(settings, logger, batch, outs, results, opts, device, *, flow=None, flow_outputs=()):
+    """The pages of one batch into `results`; the picture if env.visualize, the scores if env.gt_dir; the maps `flow` [B,2,G,G]
+    as the files `flow_outputs` names (settings.flow_outputs)."""
+    for j, (d, out) in enumerate(zip(batch, outs)):
         results.append((d["path"], out))
+        if flow_outputs:
+            write_flow_outputs(settings, logger, d, flow[j], int(out.shape[0]), int(out.shape[1]), flow_outputs, opts.png_huffman)
         if settings.env.visualize:
             from utils_flow.visualization_utils import visualize_dewarping
             name = d["path"] if os.path.splitext(d["path"])[1] else d["path"] + ".png"
@@ -407,13 +445,15 @@ def run_evaluation_docunet(settings, logger, val_loader, diffusion, model, pretr
     `val_loader` yields the reference's dicts or this package's documents (`documents_of`); env.batch_docs of them go through
     each pass (the reference: 1): adopt, ingest + pre-stage nets (:162-216), the sampler (:247-265), the unwarp tail, then the
     picture and the scores.  The engine-side switches (dvd_amd/run_options.py) are read and checked once, before the loader is
-    touched and before anything is written; so are settings.severity / corruption_number and settings.keyed_noise
-    (4.11: the sampler's noise keyed per document, reference maps kept and later rounds scored with map_dev).  The pre-stage models
+    touched and before anything is written; so are settings.severity / corruption_number, settings.keyed_noise
+    (4.11: the sampler's noise keyed per document, reference maps kept and later rounds scored with map_dev) and
+    settings.flow_outputs (4.12: every document's predicted map written under pred_flow/).  The pre-stage models
     may all be None when every document carries ready
     conditioning tensors.  Returns [(path, uint8 [H,W,3] device tensor)] (the reference returns None)."""
     opts = RunOptions.from_env(settings.env)
     corruption = corruption_of(settings)
     keyed = {"keyed_noise": True} if keyed_noise_of(settings) else {}    # absent or False: sample_batch is called as it always was
+    outputs = flow_outputs_of(settings)         # absent or "": emit is called as it always was
     stage = {}                                  # nothing corrupted: prepare_conditioning is called exactly as it always was
     if corruption is not None:
         logger.info(f"corruption {corruption[0]} ({ops.CORRUPTIONS[corruption[0]]}) severity {corruption[1]}")
@@ -440,7 +480,8 @@ def run_evaluation_docunet(settings, logger, val_loader, diffusion, model, pretr
         if keyed:
             score_map_deviation(settings, logger, batch, flow, clean=corruption is None)
         outs = unwarp_tail(batch, flow, opts.unwarp_mode, device)
-        emit(settings, logger, batch, outs, results, opts, device)
+        maps = {"flow": flow, "flow_outputs": outputs} if outputs else {}
+        emit(settings, logger, batch, outs, results, opts, device, **maps)
     summarize(settings, logger, opts, times, results)
     if keyed and (corruption is not None or settings.map_dev):
         summarize_map_deviation(settings, logger, len(results))

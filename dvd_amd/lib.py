@@ -127,14 +127,18 @@ class SflowParams(C.Structure):
 SFLOW_DEFAULTS = dict(levels=4, w_top=10, w=2, iters_top=60, iters=30, alpha=510, d=10200, gamma=1, T=8160, eps=1 << 17)
 SFLOW_MIN_TOP = 12    # DVD_SFLOW_MIN_TOP: least side of the top pyramid level
 
-RAGGED_CAP = 64   # DVD_RAGGED_CAP: documents per launch of the ragged entry points (larger batches are cut by the library)
+FLOW_NORM_DIAG, FLOW_NORM_MAX = 0, 1   # DVD_FLOW_NORM_*: rad_max of a flow picture
+E_FLOW_SHAPE = -50                     # DVD_E_FLOW_SHAPE
+
+RAGGED_CAP = 64  # DVD_RAGGED_CAP: documents per launch of the ragged entry points (larger batches are cut by the library)
 
 NON_STATUS = {"dvd_last_error", "dvd_version", "dvd_engine_workspace_bytes", "dvd_engine_tensor_count",
               "dvd_flash_attn_kernel_name", "dvd_gemm_kernel_name", "dvd_convnet_workspace_bytes", "dvd_convnet_weight_floats",
               "dvd_ingest_scratch_bytes", "dvd_ingest_ragged_scratch_bytes", "dvd_resize_gray_scratch_bytes",
               "dvd_msssim_workspace_bytes", "dvd_png_bound", "dvd_png_scratch_bytes", "dvd_png_scratch_bytes_huff", "dvd_jpeg_bound",
               "dvd_jpeg_scratch_bytes", "dvd_sflow_level_workspace_bytes", "dvd_sflow_workspace_bytes",
-              "dvd_adist_workspace_bytes", "dvd_corrupt_supported", "dvd_corrupt_table", "dvd_map_deviation_workspace_bytes"}
+              "dvd_adist_workspace_bytes", "dvd_corrupt_supported", "dvd_corrupt_table", "dvd_map_deviation_workspace_bytes",
+              "dvd_flow_workspace_bytes"}
 
 # name -> argtypes; kept in one table so tests can check every symbol of include/dvd_hip.h
 SIGNATURES = {
@@ -221,6 +225,11 @@ SIGNATURES = {
     "dvd_randn_keyed": [c_void, C.c_int, C.c_int, C.c_int, C.c_uint32, c_void, c_void],
     "dvd_map_deviation_workspace_bytes": [C.c_int, C.c_int],
     "dvd_map_deviation": [c_void, c_void, C.c_int, C.c_int, c_void, c_void, c_void],
+    "dvd_flow_workspace_bytes": [C.c_int, C.c_int, C.c_int],
+    "dvd_flow_radius_max": [c_void, C.c_int, C.c_int, C.c_int, C.c_float, c_void, c_void, c_void],
+    "dvd_flow_to_image_rgb8": [c_void, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, c_void, c_void, c_void, c_void],
+    "dvd_flow_full_uv": [c_void, C.c_int, C.c_int, C.c_int, C.c_int, c_void, c_void],
+    "dvd_flow_picture_rgb8": [c_void, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_void, c_void, c_void, c_void],
     "dvd_png_bound": [C.c_int, C.c_int],
     "dvd_png_scratch_bytes": [C.c_int, C.c_int],
     "dvd_png_encode_rgb8": [c_void, C.c_int, C.c_int, c_void, C.c_long, c_void, c_void, c_void],
@@ -256,7 +265,7 @@ RESTYPES = {"dvd_gemm_kernel_name": C.c_char_p, "dvd_ingest_ragged_scratch_bytes
             "dvd_resize_gray_scratch_bytes": C.c_long, "dvd_msssim_workspace_bytes": C.c_long,
             "dvd_sflow_level_workspace_bytes": C.c_long, "dvd_sflow_workspace_bytes": C.c_long,
             "dvd_adist_workspace_bytes": C.c_long, "dvd_map_deviation_workspace_bytes": C.c_long,
-            "dvd_png_bound": C.c_long, "dvd_png_scratch_bytes": C.c_long, "dvd_png_scratch_bytes_huff": C.c_long,
+            "dvd_flow_workspace_bytes": C.c_long, "dvd_png_bound": C.c_long, "dvd_png_scratch_bytes": C.c_long, "dvd_png_scratch_bytes_huff": C.c_long,
             "dvd_jpeg_bound": C.c_long, "dvd_jpeg_scratch_bytes": C.c_long}
 
 # entry points that exist only in the lab build (benchmarks/lab/dvd_hip_lab.h; loaded through use_library)

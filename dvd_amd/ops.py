@@ -1237,3 +1237,175 @@ def map_deviation(a: torch.Tensor, b: torch.Tensor) -> list:
     out = torch.empty(docs, dtype=torch.float64, device=a.device)
     lib.call("dvd_map_deviation", ptr(a), ptr(b), docs, g, ptr(out), ptr(ws), stream_ptr())
     return [float(v) for v in out.cpu()]
+
+
+# ---- flow pictures and .flo files of a predicted map (dvd_amd/csrc/flowviz.hip; definition: DESIGN.md 4.12, tests/flowviz_model.py)
+FLOW_NORMS = {"diag": lib.FLOW_NORM_DIAG, "max": lib.FLOW_NORM_MAX}
+FLOW_MAX_SIDE, FLOW_MAX_IMAGES = 16384, 65535
+FLO_TAG = 202021.25               # the f32 that opens a Middlebury .flo file ('PIEH' as bytes)
+
+
+def _flow_norm(norm, name):
+    if not isinstance(norm, str) or norm not in FLOW_NORMS:
+        raise ValueError(f"{name}: norm must be {either(FLOW_NORMS)}, got {norm!r}")
+    return FLOW_NORMS[norm]
+
+
+def _flow_clip(clip_flow, name):
+    """clip_flow as the library takes it: None -> -1 (no clip), otherwise a finite number >= 0."""
+    if clip_flow is None:
+        return -1.0
+    if isinstance(clip_flow, bool) or not isinstance(clip_flow, (int, float, np.integer, np.floating)) \
+            or not np.isfinite(clip_flow) or clip_flow < 0:
+        raise ValueError(f"{name}: clip_flow must be None or a finite number >= 0, got {clip_flow!r}")
+    return float(clip_flow)
+
+
+def _flow_size(h, w, n, name):
+    if not _is_int(h) or not _is_int(w) or not 1 <= h <= FLOW_MAX_SIDE or not 1 <= w <= FLOW_MAX_SIDE:
+        raise ValueError(f"{name}: h and w must be integers 1..{FLOW_MAX_SIDE}, got {h!r} x {w!r}")
+    if n > FLOW_MAX_IMAGES:
+        raise ValueError(f"{name}: {n} images ({FLOW_MAX_IMAGES} at most)")
+    return int(h), int(w)
+
+
+def _flow_field(field, name):
+    """(the field as [n,h,w,2], n, h, w, whether it came as [h,w,2]) of a displacement field, checked."""
+    if not torch.is_tensor(field) or field.dim() not in (3, 4) or field.shape[-1] != 2:
+        raise ValueError(f"{name}: expected a [H,W,2] or [N,H,W,2] tensor, got {tuple(field.shape) if torch.is_tensor(field) else type(field)}")
+    single = field.dim() == 3
+    n = 1 if single else int(field.shape[0])
+    h, w = _flow_size(int(field.shape[-3]), int(field.shape[-2]), n, name)
+    if field.dtype != torch.float32 or not field.is_contiguous():
+        raise ValueError(f"{name}: expected contiguous float32, got {field.dtype} contiguous={field.is_contiguous()}")
+    return field, n, h, w, single
+
+
+def _flow_coarse(flow, name):
+    """(n, g, whether it came as [2,g,g]) of a coarse map [n,2,g,g] or [2,g,g], checked."""
+    if not torch.is_tensor(flow) or flow.dim() not in (3, 4) or flow.shape[-3] != 2 or flow.shape[-1] != flow.shape[-2]:
+        raise ValueError(f"{name}: expected a [2,G,G] or [N,2,G,G] tensor, got {tuple(flow.shape) if torch.is_tensor(flow) else type(flow)}")
+    g = int(flow.shape[-1])
+    if not NOISE_MIN_GRID <= g <= NOISE_MAX_GRID:
+        raise ValueError(f"{name}: G must be {NOISE_MIN_GRID}..{NOISE_MAX_GRID}, got {g}")
+    if flow.dtype != torch.float32 or not flow.is_contiguous():
+        raise ValueError(f"{name}: expected contiguous float32, got {flow.dtype} contiguous={flow.is_contiguous()}")
+    return (1 if flow.dim() == 3 else int(flow.shape[0])), g, flow.dim() == 3
+
+
+def _flow_workspace(n, h, w, dev):
+    """(largest [n] f32, ws) for norm 'max'."""
+    ws = torch.empty(max(_size_query("dvd_flow_workspace_bytes", n, h, w) // 4, 1), dtype=torch.float32, device=dev)
+    return torch.empty(n, dtype=torch.float32, device=dev), ws
+
+
+def flow_radius_max(flow: torch.Tensor, clip_flow=None) -> torch.Tensor:
+    """A displacement field [N,H,W,2] (or [H,W,2]) f32 in pixels on the device -> [N] (or a 0-d) f32 tensor: per image the largest
+    sqrt(u^2 + v^2) over its pixels with finite components, after the clip - rad_max of norm 'max' less its 1e-5.  Two launches
+    in a fixed order without atomics: the value is a function of the field alone."""
+    clip = _flow_clip(clip_flow, "flow_radius_max")
+    field, n, h, w, single = _flow_field(flow, "flow_radius_max")
+    _chk(field, torch.float32, "flow")
+    out, ws = _flow_workspace(n, h, w, field.device)
+    if n:
+        lib.call("dvd_flow_radius_max", ptr(field), n, h, w, C.c_float(clip), ptr(out), ptr(ws), stream_ptr())
+    return out[0] if single else out
+
+
+def flow_to_image(flow: torch.Tensor, clip_flow=None, convert_to_bgr: bool = False, norm: str = "diag") -> torch.Tensor:
+    """datasets/utils/flow_viz.py flow_to_image on the device: a displacement field [H,W,2] (or [N,H,W,2]) f32 in pixels ->
+    the colour-wheel picture [H,W,3] (or [N,H,W,3]) uint8.  norm 'diag' (the reference): rad_max = sqrt((W//2)^2 + (H//2)^2) +
+    1e-5; 'max' (the Middlebury rule): the image's largest radius + 1e-5.  clip_flow as the reference has it: both components
+    clipped to [0, clip_flow].  A pixel with a non-finite component is black."""
+    code = _flow_norm(norm, "flow_to_image")
+    clip = _flow_clip(clip_flow, "flow_to_image")
+    field, n, h, w, single = _flow_field(flow, "flow_to_image")
+    _chk(field, torch.float32, "flow")
+    out = torch.empty((h, w, 3) if single else (n, h, w, 3), dtype=torch.uint8, device=field.device)
+    if n == 0:
+        return out
+    largest, ws = _flow_workspace(n, h, w, field.device) if norm == "max" else (None, None)
+    lib.call("dvd_flow_to_image_rgb8", ptr(field), n, h, w, code, C.c_float(clip), int(bool(convert_to_bgr)), ptr(out), ptr(largest),
+             ptr(ws), stream_ptr())
+    return out
+
+
+def flow_full_uv(flow: torch.Tensor, h: int, w: int) -> torch.Tensor:
+    """The coarse map [N,2,G,G] (or [2,G,G]) f32 -> its full-resolution pixel displacement [N,h,w,2] (or [h,w,2]) f32:
+    F.interpolate(flow, (h, w), bilinear, align_corners=True) in the arithmetic of the unwarp tail, then u = s_x (w - 1),
+    v = s_y (h - 1).  The payload of a .flo file.  One launch."""
+    n, g, single = _flow_coarse(flow, "flow_full_uv")
+    h, w = _flow_size(h, w, n, "flow_full_uv")
+    _chk(flow, torch.float32, "flow")
+    out = torch.empty((h, w, 2) if single else (n, h, w, 2), dtype=torch.float32, device=flow.device)
+    if n:
+        lib.call("dvd_flow_full_uv", ptr(flow), n, g, h, w, ptr(out), stream_ptr())
+    return out
+
+
+def flow_picture(flow: torch.Tensor, h: int, w: int, norm: str = "diag", convert_to_bgr: bool = False, return_radius: bool = False):
+    """The coarse map [N,2,G,G] (or [2,G,G]) -> its picture [N,h,w,3] (or [h,w,3]) uint8 in ONE pass: the bytes of
+    flow_to_image(flow_full_uv(flow, h, w), norm=norm) without the 8 B/px field ever being written.  return_radius: also the
+    [N] (or 0-d) f32 tensor of flow_radius_max of that field (norm 'max' only; None otherwise)."""
+    code = _flow_norm(norm, "flow_picture")
+    n, g, single = _flow_coarse(flow, "flow_picture")
+    h, w = _flow_size(h, w, n, "flow_picture")
+    _chk(flow, torch.float32, "flow")
+    out = torch.empty((h, w, 3) if single else (n, h, w, 3), dtype=torch.uint8, device=flow.device)
+    largest, ws = _flow_workspace(n, h, w, flow.device) if norm == "max" else (None, None)
+    if n:
+        lib.call("dvd_flow_picture_rgb8", ptr(flow), n, g, h, w, code, int(bool(convert_to_bgr)), ptr(out), ptr(largest), ptr(ws),
+                 stream_ptr())
+    if not return_radius:
+        return out
+    return out, (None if largest is None else (largest[0] if single else largest))
+
+
+def _one_map(flow, name):
+    n, _, single = _flow_coarse(flow, name)
+    if n != 1:
+        raise ValueError(f"{name}: one map per file, got {n}")
+    return flow if single else flow[0]
+
+
+def flow_picture_to_file(flow: torch.Tensor, h: int, w: int, path: str, norm: str = "max", huffman: str = "fixed",
+                         return_radius: bool = False):
+    """The picture of ONE coarse map [2,G,G] (or [1,2,G,G]) as a PNG file: flow_picture, then png_encode_to_file - only the
+    compressed file crosses to the host.  Returns the file's bytes; with return_radius (the file's bytes, the largest radius as
+    a float or None)."""
+    png_huffman_flag(huffman, "flow_picture_to_file")
+    img, largest = flow_picture(_one_map(flow, "flow_picture_to_file"), h, w, norm=norm, return_radius=True)
+    nbytes = png_encode_to_file(img, path, huffman)
+    return (nbytes, None if largest is None else float(largest)) if return_radius else nbytes
+
+
+def flo_write(field, path: str) -> int:
+    """A host field [h,w,2] float32 as a Middlebury .flo file: the f32 tag 202021.25, int32 w, int32 h, then h w interleaved
+    (u, v) f32, little endian.  Returns the file's bytes."""
+    field = np.asarray(field)
+    if field.ndim != 3 or field.shape[2] != 2 or min(field.shape[:2]) < 1 or field.dtype != np.float32:
+        raise ValueError(f"flo_write: expected a [h,w,2] float32 array, got {field.shape} {field.dtype}")
+    h, w = field.shape[:2]
+    with open(path, "wb") as f:
+        f.write(np.asarray([FLO_TAG], "<f4").tobytes())
+        f.write(np.asarray([w, h], "<i4").tobytes())
+        f.write(field.astype("<f4", copy=False).tobytes())
+    return 12 + field.nbytes
+
+
+def flow_write_flo(flow: torch.Tensor, h: int, w: int, path: str) -> int:
+    """The full-resolution displacement of ONE coarse map [2,G,G] (or [1,2,G,G]), flow_full_uv, as a Middlebury .flo file
+    (flo_write).  Returns the file's bytes."""
+    return flo_write(flow_full_uv(_one_map(flow, "flow_write_flo"), h, w).cpu().numpy(), path)
+
+
+def flow_read_flo(path: str) -> np.ndarray:
+    """A Middlebury .flo file -> the field [h,w,2] float32 (host).  A wrong tag, size or length is a ValueError naming the file."""
+    with open(path, "rb") as f:
+        data = f.read()
+    if len(data) < 12 or np.frombuffer(data, "<f4", 1)[0] != np.float32(FLO_TAG):
+        raise ValueError(f"{path}: not a .flo file (it does not open with the tag {FLO_TAG})")
+    w, h = (int(v) for v in np.frombuffer(data, "<i4", 2, 4))
+    if h < 1 or w < 1 or len(data) != 12 + 8 * h * w:
+        raise ValueError(f"{path}: a .flo file of {w} x {h} holds {12 + 8 * max(h, 0) * max(w, 0)} bytes, this one {len(data)}")
+    return np.frombuffer(data, "<f4", 2 * h * w, 12).reshape(h, w, 2).astype(np.float32)

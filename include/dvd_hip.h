@@ -789,6 +789,35 @@ int dvd_randn_keyed(const uint32_t* keys, int docs, int n_hyp, int g, uint32_t s
 long dvd_map_deviation_workspace_bytes(int docs, int g);
 int dvd_map_deviation(const float* a, const float* b, int docs, int g, double* out, void* ws, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Flow pictures and the .flo payload of a predicted map (tests/flowviz_model.py states every entry point byte
+ * for byte).  A picture is the Middlebury colour-wheel image of a displacement field in pixels: hue = direction, saturation =
+ * radius / rad_max.  Separately rounded f32 with a written-out angle; a pixel with a non-finite component is (0,0,0).
+ * n 0..65535 (0 is a no-op), sides 1..16384, g 2..8192: anything else is DVD_E_FLOW_SHAPE, before any launch.  No scratch
+ * memory, no atomics, no host read-back.
+ * ---------------------------------------------------------------------------------------- */
+#define DVD_E_FLOW_SHAPE (-50)
+#define DVD_FLOW_NORM_DIAG 0 /* rad_max = sqrt((w/2)^2 + (h/2)^2) + 1e-5, integer halves: datasets/utils/flow_viz.py */
+#define DVD_FLOW_NORM_MAX 1  /* rad_max = the image's largest radius + 1e-5: the Middlebury rule */
+/* bytes of `ws` for n images of h x w (4 per 4096 pixels of an image, rounded up), or DVD_E_FLOW_SHAPE */
+long dvd_flow_workspace_bytes(int n, int h, int w);
+/* field [n,h,w,2] f32 (u, v interleaved, 8-byte aligned) -> out [n] f32: per image the largest sqrt(u^2 + v^2) over its pixels
+ * with finite components (0 if there is none), after the clip.  clip < 0: none; otherwise both components are clipped to
+ * [0, clip] first (the reference's clip_flow).  Two launches in a fixed order. */
+int dvd_flow_radius_max(const float* field, int n, int h, int w, float clip, float* out, void* ws, void* stream);
+/* field [n,h,w,2] f32 -> out [n,h,w,3] u8 (4-byte aligned), RGB or, with bgr != 0, BGR.  norm DVD_FLOW_NORM_MAX runs
+ * dvd_flow_radius_max first and needs `largest` [n] f32 (it receives the radii) and `ws`; with DVD_FLOW_NORM_DIAG both may be
+ * null.  One launch, or three. */
+int dvd_flow_to_image_rgb8(const float* field, int n, int h, int w, int norm, float clip, int bgr, uint8_t* out, float* largest,
+                           void* ws, void* stream);
+/* flow [n,2,g,g] f32, the coarse map -> out [n,h,w,2] f32: s = F.interpolate(flow, (h, w), bilinear, align_corners=True) in the
+ * arithmetic of the unwarp tail, then u = s_x (w - 1), v = s_y (h - 1).  The payload of a Middlebury .flo file.  One launch. */
+int dvd_flow_full_uv(const float* flow, int n, int g, int h, int w, float* out, void* stream);
+/* The coarse map -> out [n,h,w,3] u8 in one pass: the bytes of dvd_flow_to_image_rgb8 (no clip) on dvd_flow_full_uv, without
+ * writing the field.  norm, bgr, largest, ws as above (DVD_FLOW_NORM_MAX takes the maximum over the same recomputed field). */
+int dvd_flow_picture_rgb8(const float* flow, int n, int g, int h, int w, int norm, int bgr, uint8_t* out, float* largest, void* ws,
+                          void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -11,7 +11,10 @@ ends with one table: kind -> mean of every metric of env.gt_dir.  --severity N a
 
 --keyed_noise keys the sampler's noise per document (settings.keyed_noise).  With corrupted rounds it runs the
 clean round first, under <name>, and the table gains the column map_dev: the mean distance, in pixels of the network input,
-between the map predicted from the corrupted input and the one predicted from the clean input - a number that needs no scan."""
+between the map predicted from the corrupted input and the one predicted from the clean input - a number that needs no scan.
+
+--flow_outputs png,flo,npy writes the predicted map of every document under <name>/pred_flow (settings.flow_outputs; DESIGN.md
+4.12): its colour-wheel picture, its full-resolution .flo field and / or the coarse map itself.  Every round writes its own."""
 import argparse
 import importlib
 import os
@@ -59,7 +62,7 @@ MAP_DEV = "map_dev"        # the table's column under --keyed_noise, after the e
 
 
 def run_sampling(train_module, train_name, seed, name, cudnn_benchmark=True, corruption=False, severity=None,
-                 corruption_number=None, *, keyed_noise=False):
+                 corruption_number=None, *, keyed_noise=False, flow_outputs=""):
     from dvd_amd import ops
     print(f"Sampling:  {train_module}  {train_name}\nDate: {date.today().strftime('%d/%m/%Y')}")
     settings = ws_settings.Settings()
@@ -68,6 +71,8 @@ def run_sampling(train_module, train_name, seed, name, cudnn_benchmark=True, cor
     settings.seed, settings.name = seed, name
     if keyed_noise:                                           # absent without the flag: the run is what it always was
         settings.keyed_noise = True
+    if flow_outputs:                                          # likewise: "" leaves the attribute absent
+        settings.flow_outputs = flow_outputs
     save_dir = os.path.join(settings.env.workspace_dir, settings.project_path)
     os.makedirs(save_dir, exist_ok=True)
     shutil.copyfile(settings.project_path + ".py", os.path.join(save_dir, settings.script_name + ".py"))
@@ -116,13 +121,16 @@ def main():
     p.add_argument("--corruption_number", type=int, default=None, help="one chosen round: its corruption 0..18 (0 if only --severity is given)")
     p.add_argument("--keyed_noise", action="store_true", help="key the sampler's noise per document; with corrupted rounds: the clean "
                    "round first, then the column map_dev in the table")
+    p.add_argument("--flow_outputs", type=str, default="", help="comma-separated list of png, flo, npy: what to write of every "
+                   "document's predicted map under pred_flow/ (nothing by default)")
     a = p.parse_args()
     a.seed = torch.initial_seed() & (2 ** 32 - 1)      # as the reference: the CLI value is overwritten (:77-78)
     print(f"Seed is {a.seed}")
     random.seed(int(a.seed))
     np.random.seed(a.seed)
     run_sampling(a.train_module, a.train_name, seed=a.seed, name=a.name, cudnn_benchmark=a.cudnn_benchmark,
-                 corruption=a.corruption, severity=a.severity, corruption_number=a.corruption_number, keyed_noise=a.keyed_noise)
+                 corruption=a.corruption, severity=a.severity, corruption_number=a.corruption_number, keyed_noise=a.keyed_noise,
+                 flow_outputs=a.flow_outputs)
 
 
 if __name__ == "__main__":
