@@ -20,13 +20,16 @@ from .run_options import GT_METRICS, RunOptions, parse_gt_metrics  # noqa: F401 
 
 
 def run_sample_lr_dewarping(settings, logger, diffusion, model, radius, source, feature_size, raw_corr, init_flow, c20,
-                            source_64, pyramid, doc_mask, seg_map_all=None, textline_map=None, init_feat=None, *, noise_keys=None):
+                            source_64, pyramid, doc_mask, seg_map_all=None, textline_map=None, init_feat=None, *, noise_keys=None,
+                            keep_hypotheses=False):
     """One batch of documents through the sampler, with the reference's positional signature (evaluation.py:80-138; call
     site :247-265): returns the clamped flow [B,2,G,G].  `radius`, `raw_corr`, `source_64` and `pyramid` are dead in the
     reference's body as well (the correlation code is commented out, the conv pyramid belongs to the denoiser); `c20` is
     the reference's `src_feat`, None on the live configuration (train_VGG=True, :219-221).  B = source.shape[0] documents
     are sampled in one engine batch (the reference: B = 1).  noise_keys (keyword only, an extension): one (k0, k1) pair per
-    document, handed to the loop in sampling_kwargs - the sampler's noise is then keyed per document."""
+    document, handed to the loop in sampling_kwargs - the sampler's noise is then keyed per document.
+    keep_hypotheses=True (keyword only, an extension): returns (flow, hypotheses), the second the clamped per-sample maps
+    [B*n_batch,2,G,G] the mean was taken over (sampling_kwargs["keep_hypotheses"])."""
     kw = {"init_flow": init_flow, "src_feat": c20, "src_64": None, "y512": source, "tmode": settings.env.train_mode,
           "mask_cat": doc_mask, "init_feat": init_feat, "iter": settings.env.iter}
     if not settings.env.use_gt_mask:
@@ -42,10 +45,14 @@ def run_sample_lr_dewarping(settings, logger, diffusion, model, radius, source, 
     sampling_kwargs = {"src_img": source}
     if noise_keys is not None:
         sampling_kwargs["noise_keys"] = list(noise_keys)
-    sample, _ = diffusion.ddim_sample_loop(
+    if keep_hypotheses:
+        sampling_kwargs["keep_hypotheses"] = True
+    sample, final = diffusion.ddim_sample_loop(
         model, (B, 2, feature_size, feature_size), noise=None, clip_denoised=settings.env.clip_denoised,
         model_kwargs=kw, eta=0.0, progress=True, denoised_fn=None, sampling_kwargs=sampling_kwargs, logger=logger,
         n_batch=settings.env.n_batch, time_variant=settings.env.time_variant, pyramid=pyramid, **extra)
+    if keep_hypotheses:
+        return th.clamp(sample, min=-1, max=1), final["hypotheses"]
     return th.clamp(sample, min=-1, max=1)
 
 
@@ -295,16 +302,19 @@ def keyed_noise_of(settings):
     return bool(flag)
 
 
-def sample_batch(settings, logger, diffusion, model, batch, grid, device, *, keyed_noise=None):
+def sample_batch(settings, logger, diffusion, model, batch, grid, device, *, keyed_noise=None, keep_hypotheses=False):
     """The conditioned documents of one batch through `run_sample_lr_dewarping` (evaluation.py:247-265): the flow [B,2,G,G].
     keyed_noise (None: settings.keyed_noise): the sampler's noise is keyed per document by (settings.seed, path), the
-    corruption stage's key; False calls the sampler exactly as ever."""
+    corruption stage's key; False calls the sampler exactly as ever.  keep_hypotheses=True: (flow, the per-sample maps
+    [B*n_batch,2,G,G]) - the map score's spread needs them."""
     nb = len(batch)
     src, msk, seg, line = (_stack(batch, k, device) for k in ("y512", "mask_cat", "mask_y512", "line_msk"))
     init_flow = _stack(batch, "init_flow", device) if settings.env.use_init_flow else th.zeros(nb, 2, grid, grid, device=device)  # :176-181
     extra = {}
     if keyed_noise_of(settings) if keyed_noise is None else keyed_noise:
         extra["noise_keys"] = [ops.corruption_key(getattr(settings, "seed", 0), d["path"]) for d in batch]
+    if keep_hypotheses:
+        extra["keep_hypotheses"] = True
     return run_sample_lr_dewarping(settings, logger, diffusion, model, 4, src, grid, None, init_flow, None, None, None, msk,
                                    seg, line, th.zeros(nb, 256, grid, grid, device=device), **extra)
 
@@ -394,6 +404,91 @@ def write_flow_outputs(settings, logger, d, flow, h, w, outputs, huffman="fixed"
         np.save(base + ".npy", flow.cpu().numpy())
 
 
+MAP_SCORE_LOGGED = ("epe", "pck1", "pck5", "fl", "ause_epe")                 # the per-document log line, in this order
+MAP_SCORE_COLUMNS = ("epe", "epe_std", "pck1", "pck3", "pck5", "fl", "n_valid", "ause_epe", "ause_pck1", "ause_pck5")   # map_score.txt
+
+
+def gt_map_dir_of(settings):
+    """`settings.gt_map_dir` (run_sampling.py --gt_map_dir): the directory of ground-truth maps, absent or "" -> None (nothing
+    is scored).  Anything but a string, or a directory that does not exist, is a ValueError that names the attribute."""
+    value = getattr(settings, "gt_map_dir", "")
+    if isinstance(value, str) and value == "":
+        return None
+    if not isinstance(value, str) or not os.path.isdir(value):
+        raise ValueError(f"settings.gt_map_dir must be an existing directory (or \"\" for none), got {value!r}")
+    return value
+
+
+def gt_map_candidates(path):
+    """File names under settings.gt_map_dir that may hold the ground-truth map of document `path`, in the order they are tried:
+    per stem of `gt_candidates` <stem>.flo, flow_<stem>.flo, <stem>.npy, flow_<stem>.npy."""
+    names = []
+    for png in gt_candidates(path):
+        stem = os.path.splitext(png)[0]
+        names += [stem + ".flo", f"flow_{stem}.flo", stem + ".npy", f"flow_{stem}.npy"]
+    return names
+
+
+def find_gt_map(gt_map_dir, path):
+    """The ground-truth map file of document `path` under gt_map_dir, or None."""
+    for name in gt_map_candidates(path):
+        full = os.path.join(gt_map_dir, name)
+        if os.path.isfile(full):
+            return full
+    return None
+
+
+def score_against_gt_maps(settings, logger, batch, flow, hyps, outs, gt_map_dir):
+    """settings.gt_map_dir, after a batch is sampled and unwarped: every document with a ground-truth map is
+    scored by ops.map_score - a .flo file is a displacement field in pixels at its own h x w, a .npy file a coarse map [2,g,g]
+    evaluated at the page's size - with one log line and an entry (path, dict) of `settings.map_score`.  hyps [B*H,2,G,G] are
+    the sampler's per-sample maps; with H = 1 the sparsification part is skipped with one log line."""
+    n_hyp = int(hyps.shape[0]) // len(batch)
+    for j, (d, out) in enumerate(zip(batch, outs)):
+        path = d["path"]
+        gt_file = find_gt_map(gt_map_dir, path)
+        if gt_file is None:
+            logger.info(f"{path} map_score skipped: no ground-truth map in {gt_map_dir}")
+            continue
+        if gt_file.endswith(".flo"):
+            gt, size = th.from_numpy(ops.flow_read_flo(gt_file)).to(flow.device), None
+        else:
+            coarse = np.load(gt_file)
+            if coarse.ndim != 3 or coarse.shape[0] != 2 or coarse.shape[1] != coarse.shape[2]:
+                raise ValueError(f"{gt_file}: a ground-truth .npy must hold a coarse map [2,g,g], got {coarse.shape}")
+            gt, size = th.from_numpy(np.ascontiguousarray(coarse, np.float32)).to(flow.device), (int(out.shape[0]), int(out.shape[1]))
+        mine = hyps[j * n_hyp:(j + 1) * n_hyp].float().contiguous() if n_hyp >= 2 else None
+        if mine is None:
+            logger.info(f"{path} map_score: one hypothesis, no spread: sparsification skipped")
+        score = ops.map_score(flow[j].detach().float().contiguous(), gt, mine, size=size)
+        logger.info(f"{path} map_score " + " ".join(f"{k} {score[k]:.6f}" if k in score else f"{k} -" for k in MAP_SCORE_LOGGED))
+        settings.map_score.append((path, score))
+
+
+def map_score_means(scores, keys=MAP_SCORE_COLUMNS):
+    """{key: mean over the documents that have a finite value for it} of settings.map_score."""
+    means = {}
+    for k in keys:
+        values = [float(s[k]) for _, s in scores if k in s and np.isfinite(s[k])]
+        if values:
+            means[k] = sum(values) / len(values)
+    return means
+
+
+def summarize_map_score(settings, logger, documents):
+    """The end of a round under settings.gt_map_dir: map_score.txt beside the round's other score files, and the means."""
+    scores = settings.map_score
+    with open(f"vis_hp/{settings.env.eval_dataset_name}/{settings.name}/map_score.txt", "w") as f:
+        f.write("path " + " ".join(MAP_SCORE_COLUMNS) + "\n")
+        for path, s in scores:
+            f.write(f"{path} " + " ".join((f"{s[k]}" if k == "n_valid" else f"{s[k]:.6f}") if k in s else "-" for k in MAP_SCORE_COLUMNS) + "\n")
+    if scores:
+        for k, mean in map_score_means(scores, MAP_SCORE_LOGGED).items():
+            logger.info(f"mean {k} {mean:.6f} over {sum(1 for _, s in scores if k in s and np.isfinite(s[k]))} of {documents} documents")
+    else:
+        logger.info(f"mean map_score: no document of {documents} has a ground-truth map in {settings.gt_map_dir}")
+
+
 def emit(settings, logger, batch, outs, results, opts, device, *, flow=None, flow_outputs=()):
     """The pages of one batch into `results`; the picture if env.visualize, the scores if env.gt_dir; the maps `flow` [B,2,G,G]
     as the files `flow_outputs` names (settings.flow_outputs)."""
@@ -447,13 +542,16 @@ def run_evaluation_docunet(settings, logger, val_loader, diffusion, model, pretr
     picture and the scores.  The engine-side switches (dvd_amd/run_options.py) are read and checked once, before the loader is
     touched and before anything is written; so are settings.severity / corruption_number, settings.keyed_noise
     (4.11: the sampler's noise keyed per document, reference maps kept and later rounds scored with map_dev) and
-    settings.flow_outputs (4.12: every document's predicted map written under pred_flow/).  The pre-stage models
+    settings.flow_outputs (4.12: every document's predicted map written under pred_flow/) and settings.gt_map_dir (4.13: every
+    document that has a ground-truth map there is scored: EPE, PCK, Fl, AUSE).  The pre-stage models
     may all be None when every document carries ready
     conditioning tensors.  Returns [(path, uint8 [H,W,3] device tensor)] (the reference returns None)."""
     opts = RunOptions.from_env(settings.env)
     corruption = corruption_of(settings)
     keyed = {"keyed_noise": True} if keyed_noise_of(settings) else {}    # absent or False: sample_batch is called as it always was
     outputs = flow_outputs_of(settings)         # absent or "": emit is called as it always was
+    gt_map_dir = gt_map_dir_of(settings)        # absent or "": sample_batch returns what it always did, nothing more is launched
+    hypotheses = {"keep_hypotheses": True} if gt_map_dir else {}
     stage = {}                                  # nothing corrupted: prepare_conditioning is called exactly as it always was
     if corruption is not None:
         logger.info(f"corruption {corruption[0]} ({ops.CORRUPTIONS[corruption[0]]}) severity {corruption[1]}")
@@ -468,21 +566,29 @@ def run_evaluation_docunet(settings, logger, val_loader, diffusion, model, pretr
         settings.map_dev = []                   # a round's scores are its own; the reference maps outlive the round
         if not isinstance(getattr(settings, "map_ref", None), dict):
             settings.map_ref = {}
+    if gt_map_dir:
+        settings.map_score = []
     times, results = [], []
     for batch in batches_of(val_loader, opts.batch_docs):
         adopt_reference_items(batch, device)
         prepare_conditioning(batch, device, opts.grid_size, prestage_models, bool(settings.env.use_init_flow),
                              decode_png=opts.png_decoder == "hip", **stage)
         t0 = time.time()
-        flow = sample_batch(settings, logger, diffusion, model, batch, opts.grid_size, device, **keyed)
+        flow = sample_batch(settings, logger, diffusion, model, batch, opts.grid_size, device, **keyed, **hypotheses)
+        if gt_map_dir:
+            flow, hyps = flow
         th.cuda.synchronize()
         times.append((time.time() - t0) / len(batch))
         if keyed:
             score_map_deviation(settings, logger, batch, flow, clean=corruption is None)
         outs = unwarp_tail(batch, flow, opts.unwarp_mode, device)
+        if gt_map_dir:
+            score_against_gt_maps(settings, logger, batch, flow, hyps, outs, gt_map_dir)
         maps = {"flow": flow, "flow_outputs": outputs} if outputs else {}
         emit(settings, logger, batch, outs, results, opts, device, **maps)
     summarize(settings, logger, opts, times, results)
     if keyed and (corruption is not None or settings.map_dev):
         summarize_map_deviation(settings, logger, len(results))
+    if gt_map_dir:
+        summarize_map_score(settings, logger, len(results))
     return results

@@ -109,7 +109,9 @@ class GaussianDiffusion:
         sampling_kwargs['noise_keys'] (an extension; the reference reads nothing of sampling_kwargs): B pairs (k0, k1), one per
         document (ops.corruption_key).  All noise then comes from ops.randn_keyed - x_T is slot 0 unless `noise` is given, the
         noise of step index i slot 1 + i - and nothing is drawn from torch's generator: a document's noise no longer depends on
-        the batch, on the order of the documents or on what was sampled before it."""
+        the batch, on the order of the documents or on what was sampled before it.
+        sampling_kwargs['keep_hypotheses'] = True (an extension as well): final["hypotheses"] holds the clamped per-sample maps
+        [B*n_batch,2,G,G] that the mean was taken over.  Without the entry `final` has the keys it always had."""
         if not time_variant:
             raise NotImplementedError("time_variant=False is a different network (three streams, d = 1152): only "
                                       "time_variant=True is mirrored")
@@ -138,10 +140,16 @@ class GaussianDiffusion:
             noise_fn = lambda i: ops.randn_keyed(keys, n_batch, G, 1 + i)      # noqa: E731
         elif sampler_kind == "ddpm" or eta != 0.0:
             noise_fn = lambda i: th.randn((B * n_batch, 2, G, G), device=dev)  # noqa: E731
+        keep = {"keep_hypotheses": True} if (sampling_kwargs or {}).get("keep_hypotheses") is True else {}
         sample = sampler.sample(eng, self.tables, x_T, sampler=sampler_kind, eta=eta, noise_fn=noise_fn,
                                 clip_denoised=bool(clip_denoised), denoised_fn=denoised_fn, iterate=iterate,
-                                **self._first_step_kwargs(kw, n_batch, every_step=not iterate))
+                                **self._first_step_kwargs(kw, n_batch, every_step=not iterate), **keep)
+        hypotheses = None
+        if keep:
+            sample, hypotheses = sample
         final = {"sample": sample, "pred_xstart": sample, "feat_dict": eng.feat_nchw()}
+        if keep:
+            final["hypotheses"] = hypotheses
         return sample, final
 
     def _first_step_kwargs(self, kw, n_batch, every_step=False):

@@ -1409,3 +1409,216 @@ def flow_read_flo(path: str) -> np.ndarray:
     if h < 1 or w < 1 or len(data) != 12 + 8 * h * w:
         raise ValueError(f"{path}: a .flo file of {w} x {h} holds {12 + 8 * max(h, 0) * max(w, 0)} bytes, this one {len(data)}")
     return np.frombuffer(data, "<f4", 2 * h * w, 12).reshape(h, w, 2).astype(np.float32)
+
+
+# ---- the map score: a predicted map against a ground-truth map (dvd_amd/csrc/mapscore.hip; definition: DESIGN.md 4.13,
+# tests/mapscore_model.py)
+MAP_MAX_SIDE, MAP_MAX_HYP, MAP_RANKS = 16384, 64, 50
+MAP_INTERVALS = 50                  # the reference's compute_aucs(intervals=50)
+MAP_INVALID = -1                    # the planes' int32 value at a pixel that enters nothing (the bit pattern 0xffffffff)
+MAP_CURVES = ("EPE", "PCK1", "PCK5")
+MAP_NO_PIXELS = {"EPE": 0.0, "PCK1": 1.0, "PCK5": 1.0}
+MAP_FIX_SCALE = 1048576.0           # the fixed point of the curves' sums: rint(min(e, 2^15) 2^20)
+
+
+def _map_device(t, shape_text, name, what):
+    if not torch.is_tensor(t) or not t.is_cuda:
+        raise ValueError(f"{name}: {what} must be a {shape_text} float32 tensor on the device, got "
+                         f"{t.device if torch.is_tensor(t) else type(t)}")
+    if t.dtype != torch.float32 or not t.is_contiguous():
+        raise ValueError(f"{name}: {what} must be contiguous float32, got {t.dtype} contiguous={t.is_contiguous()}")
+
+
+def _map_args(flow, gt, hyps, size, name):
+    """(g, gt_g, n_hyp, h, w) of a scoring call, every shape checked: no launch follows a bad one."""
+    _map_device(flow, "[2,G,G] or [h,w,2]", name, "flow")
+    field = flow.dim() == 3 and flow.shape[2] == 2 and tuple(flow.shape) != (2, 2, 2)       # [2,2,2] is the coarse map G = 2
+    if not field and (flow.dim() != 3 or flow.shape[0] != 2 or flow.shape[1] != flow.shape[2]
+                      or not NOISE_MIN_GRID <= flow.shape[1] <= NOISE_MAX_GRID):
+        raise ValueError(f"{name}: flow must be a coarse map [2,G,G] with G {NOISE_MIN_GRID}..{NOISE_MAX_GRID} or a field [h,w,2], "
+                         f"got {tuple(flow.shape)}")
+    g = 0 if field else int(flow.shape[1])
+    _map_device(gt, "[h,w,2] or [2,g,g]", name, "gt")
+    if gt.device != flow.device:
+        raise ValueError(f"{name}: flow is on {flow.device}, gt on {gt.device}")
+    if size is None:
+        if gt.dim() != 3 or gt.shape[2] != 2:
+            raise ValueError(f"{name}: gt must be a displacement field [h,w,2] (or, with size=(h, w), a coarse map [2,g,g]), got {tuple(gt.shape)}")
+        h, w, gt_g = int(gt.shape[0]), int(gt.shape[1]), 0
+    else:
+        if not isinstance(size, (tuple, list)) or len(size) != 2 or not all(_is_int(v) for v in size):
+            raise ValueError(f"{name}: size must be (h, w), got {size!r}")
+        h, w = int(size[0]), int(size[1])
+        if gt.dim() != 3 or gt.shape[0] != 2 or gt.shape[1] != gt.shape[2] or not NOISE_MIN_GRID <= gt.shape[1] <= NOISE_MAX_GRID:
+            raise ValueError(f"{name}: with size given gt must be a coarse map [2,g,g], g {NOISE_MIN_GRID}..{NOISE_MAX_GRID}, got {tuple(gt.shape)}")
+        gt_g = int(gt.shape[1])
+    if not 1 <= h <= MAP_MAX_SIDE or not 1 <= w <= MAP_MAX_SIDE:
+        raise ValueError(f"{name}: h and w must be 1..{MAP_MAX_SIDE}, got {h} x {w}")
+    if field and (tuple(flow.shape) != (h, w, 2) or hyps is not None):
+        raise ValueError(f"{name}: a field as flow must be [{h},{w},2] like the ground truth and comes without hyps, got {tuple(flow.shape)}")
+    n_hyp = 1
+    if hyps is not None:
+        _map_device(hyps, "[H,2,G,G]", name, "hyps")
+        if hyps.dim() != 4 or tuple(hyps.shape[1:]) != (2, g, g) or not 1 <= hyps.shape[0] <= MAP_MAX_HYP:
+            raise ValueError(f"{name}: hyps must be [H,2,{g},{g}] with H 1..{MAP_MAX_HYP}, got {tuple(hyps.shape)}")
+        if hyps.device != flow.device:
+            raise ValueError(f"{name}: flow is on {flow.device}, hyps on {hyps.device}")
+        n_hyp = int(hyps.shape[0])
+    return g, gt_g, n_hyp, h, w
+
+
+def _map_workspace(h, w, dev):
+    """(ws, e [h,w], sigma [h,w]): the planes are the last two parts of the workspace."""
+    total = _size_query("dvd_mapscore_workspace_bytes", h, w)
+    plane = (4 * h * w + 255) & ~255
+    ws = torch.empty(total, dtype=torch.uint8, device=dev)
+    e = ws[total - 2 * plane:total - 2 * plane + 4 * h * w].view(torch.float32).view(h, w)
+    sigma = ws[total - plane:total - plane + 4 * h * w].view(torch.float32).view(h, w)
+    return ws, e, sigma
+
+
+def _map_errors(flow, gt, hyps, size, name):
+    g, gt_g, n_hyp, h, w = _map_args(flow, gt, hyps, size, name)
+    ws, e, sigma = _map_workspace(h, w, flow.device)
+    lib.call("dvd_map_errors", ptr(flow), g, ptr(gt), gt_g, ptr(hyps) if n_hyp >= 2 else None, n_hyp, h, w, ptr(e), ptr(sigma), ptr(ws),
+             stream_ptr())
+    return ws, e, sigma, n_hyp, h, w
+
+
+def map_errors(flow: torch.Tensor, gt: torch.Tensor, hyps: torch.Tensor = None, size=None):
+    """The planes of one document: flow [2,G,G] (the predicted map; or its displacement field [h,w,2]) against gt - a displacement field [h,w,2] in pixels, the
+    layout of a .flo file, or with size=(h, w) a coarse map [2,g,g] - both evaluated at h x w with flow_full_uv's arithmetic.
+    Returns (e, sigma), [h,w] f32 each: the end-point error and the spread sqrt(mean_h |d_h - mean|^2) of the hypotheses hyps
+    [H,2,G,G] (0 without them or with H = 1).  A pixel whose ground truth is not finite or exceeds 1e9 in a component (or whose
+    prediction is not finite) holds the bit pattern 0xffffffff in both planes and enters nothing.  One launch."""
+    _, e, sigma, _, _, _ = _map_errors(flow, gt, hyps, size, "map_errors")
+    return e, sigma
+
+
+def _map_metrics(ws, h, w):
+    out = torch.empty(7, dtype=torch.int64, device=ws.device)
+    lib.call("dvd_map_metrics", ptr(ws), h, w, ptr(out), stream_ptr())
+    words = out.cpu().numpy()
+    n, n1, n3, n5, nfl = (int(v) for v in words[:5])
+    se, se2 = (float(v) for v in words[5:].view(np.float64))
+    nan = float("nan")
+    if n == 0:
+        return {"epe": nan, "epe_std": nan, "pck1": nan, "pck3": nan, "pck5": nan, "fl": nan, "n_valid": 0, "sum_e": 0.0, "sum_e2": 0.0}
+    var = max(se2 - se * se / n, 0.0) / (n - 1) if n > 1 else nan
+    return {"epe": se / n, "epe_std": float(np.sqrt(var)), "pck1": n1 / n, "pck3": n3 / n, "pck5": n5 / n, "fl": nfl / n,
+            "n_valid": n, "sum_e": se, "sum_e2": se2}
+
+
+def map_metrics(flow: torch.Tensor, gt: torch.Tensor, hyps: torch.Tensor = None, size=None) -> dict:
+    """The headline numbers of one document (arguments as map_errors), the reference's definitions over the valid pixels: epe
+    (mean of e), epe_std (unbiased, torch.std), pck1 / pck3 / pck5 (share with e <= 1, 3, 5 px), fl (share with e > 3 and
+    e / |gt| > 0.05), n_valid, and the f64 sums sum_e, sum_e2 they come from (added in a fixed order; counts are exact).
+    Two launches, one read-back of seven words."""
+    ws, _, _, _, h, w = _map_errors(flow, gt, hyps, size, "map_metrics")
+    return _map_metrics(ws, h, w)
+
+
+def _map_plane(t, name, what):
+    _map_device(t, "[n]", name, what)
+    n = int(t.numel())
+    if not 1 <= n <= MAP_MAX_SIDE * MAP_MAX_SIDE:
+        raise ValueError(f"{name}: {what} must hold 1..{MAP_MAX_SIDE * MAP_MAX_SIDE} values, got {n}")
+    return n
+
+
+def _map_head(dev):
+    """The part of the workspace that the selection and the bins use: one size for every plane."""
+    return torch.empty(_size_query("dvd_mapscore_workspace_bytes", 1, 1), dtype=torch.uint8, device=dev)
+
+
+def _map_bins(e, key, thr, ws):
+    k = int(thr.numel())
+    out = torch.empty((k + 1, 4), dtype=torch.int64, device=e.device)
+    lib.call("dvd_sparsify_bins", ptr(e), ptr(key), int(e.numel()), ptr(thr), k, ptr(out), ptr(ws), stream_ptr())
+    return out
+
+
+def map_valid_count(e: torch.Tensor, ws=None) -> int:
+    """How many pixels of a plane of map_errors are valid: the bins kernel with one threshold above every valid key."""
+    _map_plane(e, "map_valid_count", "e")
+    thr = torch.full((1,), 0x7fffffff, dtype=torch.int32, device=e.device)        # above every non-negative float, below invalid
+    return int(_map_bins(e, e, thr, _map_head(e.device) if ws is None else ws)[1, 0])
+
+
+def select_kth_desc(keys: torch.Tensor, ranks, n_valid: int = None, ws=None) -> torch.Tensor:
+    """keys: a plane of non-negative finite f32 on the device (invalid pixels: the pattern 0xffffffff) -> the f32 tensor
+    keys_sorted_descending[ranks] over its valid values.  ranks: 1..50 integers in 0..n_valid-1, in any order, repeats allowed.
+    Exact: an MSD radix selection on the bit patterns, all ranks at once, eight launches and no read-back."""
+    n = _map_plane(keys, "select_kth_desc", "keys")
+    ranks = list(ranks) if isinstance(ranks, (list, tuple, np.ndarray)) else None
+    if not ranks or len(ranks) > MAP_RANKS or not all(_is_int(r) for r in ranks):
+        raise ValueError(f"select_kth_desc: ranks must be 1..{MAP_RANKS} integers, got {ranks!r}")
+    ws = _map_head(keys.device) if ws is None else ws
+    if n_valid is None:
+        n_valid = map_valid_count(keys, ws)
+    if not _is_int(n_valid) or not 1 <= n_valid <= n or min(ranks) < 0 or max(ranks) >= n_valid:
+        raise ValueError(f"select_kth_desc: ranks must lie in 0..n_valid-1 with n_valid 1..{n}, got n_valid = {n_valid!r}, "
+                         f"ranks {min(ranks)}..{max(ranks)}")
+    asc = sorted({int(n_valid) - 1 - int(r) for r in ranks})
+    out = torch.empty(len(asc), dtype=torch.float32, device=keys.device)
+    host = (C.c_uint32 * len(asc))(*asc)
+    lib.call("dvd_select_u32", ptr(keys), n, host, len(asc), ptr(out), ptr(ws), stream_ptr())
+    if len(asc) == len(ranks) and all(int(n_valid) - 1 - int(r) == a for r, a in zip(reversed(ranks), asc)):
+        return out.flip(0)                                       # distinct ranks in ascending order: the common case
+    return out[torch.tensor([asc.index(int(n_valid) - 1 - int(r)) for r in ranks], device=keys.device)]
+
+
+def map_ranks(n_valid: int, intervals: int = MAP_INTERVALS):
+    """hi = ceil(q (N - 1) / 100) for q = 0, 100 / intervals, ..: the descending rank whose key closes the kept set of q."""
+    return [(q * (n_valid - 1) + 99) // 100 for q in range(0, 100, 100 // intervals)]
+
+
+def _map_curves(bins):
+    """[51,4] integer bins (host) -> {metric: 51 float64 values}: suffix sums give the kept sets; the value for no pixel is
+    appended as the reference appends it."""
+    kept = np.cumsum(bins[::-1].astype(np.uint64), axis=0, dtype=np.uint64)[::-1][1:]
+    cnt = kept[:, 0].astype(np.float64)
+    vals = {"EPE": kept[:, 3].astype(np.float64) / MAP_FIX_SCALE / cnt, "PCK1": kept[:, 1] / cnt, "PCK5": kept[:, 2] / cnt}
+    return {m: np.append(vals[m], MAP_NO_PIXELS[m]) for m in MAP_CURVES}
+
+
+def sparsification(e: torch.Tensor, sigma: torch.Tensor, n_valid: int = None) -> dict:
+    """The reference's compute_aucs(intervals=50) from the planes of map_errors: for q = 0, 2, .., 98 the kept set is
+    {p : key(p) <= key_desc[ceil(q (N - 1) / 100)]}, all ties kept; key = sigma gives sparse_curve, key = e the oracle's
+    opt_curve, each {EPE, PCK1, PCK5: 51 values} over max(opt) + 1e-6 with 0, 1, 1 appended; AUSE = |trapz(sparse) - trapz(opt)|.
+    The thresholds are selected and the kept sets summed on the device in integers (e as rint(min(e, 2^15) 2^20)); the 153
+    numbers are made on the host in float64.  The reference's np.percentile keeps one pixel more where its float32 interpolation
+    rounds down onto the lower order statistic."""
+    n = _map_plane(e, "sparsification", "e")
+    if _map_plane(sigma, "sparsification", "sigma") != n or sigma.device != e.device:
+        raise ValueError(f"sparsification: e holds {n} values on {e.device}, sigma {sigma.numel()} on {sigma.device}")
+    ws = _map_head(e.device)
+    if n_valid is None:
+        n_valid = map_valid_count(e, ws)
+    if not _is_int(n_valid) or not 1 <= n_valid <= n:
+        raise ValueError(f"sparsification: n_valid must be 1..{n} (a plane without a valid pixel has no curve), got {n_valid!r}")
+    ranks = map_ranks(int(n_valid))
+    bins = [_map_bins(e, key, select_kth_desc(key, ranks, n_valid, ws).view(torch.int32), ws) for key in (sigma, e)]
+    sparse, opt = (_map_curves(b.view(np.uint64)) for b in torch.stack(bins).cpu().numpy())
+    k = len(ranks)
+    plotx = np.asarray([1.0 / k * t for t in range(k + 1)], np.float64)
+    out = {"sparse_curve": {}, "opt_curve": {}, "AUSE": {}}
+    for m in MAP_CURVES:
+        top = np.asarray(opt[m]).max() + 1e-6
+        area = [float(((y[1:] + y[:-1]) * 0.5 * np.diff(plotx)).sum()) for y in (sparse[m] / top, opt[m] / top)]
+        out["AUSE"][m] = abs(area[0] - area[1])
+        out["sparse_curve"][m], out["opt_curve"][m] = sparse[m] / top, opt[m] / top
+    return out
+
+
+def map_score(flow: torch.Tensor, gt: torch.Tensor, hyps: torch.Tensor = None, size=None) -> dict:
+    """Everything of one document (arguments as map_errors): map_metrics' numbers and, with H >= 2 hypotheses and a valid pixel,
+    sparsification's sparse_curve, opt_curve and AUSE plus ause_epe, ause_pck1, ause_pck5.  A map scored against the .flo file
+    written from it gives epe == 0.0 exactly."""
+    ws, e, sigma, n_hyp, h, w = _map_errors(flow, gt, hyps, size, "map_score")
+    out = _map_metrics(ws, h, w)
+    if n_hyp >= 2 and out["n_valid"] > 0:
+        sp = sparsification(e, sigma, out["n_valid"])
+        out.update(sp)
+        out.update({f"ause_{m.lower()}": sp["AUSE"][m] for m in MAP_CURVES})
+    return out

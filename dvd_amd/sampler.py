@@ -19,7 +19,8 @@ def feat_mode_for(t_model: float, n: int, first_step: bool) -> int:
 
 def sample(engine: Engine, tables: schedule.Tables, x_T: torch.Tensor, sampler: str = "ddim", eta: float = 0.0,
            noise_fn=None, mean_hyp: bool = True, trace=None, last_step: int = 0, init_flow=None, init_feat=None,
-           t_override: bool = True, clip_denoised: bool = False, denoised_fn=None, iterate: bool = True):
+           t_override: bool = True, clip_denoised: bool = False, denoised_fn=None, iterate: bool = True, *,
+           keep_hypotheses: bool = False):
     """x_T [docs*H, 2, G, G] on the engine's device (sample index = doc*H + h).  The engine must have been
     prepared for its documents.  noise_fn(step) -> [N,2,G,G] supplies the per-step noise (DDPM, or DDIM with
     eta > 0).  Returns [docs,2,G,G] (hypothesis mean + clamp, :639-640) or the clamped per-sample maps.
@@ -33,7 +34,9 @@ def sample(engine: Engine, tables: schedule.Tables, x_T: torch.Tensor, sampler: 
     engine's x0 buffer), the clamp to [-1, 1] second, fused into the scheduler launch and done in place - so the
     step arithmetic, `trace`, the next step's init_flow and its warp grid all see the processed value.
     iterate=False is the loop's `iter != True` branch (:579-594): every step gets the caller's init_flow and init_feat,
-    nothing is fed back, and the model never swaps in the pyramid features (idf/cross_model.py:596-603 need iter)."""
+    nothing is fed back, and the model never swaps in the pyramid features (idf/cross_model.py:596-603 need iter).
+    keep_hypotheses (with mean_hyp): returns (the mean map, the clamped per-sample maps [docs*H,2,G,G]) - what the map score's
+    spread is made of."""
     n = engine.n
     S = tables.num_timesteps
     # The loop's I/O lives in buffers owned by the engine object and reused by every roll-out: x_t and x0 ping-pong
@@ -93,6 +96,8 @@ def sample(engine: Engine, tables: schedule.Tables, x_T: torch.Tensor, sampler: 
         img = ops.sched_step(coef, img, x0, noise, out=img_bufs[(k + 1) & 1], clip=clip_denoised)
         if trace is not None:                                      # after the launch that clamps: the processed x0
             trace.append(x0.clone())
+    if mean_hyp and keep_hypotheses:
+        return ops.hyp_mean_clamp(x0, engine.n_hyp), torch.clamp(x0, -1, 1)
     if mean_hyp:
         return ops.hyp_mean_clamp(x0, engine.n_hyp)
     return torch.clamp(x0, -1, 1)

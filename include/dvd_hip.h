@@ -818,6 +818,42 @@ int dvd_flow_full_uv(const float* flow, int n, int g, int h, int w, float* out, 
 int dvd_flow_picture_rgb8(const float* flow, int n, int g, int h, int w, int norm, int bgr, uint8_t* out, float* largest, void* ws,
                           void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * The map score: a predicted map against a ground-truth map (tests/mapscore_model.py is the definition).
+ * One document per call.  The prediction flow [2,g,g] is evaluated at the ground truth's h x w with the arithmetic of
+ * dvd_flow_full_uv.  A pixel is valid when both ground-truth components are finite and at most 1e9 in magnitude (the Middlebury
+ * unknown-flow rule) and the prediction and every hypothesis are finite there; an invalid pixel enters nothing.
+ * Sides 1..16384, g 2..8192, n_hyp 1..64: anything else is DVD_E_MAP_SHAPE; bad ranks are DVD_E_MAP_RANKS; both before any
+ * launch.  No scratch memory, no atomics on floats, integer sums only where the order could matter.
+ * ---------------------------------------------------------------------------------------- */
+#define DVD_E_MAP_SHAPE (-51)
+#define DVD_E_MAP_RANKS (-52)
+/* bytes of `ws` for a document of h x w, 256-byte aligned, or DVD_E_MAP_SHAPE.  Its parts in order: a head of one size for every
+ * h x w (selection state, block histograms, block bins: dvd_select_u32 and dvd_sparsify_bins use nothing else, so
+ * dvd_mapscore_workspace_bytes(1, 1) serves them for any n), the block partials of dvd_map_errors, and room for the two planes:
+ * the last two parts, each 4 h w bytes rounded up to 256. */
+long dvd_mapscore_workspace_bytes(int h, int w);
+/* e [h w] and sigma [h w] f32 <- flow [2,g,g], the ground truth gt (gt_g = 0: a displacement field [h,w,2] in pixels, 8-byte
+ * aligned, the layout of a .flo file; gt_g >= 2: a coarse map [2,gt_g,gt_g]) and hyps [n_hyp,2,g,g] (may be null with n_hyp 1).
+ * g = 0: flow is itself such a field [h,w,2] (then n_hyp must be 1).
+ * e = sqrt(du^2 + dv^2) in separately rounded f32; sigma = sqrt(mean_h |d_h - mean|^2) over the up-sampled hypotheses, 0 with
+ * n_hyp = 1.  An invalid pixel gets the bit pattern 0xffffffff in both planes.  Also writes the block partials of the headline
+ * numbers into ws.  One launch. */
+int dvd_map_errors(const float* flow, int g, const float* gt, int gt_g, const float* hyps, int n_hyp, int h, int w, float* e,
+                   float* sigma, void* ws, void* stream);
+/* Adds the block partials a dvd_map_errors call of the same h x w left in ws: out (device, seven 8-byte words) = u64 n_valid,
+ * #(e <= 1), #(e <= 3), #(e <= 5), #(e > 3 and e / |gt| > 0.05), then the f64 sums of e and of e^2, added in a fixed order. */
+int dvd_map_metrics(const void* ws, int h, int w, void* out, void* stream);
+/* out [k] (device) = the order statistics keys_sorted_ascending[ranks[i]] of n u32 keys on the device.  ranks: k = 1..50 values
+ * on the HOST, non-decreasing, each below n.  MSD radix selection in four 8-bit levels, eight launches, no host read-back.
+ * Non-negative finite f32 values select as their bit patterns. */
+int dvd_select_u32(const uint32_t* keys, long n, const uint32_t* ranks, int k, uint32_t* out, void* ws, void* stream);
+/* out [(k + 1) * 4] u64 (device): bin b = 0..k holds, over the pixels p with e[p] valid whose key[p] is <= exactly b of the k
+ * thresholds thr (device, u32 bit patterns in non-increasing order), the count, #(e <= 1), #(e <= 5) and the sum of
+ * rint(min(e, 2^15) 2^20): at most 2^63 over 2^28 pixels.  key and e are planes of dvd_map_errors (key = e or sigma). */
+int dvd_sparsify_bins(const float* e, const float* key, long n, const uint32_t* thr, int k, unsigned long long* out, void* ws,
+                      void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -14,7 +14,11 @@ clean round first, under <name>, and the table gains the column map_dev: the mea
 between the map predicted from the corrupted input and the one predicted from the clean input - a number that needs no scan.
 
 --flow_outputs png,flo,npy writes the predicted map of every document under <name>/pred_flow (settings.flow_outputs; DESIGN.md
-4.12): its colour-wheel picture, its full-resolution .flo field and / or the coarse map itself.  Every round writes its own."""
+4.12): its colour-wheel picture, its full-resolution .flo field and / or the coarse map itself.  Every round writes its own.
+
+--gt_map_dir DIR scores every document's predicted map against the ground-truth map DIR holds for it (settings.gt_map_dir;
+DESIGN.md 4.13: <stem>.flo, flow_<stem>.flo, <stem>.npy or flow_<stem>.npy - the files --flow_outputs flo,npy writes): EPE, PCK,
+Fl and the sparsification error AUSE, in map_score.txt; under --corruption the table gains the columns epe, pck5, ause_epe."""
 import argparse
 import importlib
 import os
@@ -59,10 +63,12 @@ def write_corruption_table(path, rows, metrics):
 
 
 MAP_DEV = "map_dev"        # the table's column under --keyed_noise, after the env.gt_dir metrics
+MAP_SCORE = "map_score"    # settings.map_score under --gt_map_dir: [(path, dict)]
+MAP_SCORE_COLUMNS = ("epe", "pck5", "ause_epe")   # ... and the table's columns from it, after every other one
 
 
 def run_sampling(train_module, train_name, seed, name, cudnn_benchmark=True, corruption=False, severity=None,
-                 corruption_number=None, *, keyed_noise=False, flow_outputs=""):
+                 corruption_number=None, *, keyed_noise=False, flow_outputs="", gt_map_dir=""):
     from dvd_amd import ops
     print(f"Sampling:  {train_module}  {train_name}\nDate: {date.today().strftime('%d/%m/%Y')}")
     settings = ws_settings.Settings()
@@ -73,6 +79,8 @@ def run_sampling(train_module, train_name, seed, name, cudnn_benchmark=True, cor
         settings.keyed_noise = True
     if flow_outputs:                                          # likewise: "" leaves the attribute absent
         settings.flow_outputs = flow_outputs
+    if gt_map_dir:                                            # likewise
+        settings.gt_map_dir = gt_map_dir
     save_dir = os.path.join(settings.env.workspace_dir, settings.project_path)
     os.makedirs(save_dir, exist_ok=True)
     shutil.copyfile(settings.project_path + ".py", os.path.join(save_dir, settings.script_name + ".py"))
@@ -96,16 +104,20 @@ def run_sampling(train_module, train_name, seed, name, cudnn_benchmark=True, cor
             print(f"corruption {number} ({kind}): no device kernel, round skipped")
             continue
         settings.severity, settings.corruption_number, settings.name = sev, number, round_name(name, sev, number)
-        for metric in ops.GT_METRIC_NAMES + (MAP_DEV,):         # a round's scores are its own
+        for metric in ops.GT_METRIC_NAMES + (MAP_DEV, MAP_SCORE):   # a round's scores are its own
             if hasattr(settings, metric):
                 delattr(settings, metric)
         run(settings)
         means = {m: sum(v for _, v in getattr(settings, m)) / len(getattr(settings, m))
                  for m in ops.GT_METRIC_NAMES + ((MAP_DEV,) if keyed_noise else ()) if getattr(settings, m, None)}
+        if gt_map_dir:
+            from dvd_amd.evaluation import map_score_means
+            means.update(map_score_means(getattr(settings, MAP_SCORE, None) or [], MAP_SCORE_COLUMNS))
         rows.append((number, kind, sev, means))
     settings.name = name
     if rows:
-        metrics = [m for m in ops.GT_METRIC_NAMES if any(m in r[3] for r in rows)] + ([MAP_DEV] if keyed_noise else [])
+        metrics = [m for m in ops.GT_METRIC_NAMES if any(m in r[3] for r in rows)] + ([MAP_DEV] if keyed_noise else []) + \
+            (list(MAP_SCORE_COLUMNS) if gt_map_dir else [])
         write_corruption_table(os.path.join("vis_hp", str(settings.env.eval_dataset_name), name, "corruption_table.txt"), rows, metrics)
 
 
@@ -123,6 +135,8 @@ def main():
                    "round first, then the column map_dev in the table")
     p.add_argument("--flow_outputs", type=str, default="", help="comma-separated list of png, flo, npy: what to write of every "
                    "document's predicted map under pred_flow/ (nothing by default)")
+    p.add_argument("--gt_map_dir", type=str, default="", help="directory of ground-truth maps (<stem>.flo, flow_<stem>.flo, <stem>.npy, "
+                   "flow_<stem>.npy): score every document's predicted map against its own (EPE, PCK, Fl, AUSE)")
     a = p.parse_args()
     a.seed = torch.initial_seed() & (2 ** 32 - 1)      # as the reference: the CLI value is overwritten (:77-78)
     print(f"Seed is {a.seed}")
@@ -130,7 +144,7 @@ def main():
     np.random.seed(a.seed)
     run_sampling(a.train_module, a.train_name, seed=a.seed, name=a.name, cudnn_benchmark=a.cudnn_benchmark,
                  corruption=a.corruption, severity=a.severity, corruption_number=a.corruption_number, keyed_noise=a.keyed_noise,
-                 flow_outputs=a.flow_outputs)
+                 flow_outputs=a.flow_outputs, gt_map_dir=a.gt_map_dir)
 
 
 if __name__ == "__main__":
