@@ -3,7 +3,13 @@
     python -m dvd_amd.apply_map MAP.npy IMAGE OUT.png [--mode bicubic]
 
 The image is decoded by PIL, unwarped on the device by ops.unwarp_u8 - the kernel that made the run's page - and written as
-a PNG by PIL."""
+a PNG by PIL.
+
+    python -m dvd_amd.apply_map MAP.npy IMAGE OUT.txt --points PTS.txt --to page|photo [--step 8]
+
+carries the N x 2 coordinates (x y per line, in pixels) of PTS.txt through the map instead: --to page takes positions on the
+photograph IMAGE to the dewarped page (ops.map_invert, ops.transfer_points; "nan nan" where the page does not reach), --to photo
+takes positions on the page to the photograph (ops.map_points).  IMAGE is opened for its size only."""
 import argparse
 
 import numpy as np
@@ -34,13 +40,65 @@ def apply_map(map_path, image_path, out_path, mode="bilinear"):
     return page
 
 
+POINT_TARGETS = ("page", "photo")
+
+
+def load_points(path):
+    """The N x 2 coordinates of a text file (x y per line) as float32 [N,2]; anything else is a ValueError naming the file."""
+    try:
+        pts = np.loadtxt(path, dtype=np.float64, ndmin=2)
+    except ValueError as e:
+        raise ValueError(f"{path}: expected lines of two numbers: {e}") from None
+    if pts.ndim != 2 or pts.shape[1] != 2:
+        raise ValueError(f"{path}: expected N x 2 coordinates, got {pts.shape}")
+    return np.ascontiguousarray(pts, dtype=np.float32)
+
+
+def carry_points(flow, pts, h, w, to, step):
+    """flow [1,2,G,G], pts [N,2] float32 on the host -> the carried points [N,2] float32 on the host, NaN where there is none."""
+    import torch
+    from . import ops
+    dev_flow, dev_pts = torch.from_numpy(flow[0]).cuda(), torch.from_numpy(pts).cuda()
+    if to == "page":
+        fwd, _ = ops.map_invert(dev_flow, h, w, step=step)
+        got = ops.transfer_points(fwd, dev_pts)
+    else:
+        got = ops.map_points(dev_flow, dev_pts, h, w)
+    got = got.cpu().numpy()
+    got[got.view(np.int32) == ops.MAP_INVALID] = np.nan
+    return got
+
+
+def apply_points(map_path, image_path, out_path, points_path, to="page", step=8):
+    """Carry the points of `points_path` through the map at the size of `image_path`; writes and returns the N x 2 result
+    (NaN where there is none)."""
+    if to not in POINT_TARGETS:
+        raise ValueError(f"--to must be one of {POINT_TARGETS}, got {to!r}")
+    if isinstance(step, bool) or not isinstance(step, int) or step < 1:
+        raise ValueError(f"--step must be a positive integer, got {step!r}")
+    flow, pts = load_map(map_path), load_points(points_path)
+    from PIL import Image
+    with Image.open(image_path) as im:
+        w, h = im.size
+    got = carry_points(flow, pts, h, w, to, step)
+    np.savetxt(out_path, got, fmt="%.4f")
+    return got
+
+
 def main(argv=None):
     p = argparse.ArgumentParser(prog="python -m dvd_amd.apply_map", description="Unwarp an image with a saved coarse map.")
     p.add_argument("map", help="flow_<stem>.npy: the coarse map [2,G,G]")
     p.add_argument("image", help="the image to unwarp (any format PIL reads)")
     p.add_argument("out", help="the PNG to write")
     p.add_argument("--mode", default="bilinear", choices=WARP_MODES)
+    p.add_argument("--points", default=None, metavar="FILE", help="carry the N x 2 coordinates of FILE through the map; OUT is then "
+                   "a text file and IMAGE gives the size only")
+    p.add_argument("--to", default="page", choices=POINT_TARGETS, help="with --points: photograph -> page (default) or page -> photo")
+    p.add_argument("--step", type=int, default=8, help="with --points --to page: the mesh step of the inverse")
     a = p.parse_args(argv)
+    if a.points is not None:
+        apply_points(a.map, a.image, a.out, a.points, a.to, a.step)
+        return
     apply_map(a.map, a.image, a.out, a.mode)
 
 

@@ -489,6 +489,79 @@ def summarize_map_score(settings, logger, documents):
         logger.info(f"mean map_score: no document of {documents} has a ground-truth map in {settings.gt_map_dir}")
 
 
+INVERSE_OUTPUTS = ("mesh", "flo", "mask")     # what settings.inverse_outputs may name
+MAP_INVERSE_LOGGED = ("covered", "fold_px", "flipped", "skipped", "cycle_mean", "cycle_max")     # the per-document log line
+MAP_INVERSE_COLUMNS = ("covered", "fold_px", "flipped", "degenerate", "skipped", "tris", "cycle_mean", "cycle_max", "fold", "cycle")
+_INVERSE_INTEGERS = ("covered", "fold_px", "flipped", "degenerate", "skipped", "tris")
+
+
+def inverse_outputs_of(settings):
+    """`settings.inverse_outputs` (run_sampling.py --inverse_outputs): a comma-separated list of INVERSE_OUTPUTS names without
+    repeats -> the names, in the order of INVERSE_OUTPUTS.  Absent or "" means none: nothing is inverted.  Anything else is a
+    ValueError that names the attribute."""
+    value = getattr(settings, "inverse_outputs", "")
+    if isinstance(value, str) and value == "":
+        return ()
+    names = [n.strip() for n in value.split(",")] if isinstance(value, str) else None
+    if not names or any(n not in INVERSE_OUTPUTS for n in names) or len(set(names)) != len(names):
+        raise ValueError(f"settings.inverse_outputs must be a comma-separated list of {INVERSE_OUTPUTS} without repeats, got {value!r}")
+    return tuple(n for n in INVERSE_OUTPUTS if n in names)
+
+
+def _photograph_u8(d, device):
+    """The document's photograph as uint8 [H,W,3] on the device: its byte image, or its float image truncated."""
+    if "src_u8" in d:
+        return _on_device(d["src_u8"], device).contiguous()
+    return d["source_vis"].to(device).float().clamp(0, 255).to(th.uint8).permute(1, 2, 0).contiguous()
+
+
+def write_inverse_outputs(settings, logger, batch, flow, outs, outputs, device, huffman="fixed"):
+    """settings.inverse_outputs, after a batch is unwarped: every document's predicted map is inverted at its
+    photograph's size (ops.map_invert, ops.map_cycle_error), with one log line and an entry (path, dict) of
+    `settings.map_inverse`; under pred_flow/ 'mesh' writes mesh_<stem>.png, the page mesh on the photograph, 'flo'
+    inv_<stem>.flo, the forward displacement (1e10 where the page does not reach), 'mask' mask_<stem>.png, 255 where it does."""
+    from utils_flow.visualization_utils import _stem
+    out_dir = f"vis_hp/{settings.env.eval_dataset_name}/{settings.name}/pred_flow"
+    os.makedirs(out_dir, exist_ok=True)
+    for j, (d, out) in enumerate(zip(batch, outs)):
+        path = d["path"]
+        name = path if os.path.splitext(path)[1] else path + ".png"
+        stem = _stem([name])
+        h, w = int(out.shape[0]), int(out.shape[1])
+        mine = flow[j].detach().float().contiguous()
+        fwd, stats = ops.map_invert(mine, h, w)
+        cycle = ops.map_cycle_error(mine, fwd)
+        score = {"covered": stats["covered"], "fold_px": stats["fold_px"], "flipped": stats["flipped_tris"],
+                 "degenerate": stats["degenerate_tris"], "skipped": stats["skipped_tris"], "tris": stats["tris"],
+                 "cycle_mean": cycle["cycle_mean"], "cycle_max": cycle["cycle_max"],
+                 "fold": stats["fold_px"] / stats["covered"] if stats["covered"] else float("nan"), "cycle": cycle["cycle_mean"]}
+        logger.info(f"{path} map_inverse " + " ".join(f"{k} {score[k]}" if k in _INVERSE_INTEGERS else f"{k} {score[k]:.6f}"
+                                                      for k in MAP_INVERSE_LOGGED))
+        settings.map_inverse.append((path, score))
+        if "mesh" in outputs:
+            ops.mesh_overlay_to_file(_photograph_u8(d, device), fwd, f"{out_dir}/mesh_{stem}.png", huffman=huffman)
+        if "flo" in outputs:
+            ops.inverse_write_flo(fwd, f"{out_dir}/inv_{stem}.flo")
+        if "mask" in outputs:
+            ops.png_encode_to_file(ops.coverage_mask(fwd), f"{out_dir}/mask_{stem}.png", huffman)
+
+
+def map_inverse_means(scores, keys=MAP_INVERSE_COLUMNS):
+    """{key: mean over the documents that have a finite value for it} of settings.map_inverse."""
+    return map_score_means(scores, keys)
+
+
+def summarize_map_inverse(settings, logger, documents):
+    """The end of a round under settings.inverse_outputs: map_inverse.txt beside the round's other score files, and the means."""
+    scores = settings.map_inverse
+    with open(f"vis_hp/{settings.env.eval_dataset_name}/{settings.name}/map_inverse.txt", "w") as f:
+        f.write("path " + " ".join(MAP_INVERSE_COLUMNS) + "\n")
+        for path, s in scores:
+            f.write(f"{path} " + " ".join(f"{s[k]}" if k in _INVERSE_INTEGERS else f"{s[k]:.6f}" for k in MAP_INVERSE_COLUMNS) + "\n")
+    for k, mean in map_inverse_means(scores, ("fold", "cycle_mean", "cycle_max")).items():
+        logger.info(f"mean map_inverse {k} {mean:.6f} over {sum(1 for _, s in scores if np.isfinite(s[k]))} of {documents} documents")
+
+
 def emit(settings, logger, batch, outs, results, opts, device, *, flow=None, flow_outputs=()):
     """The pages of one batch into `results`; the picture if env.visualize, the scores if env.gt_dir; the maps `flow` [B,2,G,G]
     as the files `flow_outputs` names (settings.flow_outputs)."""
@@ -543,7 +616,8 @@ def run_evaluation_docunet(settings, logger, val_loader, diffusion, model, pretr
     touched and before anything is written; so are settings.severity / corruption_number, settings.keyed_noise
     (4.11: the sampler's noise keyed per document, reference maps kept and later rounds scored with map_dev) and
     settings.flow_outputs (4.12: every document's predicted map written under pred_flow/) and settings.gt_map_dir (4.13: every
-    document that has a ground-truth map there is scored: EPE, PCK, Fl, AUSE).  The pre-stage models
+    document that has a ground-truth map there is scored: EPE, PCK, Fl, AUSE) and settings.inverse_outputs (4.14: every document's
+    map inverted on the device: mesh picture, forward field, coverage mask, fold count, cycle error).  The pre-stage models
     may all be None when every document carries ready
     conditioning tensors.  Returns [(path, uint8 [H,W,3] device tensor)] (the reference returns None)."""
     opts = RunOptions.from_env(settings.env)
@@ -552,6 +626,7 @@ def run_evaluation_docunet(settings, logger, val_loader, diffusion, model, pretr
     outputs = flow_outputs_of(settings)         # absent or "": emit is called as it always was
     gt_map_dir = gt_map_dir_of(settings)        # absent or "": sample_batch returns what it always did, nothing more is launched
     hypotheses = {"keep_hypotheses": True} if gt_map_dir else {}
+    inverse = inverse_outputs_of(settings)      # absent or "": no map is inverted, no file, the same log
     stage = {}                                  # nothing corrupted: prepare_conditioning is called exactly as it always was
     if corruption is not None:
         logger.info(f"corruption {corruption[0]} ({ops.CORRUPTIONS[corruption[0]]}) severity {corruption[1]}")
@@ -568,6 +643,8 @@ def run_evaluation_docunet(settings, logger, val_loader, diffusion, model, pretr
             settings.map_ref = {}
     if gt_map_dir:
         settings.map_score = []
+    if inverse:
+        settings.map_inverse = []
     times, results = [], []
     for batch in batches_of(val_loader, opts.batch_docs):
         adopt_reference_items(batch, device)
@@ -584,6 +661,8 @@ def run_evaluation_docunet(settings, logger, val_loader, diffusion, model, pretr
         outs = unwarp_tail(batch, flow, opts.unwarp_mode, device)
         if gt_map_dir:
             score_against_gt_maps(settings, logger, batch, flow, hyps, outs, gt_map_dir)
+        if inverse:
+            write_inverse_outputs(settings, logger, batch, flow, outs, inverse, device, opts.png_huffman)
         maps = {"flow": flow, "flow_outputs": outputs} if outputs else {}
         emit(settings, logger, batch, outs, results, opts, device, **maps)
     summarize(settings, logger, opts, times, results)
@@ -591,4 +670,6 @@ def run_evaluation_docunet(settings, logger, val_loader, diffusion, model, pretr
         summarize_map_deviation(settings, logger, len(results))
     if gt_map_dir:
         summarize_map_score(settings, logger, len(results))
+    if inverse:
+        summarize_map_inverse(settings, logger, len(results))
     return results

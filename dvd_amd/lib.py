@@ -130,6 +130,7 @@ SFLOW_MIN_TOP = 12    # DVD_SFLOW_MIN_TOP: least side of the top pyramid level
 FLOW_NORM_DIAG, FLOW_NORM_MAX = 0, 1   # DVD_FLOW_NORM_*: rad_max of a flow picture
 E_FLOW_SHAPE = -50                     # DVD_E_FLOW_SHAPE
 E_MAP_SHAPE, E_MAP_RANKS = -51, -52    # DVD_E_MAP_*: what the map score refuses
+E_INV_SHAPE, E_INV_STEP, E_INV_LINES, E_INV_POINTS = -53, -54, -55, -56    # DVD_E_INV_*: what the map inverse refuses
 
 RAGGED_CAP = 64  # DVD_RAGGED_CAP: documents per launch of the ragged entry points (larger batches are cut by the library)
 
@@ -139,7 +140,7 @@ NON_STATUS = {"dvd_last_error", "dvd_version", "dvd_engine_workspace_bytes", "dv
               "dvd_msssim_workspace_bytes", "dvd_png_bound", "dvd_png_scratch_bytes", "dvd_png_scratch_bytes_huff", "dvd_jpeg_bound",
               "dvd_jpeg_scratch_bytes", "dvd_sflow_level_workspace_bytes", "dvd_sflow_workspace_bytes",
               "dvd_adist_workspace_bytes", "dvd_corrupt_supported", "dvd_corrupt_table", "dvd_map_deviation_workspace_bytes",
-              "dvd_flow_workspace_bytes", "dvd_mapscore_workspace_bytes"}
+              "dvd_flow_workspace_bytes", "dvd_mapscore_workspace_bytes", "dvd_map_invert_workspace_bytes"}
 
 # name -> argtypes; kept in one table so tests can check every symbol of include/dvd_hip.h
 SIGNATURES = {
@@ -236,6 +237,12 @@ SIGNATURES = {
     "dvd_map_metrics": [c_void, C.c_int, C.c_int, c_void, c_void],
     "dvd_select_u32": [c_void, C.c_long, C.POINTER(C.c_uint32), C.c_int, c_void, c_void, c_void],
     "dvd_sparsify_bins": [c_void, c_void, C.c_long, c_void, C.c_int, c_void, c_void, c_void],
+    "dvd_map_invert_workspace_bytes": [C.c_int, C.c_int, C.c_int],
+    "dvd_map_invert": [c_void, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, c_void, c_void, c_void, c_void],
+    "dvd_map_cycle_error": [c_void, C.c_int, c_void, C.c_int, C.c_int, C.c_float, c_void, c_void, c_void],
+    "dvd_mesh_overlay_rgb8": [c_void, c_void, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_uint32, C.c_int, c_void, c_void],
+    "dvd_transfer_points": [c_void, C.c_int, C.c_int, c_void, C.c_long, c_void, c_void],
+    "dvd_map_points": [c_void, C.c_int, C.c_int, C.c_int, C.c_float, c_void, C.c_long, c_void, c_void],
     "dvd_png_bound": [C.c_int, C.c_int],
     "dvd_png_scratch_bytes": [C.c_int, C.c_int],
     "dvd_png_encode_rgb8": [c_void, C.c_int, C.c_int, c_void, C.c_long, c_void, c_void, c_void],
@@ -271,7 +278,8 @@ RESTYPES = {"dvd_gemm_kernel_name": C.c_char_p, "dvd_ingest_ragged_scratch_bytes
             "dvd_resize_gray_scratch_bytes": C.c_long, "dvd_msssim_workspace_bytes": C.c_long,
             "dvd_sflow_level_workspace_bytes": C.c_long, "dvd_sflow_workspace_bytes": C.c_long,
             "dvd_adist_workspace_bytes": C.c_long, "dvd_map_deviation_workspace_bytes": C.c_long,
-            "dvd_flow_workspace_bytes": C.c_long, "dvd_mapscore_workspace_bytes": C.c_long, "dvd_png_bound": C.c_long, "dvd_png_scratch_bytes": C.c_long, "dvd_png_scratch_bytes_huff": C.c_long,
+            "dvd_flow_workspace_bytes": C.c_long, "dvd_mapscore_workspace_bytes": C.c_long,
+            "dvd_map_invert_workspace_bytes": C.c_long, "dvd_png_bound": C.c_long, "dvd_png_scratch_bytes": C.c_long, "dvd_png_scratch_bytes_huff": C.c_long,
             "dvd_jpeg_bound": C.c_long, "dvd_jpeg_scratch_bytes": C.c_long}
 
 # entry points that exist only in the lab build (benchmarks/lab/dvd_hip_lab.h; loaded through use_library)

@@ -1622,3 +1622,196 @@ def map_score(flow: torch.Tensor, gt: torch.Tensor, hyps: torch.Tensor = None, s
         out.update(sp)
         out.update({f"ause_{m.lower()}": sp["AUSE"][m] for m in MAP_CURVES})
     return out
+
+
+# ---- the map inverse: mesh overlay, point transfer, fold count (dvd_amd/csrc/mapinv.hip; definition: DESIGN.md 4.14,
+# tests/mapinv_model.py)
+INV_MAX_SIDE, INV_MAX_POINTS = 16384, 1 << 28
+INV_STATS = ("covered", "fold_px", "flipped_tris", "degenerate_tris", "skipped_tris", "tris")
+FLO_UNKNOWN = 1e10                  # the .flo format's own "unknown" value: map_errors counts such a pixel as invalid
+
+
+def _inv_size(h, w, name):
+    if not _is_int(h) or not _is_int(w) or not 1 <= h <= INV_MAX_SIDE or not 1 <= w <= INV_MAX_SIDE:
+        raise ValueError(f"{name}: h and w must be integers 1..{INV_MAX_SIDE}, got {h!r} x {w!r}")
+    return int(h), int(w)
+
+
+def _inv_flow(flow, name):
+    """g of the coarse map [2,G,G] (or [1,2,G,G]) on the device, checked."""
+    _map_device(flow, "[2,G,G]", name, "flow")
+    if flow.dim() == 4 and flow.shape[0] == 1:
+        flow = flow[0]
+    if flow.dim() != 3 or flow.shape[0] != 2 or flow.shape[1] != flow.shape[2] or not NOISE_MIN_GRID <= flow.shape[1] <= NOISE_MAX_GRID:
+        raise ValueError(f"{name}: flow must be a coarse map [2,G,G] with G {NOISE_MIN_GRID}..{NOISE_MAX_GRID}, got {tuple(flow.shape)}")
+    return flow, int(flow.shape[1])
+
+
+def _inv_fwd(fwd, name):
+    """(h, w) of a forward map [h,w,2] f32 on the device, checked."""
+    _map_device(fwd, "[h,w,2]", name, "fwd")
+    if fwd.dim() != 3 or fwd.shape[2] != 2:
+        raise ValueError(f"{name}: fwd must be [h,w,2], got {tuple(fwd.shape)}")
+    return _inv_size(int(fwd.shape[0]), int(fwd.shape[1]), name)
+
+
+def _inv_scale(scale, name):
+    if isinstance(scale, bool) or not isinstance(scale, (int, float)) or not np.isfinite(scale):
+        raise ValueError(f"{name}: scale must be a finite number, got {scale!r}")
+    return C.c_float(scale)
+
+
+def _inv_out(out, shape, dtype, dev, name):
+    """The caller's optional output tensor, checked, or a fresh one."""
+    if out is None:
+        return torch.empty(shape, dtype=dtype, device=dev)
+    if not torch.is_tensor(out) or tuple(out.shape) != tuple(shape) or out.dtype != dtype or not out.is_contiguous() or out.device != dev:
+        raise ValueError(f"{name}: out must be a contiguous {dtype} tensor {tuple(shape)} on {dev}")
+    return out
+
+
+def _inv_points(pts, dev, name):
+    _map_device(pts, "[N,2]", name, "pts")
+    if pts.dim() != 2 or pts.shape[1] != 2 or pts.shape[0] > INV_MAX_POINTS:
+        raise ValueError(f"{name}: pts must be [N,2] with N at most {INV_MAX_POINTS}, got {tuple(pts.shape)}")
+    if pts.device != dev:
+        raise ValueError(f"{name}: pts is on {pts.device}, the map on {dev}")
+    return int(pts.shape[0])
+
+
+def _inv_color(color, name, what):
+    if not isinstance(color, (tuple, list)) or len(color) != 3 or not all(_is_int(c) and 0 <= c <= 255 for c in color):
+        raise ValueError(f"{name}: {what} must be three integers 0..255, got {color!r}")
+    return int(color[0]) | int(color[1]) << 8 | int(color[2]) << 16
+
+
+def _inv_workspace(h, w, step, dev):
+    return torch.empty(_size_query("dvd_map_invert_workspace_bytes", h, w, step), dtype=torch.uint8, device=dev)
+
+
+def map_invert(flow: torch.Tensor, h: int, w: int, step: int = 8, scale: float = 0.987, out: torch.Tensor = None, lattice: bool = False):
+    """The inverse of the predicted map at the photograph's h x w.  flow [2,G,G] is a backward map (page pixel -> photograph
+    position, what unwarp_u8 samples); the page's triangle mesh - lattice rows and columns 0, step, 2 step, .., the last pixel -
+    is rasterised on the photograph with exact integer edge tests, the smallest triangle id winning where the map folds.
+    Returns (fwd, stats): fwd [h,w,2] f32 holds the page position (u, v) of every covered photograph pixel and the bit pattern
+    0xffffffff (MAP_INVALID as int32) in both components elsewhere; stats = {covered, fold_px, flipped_tris, degenerate_tris,
+    skipped_tris, tris}, exact integers (fold_px: pixels covered by two or more triangles).  lattice=True: also the lattice's
+    Q8 vertices [rows,cols,2] int32 and validity flags [rows,cols] uint8.  Five launches; equal calls give equal bytes."""
+    flow, g = _inv_flow(flow, "map_invert")
+    h, w = _inv_size(h, w, "map_invert")
+    if not _is_int(step) or not 1 <= step <= INV_MAX_SIDE:
+        raise ValueError(f"map_invert: step must be an integer 1..{INV_MAX_SIDE}, got {step!r}")
+    cscale = _inv_scale(scale, "map_invert")
+    dev = flow.device
+    fwd = _inv_out(out, (h, w, 2), torch.float32, dev, "map_invert")
+    ws = _inv_workspace(h, w, int(step), dev)
+    words = torch.empty(len(INV_STATS), dtype=torch.int64, device=dev)
+    lib.call("dvd_map_invert", ptr(flow), g, h, w, int(step), cscale, ptr(fwd), ptr(words), ptr(ws), stream_ptr())
+    stats = dict(zip(INV_STATS, (int(v) for v in words.cpu().numpy())))
+    if not lattice:
+        return fwd, stats
+    rows, cols = ((n - 1) // step + 1 + ((n - 1) % step != 0) for n in (h, w))
+    up = lambda x: (x + 255) & ~255                                                      # noqa: E731
+    blocks = (h * w + 1023) // 1024
+    verts_at = up(up(up(up(blocks * 24) + blocks * 16) + 4 * h * w) + h * w)              # mapinv_core.h's layout
+    valid_at = up(verts_at + 8 * rows * cols)
+    verts = ws[verts_at:verts_at + 8 * rows * cols].view(torch.int32).view(rows, cols, 2).clone()
+    return fwd, stats, verts, ws[valid_at:valid_at + rows * cols].view(rows, cols).clone()
+
+
+def map_cycle_error(flow: torch.Tensor, fwd: torch.Tensor, scale: float = 0.987) -> dict:
+    """How well fwd inverts the map: at every covered photograph pixel p the f32 distance |backward(fwd(p)) - p|, the backward
+    map evaluated bilinearly between the page pixels.  Returns {cycle_mean, cycle_max, n}: the f64 sum, added in a fixed order,
+    over the count n; NaN without a covered pixel.  Two launches."""
+    flow, g = _inv_flow(flow, "map_cycle_error")
+    h, w = _inv_fwd(fwd, "map_cycle_error")
+    if fwd.device != flow.device:
+        raise ValueError(f"map_cycle_error: flow is on {flow.device}, fwd on {fwd.device}")
+    cscale = _inv_scale(scale, "map_cycle_error")
+    ws = torch.empty(max((((h * w + 1023) // 1024) * 24 + 255) & ~255, 256), dtype=torch.uint8, device=flow.device)
+    words = torch.empty(3, dtype=torch.int64, device=flow.device)
+    lib.call("dvd_map_cycle_error", ptr(flow), g, ptr(fwd), h, w, cscale, ptr(words), ptr(ws), stream_ptr())
+    host = words.cpu().numpy()
+    n = int(host[0])
+    if n == 0:
+        return {"cycle_mean": float("nan"), "cycle_max": float("nan"), "n": 0}
+    return {"cycle_mean": float(host[1:2].view(np.float64)[0]) / n, "cycle_max": float(host[2:3].view(np.uint32)[:1].view(np.float32)[0]), "n": n}
+
+
+def mesh_overlay(src_u8: torch.Tensor, fwd: torch.Tensor, lines: int = 17, thickness: int = 1, color=(255, 0, 0),
+                 outline_color=(0, 255, 0), dim: bool = False, out: torch.Tensor = None) -> torch.Tensor:
+    """The predicted page mesh drawn on the photograph src_u8 [h,w,3] uint8: `lines` grid lines per axis of the page in `color`,
+    the page's outline in `outline_color`, both widened to `thickness` 1..3; dim=True halves the pixels the page does not cover.
+    Returns a new [h,w,3] uint8 tensor.  One launch."""
+    h, w = _inv_fwd(fwd, "mesh_overlay")
+    if _rgb8_input(src_u8, "mesh_overlay") != (h, w) or not src_u8.is_cuda or src_u8.device != fwd.device:
+        raise ValueError(f"mesh_overlay: src_u8 must be [{h},{w},3] on {fwd.device} like fwd, got {tuple(src_u8.shape)} on {src_u8.device}")
+    if not _is_int(lines) or not 2 <= lines <= INV_MAX_SIDE:
+        raise ValueError(f"mesh_overlay: lines must be an integer 2..{INV_MAX_SIDE}, got {lines!r}")
+    if not _is_int(thickness) or not 1 <= thickness <= 3:
+        raise ValueError(f"mesh_overlay: thickness must be 1, 2 or 3, got {thickness!r}")
+    c0, c1 = _inv_color(color, "mesh_overlay", "color"), _inv_color(outline_color, "mesh_overlay", "outline_color")
+    out = _inv_out(out, (h, w, 3), torch.uint8, fwd.device, "mesh_overlay")
+    if out.data_ptr() == src_u8.data_ptr():
+        raise ValueError("mesh_overlay: out must be another buffer than src_u8 (a line pixel reads its neighbours' source)")
+    lib.call("dvd_mesh_overlay_rgb8", ptr(src_u8), ptr(fwd), h, w, int(lines), int(thickness), c0, c1, int(bool(dim)), ptr(out),
+             stream_ptr())
+    return out
+
+
+def mesh_overlay_to_file(src_u8: torch.Tensor, fwd: torch.Tensor, path: str, huffman: str = "fixed", **kwargs) -> int:
+    """mesh_overlay as a PNG file through the device encoder: only the compressed file crosses to the host.  Returns its bytes."""
+    png_huffman_flag(huffman, "mesh_overlay_to_file")
+    return png_encode_to_file(mesh_overlay(src_u8, fwd, **kwargs), path, huffman)
+
+
+def transfer_points(fwd: torch.Tensor, pts: torch.Tensor, out: torch.Tensor = None) -> torch.Tensor:
+    """Photograph -> page: pts [N,2] f32 (x, y) on the photograph -> [N,2] f32 (u, v) on the dewarped page, fwd sampled
+    bilinearly.  A point outside the photograph, or with an uncovered pixel among its four taps, gives the bit pattern
+    0xffffffff in both components."""
+    h, w = _inv_fwd(fwd, "transfer_points")
+    n = _inv_points(pts, fwd.device, "transfer_points")
+    out = _inv_out(out, (n, 2), torch.float32, fwd.device, "transfer_points")
+    lib.call("dvd_transfer_points", ptr(fwd), h, w, ptr(pts), n, ptr(out), stream_ptr())
+    return out
+
+
+def map_points(flow: torch.Tensor, pts: torch.Tensor, h: int, w: int, scale: float = 0.987, out: torch.Tensor = None) -> torch.Tensor:
+    """Page -> photograph: pts [N,2] f32 (u, v) on the page of h x w -> [N,2] f32 (x, y) on the photograph, the backward map
+    evaluated bilinearly between the page pixels (a position outside the page is clamped to it); 0xffffffff where a component
+    is not finite."""
+    flow, g = _inv_flow(flow, "map_points")
+    h, w = _inv_size(h, w, "map_points")
+    cscale = _inv_scale(scale, "map_points")
+    n = _inv_points(pts, flow.device, "map_points")
+    out = _inv_out(out, (n, 2), torch.float32, flow.device, "map_points")
+    lib.call("dvd_map_points", ptr(flow), g, h, w, cscale, ptr(pts), n, ptr(out), stream_ptr())
+    return out
+
+
+def inverse_displacement(fwd) -> np.ndarray:
+    """fwd [h,w,2] (a device tensor or a host array) -> the host field fwd(p) - p, [h,w,2] float32, with FLO_UNKNOWN at every
+    uncovered pixel."""
+    host = fwd.cpu().numpy() if torch.is_tensor(fwd) else np.asarray(fwd)
+    if host.ndim != 3 or host.shape[2] != 2 or host.dtype != np.float32:
+        raise ValueError(f"inverse_displacement: fwd must be [h,w,2] float32, got {host.shape} {host.dtype}")
+    h, w = host.shape[:2]
+    covered = np.ascontiguousarray(host).view(np.int32)[..., 0] != MAP_INVALID
+    with np.errstate(invalid="ignore"):
+        d = np.stack([host[..., 0] - np.arange(w, dtype=np.float32)[None, :], host[..., 1] - np.arange(h, dtype=np.float32)[:, None]],
+                     axis=-1).astype(np.float32)
+    d[~covered] = np.float32(FLO_UNKNOWN)
+    return d
+
+
+def inverse_write_flo(fwd, path: str) -> int:
+    """The forward displacement fwd(p) - p as a Middlebury .flo file (flo_write); uncovered pixels hold 1e10, the format's own
+    "unknown" value, which map_errors treats as invalid.  Returns the file's bytes."""
+    return flo_write(inverse_displacement(fwd), path)
+
+
+def coverage_mask(fwd: torch.Tensor) -> torch.Tensor:
+    """[h,w,3] uint8 on the device: 255 where fwd is covered, 0 elsewhere (the input of png_encode)."""
+    h, w = _inv_fwd(fwd, "coverage_mask")
+    covered = fwd.view(torch.int32)[..., 0] != MAP_INVALID
+    return (covered.to(torch.uint8) * 255)[..., None].expand(h, w, 3).contiguous()

@@ -854,6 +854,44 @@ int dvd_select_u32(const uint32_t* keys, long n, const uint32_t* ranks, int k, u
 int dvd_sparsify_bins(const float* e, const float* key, long n, const uint32_t* thr, int k, unsigned long long* out, void* ws,
                       void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * The map inverse (tests/mapinv_model.py is the definition).  The predicted map flow [2,g,g] is a backward map:
+ * page pixel -> photograph position, the position the unwarp tail samples (dvd_unwarp_grid, un-normalised with
+ * align_corners=True).  Its inverse at the photograph's h x w comes from rasterising the page's triangle mesh - lattice rows and
+ * columns 0, step, 2 step, .., h - 1 / w - 1 - on the photograph: vertices in Q8 integers, exact int64 edge functions, the
+ * top-left rule, the smallest triangle id wins.  fwd [h,w,2] f32 holds the page position (u, v) of every covered photograph
+ * pixel and the bit pattern 0xffffffff in both components elsewhere.
+ * Sides 1..16384 and g 2..8192 (else DVD_E_INV_SHAPE), step 1..16384 (DVD_E_INV_STEP), lines 2..16384 and thickness 1..3
+ * (DVD_E_INV_LINES), 0..2^28 points (DVD_E_INV_POINTS): all refused before any launch.  No scratch memory; the one atomic is an
+ * integer minimum.
+ * ---------------------------------------------------------------------------------------- */
+#define DVD_E_INV_SHAPE (-53)
+#define DVD_E_INV_STEP (-54)
+#define DVD_E_INV_LINES (-55)
+#define DVD_E_INV_POINTS (-56)
+/* bytes of `ws` for a photograph of h x w and a mesh of `step`, 256-byte aligned, or a status above */
+long dvd_map_invert_workspace_bytes(int h, int w, int step);
+/* fwd [h,w,2] f32 (8-byte aligned) and stats (device, six u64: covered, fold_px, flipped_tris, degenerate_tris, skipped_tris,
+ * tris) <- flow [2,g,g].  A triangle with an invalid vertex (not finite, or beyond 2^22 px) or whose clipped bounding box holds
+ * more than max(1024, 64 step^2) pixels is skipped; one of area 0 is degenerate; one of negative area is rasterised with two
+ * vertices swapped and counted as flipped.  fold_px = the pixels covered by two or more triangles.  Five launches. */
+int dvd_map_invert(const float* flow, int g, int h, int w, int step, float scale, float* fwd, unsigned long long* stats, void* ws,
+                   void* stream);
+/* out (device, three 8-byte words) = n, the bits of the f64 sum and the bits of the f32 maximum of |backward(fwd(p)) - p| over
+ * the covered pixels p where it is finite; the sum is added in a fixed order.  ws: a workspace of the same h x w, any step. */
+int dvd_map_cycle_error(const float* flow, int g, const float* fwd, int h, int w, float scale, unsigned long long* out, void* ws,
+                        void* stream);
+/* out [h,w,3] u8 <- src [h,w,3] u8 (another buffer) with the page's grid drawn on it: `lines` lines per axis in `color`, the
+ * page's outline in `outline_color` (both 0x00BBGGRR), widened to `thickness`; dim != 0 halves the uncovered pixels. */
+int dvd_mesh_overlay_rgb8(const uint8_t* src, const float* fwd, int h, int w, int lines, int thickness, uint32_t color,
+                          uint32_t outline_color, int dim, uint8_t* out, void* stream);
+/* out [n,2] f32 (u, v on the page) <- pts [n,2] f32 (x, y on the photograph): fwd sampled bilinearly; 0xffffffff in both
+ * components where the point is outside the photograph or a tap is uncovered. */
+int dvd_transfer_points(const float* fwd, int h, int w, const float* pts, long n, float* out, void* stream);
+/* out [n,2] f32 (x, y on the photograph) <- pts [n,2] f32 (u, v on the page, clamped to it): the backward map, bilinear over the
+ * four surrounding page pixels' positions; 0xffffffff where a component is not finite. */
+int dvd_map_points(const float* flow, int g, int h, int w, float scale, const float* pts, long n, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -18,7 +18,12 @@ between the map predicted from the corrupted input and the one predicted from th
 
 --gt_map_dir DIR scores every document's predicted map against the ground-truth map DIR holds for it (settings.gt_map_dir;
 DESIGN.md 4.13: <stem>.flo, flow_<stem>.flo, <stem>.npy or flow_<stem>.npy - the files --flow_outputs flo,npy writes): EPE, PCK,
-Fl and the sparsification error AUSE, in map_score.txt; under --corruption the table gains the columns epe, pck5, ause_epe."""
+Fl and the sparsification error AUSE, in map_score.txt; under --corruption the table gains the columns epe, pck5, ause_epe.
+
+--inverse_outputs mesh,flo,mask inverts every document's predicted map on the device (settings.inverse_outputs)
+and writes under <name>/pred_flow the predicted page mesh drawn on the photograph, the forward displacement field and / or the
+coverage mask; map_inverse.txt holds the coverage, the fold count and the cycle error, which need neither a scan nor a
+ground-truth map; under --corruption the table gains the columns fold and cycle."""
 import argparse
 import importlib
 import os
@@ -65,10 +70,12 @@ def write_corruption_table(path, rows, metrics):
 MAP_DEV = "map_dev"        # the table's column under --keyed_noise, after the env.gt_dir metrics
 MAP_SCORE = "map_score"    # settings.map_score under --gt_map_dir: [(path, dict)]
 MAP_SCORE_COLUMNS = ("epe", "pck5", "ause_epe")   # ... and the table's columns from it, after every other one
+MAP_INVERSE = "map_inverse"                       # settings.map_inverse under --inverse_outputs: [(path, dict)]
+MAP_INVERSE_COLUMNS = ("fold", "cycle")           # ... and the table's last columns: fold_px / covered and cycle_mean
 
 
 def run_sampling(train_module, train_name, seed, name, cudnn_benchmark=True, corruption=False, severity=None,
-                 corruption_number=None, *, keyed_noise=False, flow_outputs="", gt_map_dir=""):
+                 corruption_number=None, *, keyed_noise=False, flow_outputs="", gt_map_dir="", inverse_outputs=""):
     from dvd_amd import ops
     print(f"Sampling:  {train_module}  {train_name}\nDate: {date.today().strftime('%d/%m/%Y')}")
     settings = ws_settings.Settings()
@@ -81,6 +88,8 @@ def run_sampling(train_module, train_name, seed, name, cudnn_benchmark=True, cor
         settings.flow_outputs = flow_outputs
     if gt_map_dir:                                            # likewise
         settings.gt_map_dir = gt_map_dir
+    if inverse_outputs:                                       # likewise
+        settings.inverse_outputs = inverse_outputs
     save_dir = os.path.join(settings.env.workspace_dir, settings.project_path)
     os.makedirs(save_dir, exist_ok=True)
     shutil.copyfile(settings.project_path + ".py", os.path.join(save_dir, settings.script_name + ".py"))
@@ -104,7 +113,7 @@ def run_sampling(train_module, train_name, seed, name, cudnn_benchmark=True, cor
             print(f"corruption {number} ({kind}): no device kernel, round skipped")
             continue
         settings.severity, settings.corruption_number, settings.name = sev, number, round_name(name, sev, number)
-        for metric in ops.GT_METRIC_NAMES + (MAP_DEV, MAP_SCORE):   # a round's scores are its own
+        for metric in ops.GT_METRIC_NAMES + (MAP_DEV, MAP_SCORE, MAP_INVERSE):   # a round's scores are its own
             if hasattr(settings, metric):
                 delattr(settings, metric)
         run(settings)
@@ -113,11 +122,14 @@ def run_sampling(train_module, train_name, seed, name, cudnn_benchmark=True, cor
         if gt_map_dir:
             from dvd_amd.evaluation import map_score_means
             means.update(map_score_means(getattr(settings, MAP_SCORE, None) or [], MAP_SCORE_COLUMNS))
+        if inverse_outputs:
+            from dvd_amd.evaluation import map_inverse_means
+            means.update(map_inverse_means(getattr(settings, MAP_INVERSE, None) or [], MAP_INVERSE_COLUMNS))
         rows.append((number, kind, sev, means))
     settings.name = name
     if rows:
         metrics = [m for m in ops.GT_METRIC_NAMES if any(m in r[3] for r in rows)] + ([MAP_DEV] if keyed_noise else []) + \
-            (list(MAP_SCORE_COLUMNS) if gt_map_dir else [])
+            (list(MAP_SCORE_COLUMNS) if gt_map_dir else []) + (list(MAP_INVERSE_COLUMNS) if inverse_outputs else [])
         write_corruption_table(os.path.join("vis_hp", str(settings.env.eval_dataset_name), name, "corruption_table.txt"), rows, metrics)
 
 
@@ -137,6 +149,8 @@ def main():
                    "document's predicted map under pred_flow/ (nothing by default)")
     p.add_argument("--gt_map_dir", type=str, default="", help="directory of ground-truth maps (<stem>.flo, flow_<stem>.flo, <stem>.npy, "
                    "flow_<stem>.npy): score every document's predicted map against its own (EPE, PCK, Fl, AUSE)")
+    p.add_argument("--inverse_outputs", type=str, default="", help="comma-separated list of mesh, flo, mask: invert every document's "
+                   "predicted map and write the page mesh on the photograph, the forward field and / or the coverage mask under pred_flow/")
     a = p.parse_args()
     a.seed = torch.initial_seed() & (2 ** 32 - 1)      # as the reference: the CLI value is overwritten (:77-78)
     print(f"Seed is {a.seed}")
@@ -144,7 +158,7 @@ def main():
     np.random.seed(a.seed)
     run_sampling(a.train_module, a.train_name, seed=a.seed, name=a.name, cudnn_benchmark=a.cudnn_benchmark,
                  corruption=a.corruption, severity=a.severity, corruption_number=a.corruption_number, keyed_noise=a.keyed_noise,
-                 flow_outputs=a.flow_outputs, gt_map_dir=a.gt_map_dir)
+                 flow_outputs=a.flow_outputs, gt_map_dir=a.gt_map_dir, inverse_outputs=a.inverse_outputs)
 
 
 if __name__ == "__main__":
