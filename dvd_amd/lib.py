@@ -132,6 +132,14 @@ E_FLOW_SHAPE = -50                     # DVD_E_FLOW_SHAPE
 E_MAP_SHAPE, E_MAP_RANKS = -51, -52    # DVD_E_MAP_*: what the map score refuses
 E_INV_SHAPE, E_INV_STEP, E_INV_LINES, E_INV_POINTS = -53, -54, -55, -56    # DVD_E_INV_*: what the map inverse refuses
 
+E_SYNTH_SHAPE, E_SYNTH_PARAM = -57, -58    # DVD_E_SYNTH_*: what the synthetic-document render refuses
+
+
+class SynthParams(C.Structure):
+    """dvd_synth_params: the render's shading (all of l0, lgx, lgy, k zero: none) and the mean scan area per covered pixel."""
+    _fields_ = [(name, C.c_float) for name in ("l0", "lgx", "lgy", "k", "a_ref")]
+
+
 RAGGED_CAP = 64  # DVD_RAGGED_CAP: documents per launch of the ragged entry points (larger batches are cut by the library)
 
 NON_STATUS = {"dvd_last_error", "dvd_version", "dvd_engine_workspace_bytes", "dvd_engine_tensor_count",
@@ -243,6 +251,8 @@ SIGNATURES = {
     "dvd_mesh_overlay_rgb8": [c_void, c_void, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_uint32, C.c_int, c_void, c_void],
     "dvd_transfer_points": [c_void, C.c_int, C.c_int, c_void, C.c_long, c_void, c_void],
     "dvd_map_points": [c_void, C.c_int, C.c_int, C.c_int, C.c_float, c_void, C.c_long, c_void, c_void],
+    "dvd_synth_render_rgb8": [c_void, C.c_int, C.c_int, c_void, C.c_int, C.c_int, c_void, C.c_uint32, C.POINTER(SynthParams), c_void, c_void],
+    "dvd_synth_footprint": [c_void, C.c_int, C.c_int, C.c_int, C.c_int, c_void, c_void],
     "dvd_png_bound": [C.c_int, C.c_int],
     "dvd_png_scratch_bytes": [C.c_int, C.c_int],
     "dvd_png_encode_rgb8": [c_void, C.c_int, C.c_int, c_void, C.c_long, c_void, c_void, c_void],

@@ -1815,3 +1815,123 @@ def coverage_mask(fwd: torch.Tensor) -> torch.Tensor:
     h, w = _inv_fwd(fwd, "coverage_mask")
     covered = fwd.view(torch.int32)[..., 0] != MAP_INVALID
     return (covered.to(torch.uint8) * 255)[..., None].expand(h, w, 3).contiguous()
+
+
+# ---- synthetic documents: a flat scan drawn through a known map (dvd_amd/csrc/synth.hip; definition: DESIGN.md 4.15,
+# tests/synth_model.py)
+SYNTH_MAX_SIDE, SYNTH_MAX_RADIUS = 16384, 8
+SYNTH_SHADING = ("l0", "lgx", "lgy", "k", "a_ref")
+
+
+def _synth_device(t, dtype, shape_text, name, what):
+    """A host tensor is a lib.DvdError (there is no CPU path); a wrong type or layout a ValueError."""
+    if not torch.is_tensor(t):
+        raise ValueError(f"{name}: {what} must be a {shape_text} tensor, got {type(t)}")
+    if not t.is_cuda:
+        raise lib.DvdError(f"{name}: {what} must be on the device (the render has no CPU path), got {t.device}")
+    if t.dtype != dtype or not t.is_contiguous():
+        raise ValueError(f"{name}: {what} must be contiguous {dtype}, got {t.dtype} contiguous={t.is_contiguous()}")
+
+
+def _synth_sides(h, w, name, what):
+    if not 1 <= h <= SYNTH_MAX_SIDE or not 1 <= w <= SYNTH_MAX_SIDE:
+        raise ValueError(f"{name}: the sides of {what} must be 1..{SYNTH_MAX_SIDE}, got {h} x {w}")
+    return int(h), int(w)
+
+
+def _synth_fwd(fwd, name):
+    _synth_device(fwd, torch.float32, "[h,w,2] float32", name, "fwd")
+    if fwd.dim() != 3 or fwd.shape[2] != 2:
+        raise ValueError(f"{name}: fwd must be [h,w,2], got {tuple(fwd.shape)}")
+    return _synth_sides(int(fwd.shape[0]), int(fwd.shape[1]), name, "fwd")
+
+
+def _synth_scan(scan_u8, name):
+    _synth_device(scan_u8, torch.uint8, "[hs,ws,3] uint8", name, "scan_u8")
+    if scan_u8.dim() != 3 or scan_u8.shape[2] != 3:
+        raise ValueError(f"{name}: scan_u8 must be [hs,ws,3], got {tuple(scan_u8.shape)}")
+    return _synth_sides(int(scan_u8.shape[0]), int(scan_u8.shape[1]), name, "scan_u8")
+
+
+def synth_shading(shading, name="synth_render", need_a_ref=False) -> dict:
+    """shading (None, or a dict with some of l0, lgx, lgy, k, a_ref) -> all five as floats, checked.  None, or all of l0, lgx,
+    lgy and k zero, is no shading.  a_ref stays None where it is not given (synth_render then counts fwd's covered pixels)."""
+    if shading is None:
+        return dict(l0=0.0, lgx=0.0, lgy=0.0, k=0.0, a_ref=1.0)
+    if not isinstance(shading, dict) or set(shading) - set(SYNTH_SHADING):
+        raise ValueError(f"{name}: shading must be None or a dict with keys among {SYNTH_SHADING}, got {shading!r}")
+    out = dict(l0=1.0, lgx=0.0, lgy=0.0, k=0.0, a_ref=None)
+    out.update(shading)
+    for key, v in out.items():
+        if key == "a_ref" and v is None and not need_a_ref:
+            continue
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not np.isfinite(v) or abs(v) > float(np.finfo(np.float32).max):
+            raise ValueError(f"{name}: shading[{key!r}] must be a finite number, got {v!r}")
+        out[key] = float(v)
+    if out["a_ref"] is not None and not out["a_ref"] > 0:
+        raise ValueError(f"{name}: shading['a_ref'] must be positive, got {out['a_ref']!r}")
+    return out
+
+
+def synth_render(scan_u8: torch.Tensor, fwd: torch.Tensor, background=(255, 255, 255), shading=None, out: torch.Tensor = None) -> torch.Tensor:
+    """The photograph [h,w,3] uint8 of a flat scan [hs,ws,3] uint8 seen through fwd [h,w,2] f32, the forward field map_invert
+    returns (photograph pixel -> page position).  A covered pixel samples the scan with an integer tent filter whose radii 1..8
+    follow fwd's first differences (radius 1: Q8 bilinear); an uncovered pixel takes the background, an RGB triple or a
+    [h,w,3] uint8 tensor; the page's edge blends by the covered share of the 3 x 3 window.  shading: None or a dict with l0
+    (default 1), lgx, lgy, k and a_ref (default: scan pixels per covered pixel of fwd).  One launch; equal calls, equal bytes."""
+    name = "synth_render"
+    hs, ws = _synth_scan(scan_u8, name)
+    h, w = _synth_fwd(fwd, name)
+    dev = fwd.device
+    if scan_u8.device != dev:
+        raise ValueError(f"{name}: scan_u8 is on {scan_u8.device}, fwd on {dev}")
+    bg, color = None, 0
+    if torch.is_tensor(background):
+        _synth_device(background, torch.uint8, f"[{h},{w},3] uint8", name, "background")
+        if tuple(background.shape) != (h, w, 3) or background.device != dev:
+            raise ValueError(f"{name}: background must be [{h},{w},3] on {dev}, got {tuple(background.shape)} on {background.device}")
+        bg = background
+    else:
+        color = _inv_color(background, name, "background")
+    prm = synth_shading(shading, name)
+    if prm["a_ref"] is None:
+        covered = int((fwd.view(torch.int32)[..., 0] != MAP_INVALID).sum())
+        prm["a_ref"] = hs * ws / covered if covered else 1.0
+    out = _inv_out(out, (h, w, 3), torch.uint8, dev, name)
+    if out.data_ptr() == scan_u8.data_ptr() or (bg is not None and out.data_ptr() == bg.data_ptr()):
+        raise ValueError(f"{name}: out must be another buffer than scan_u8 and background")
+    if w % 4 == 0 and out.data_ptr() % 4:
+        raise ValueError(f"{name}: out must be 4-byte aligned where w is a multiple of 4")
+    cprm = lib.SynthParams(*(prm[k] for k in SYNTH_SHADING))
+    lib.call("dvd_synth_render_rgb8", ptr(scan_u8), hs, ws, ptr(fwd), h, w, ptr(bg), color, C.byref(cprm), ptr(out), stream_ptr())
+    return out
+
+
+def synth_footprint(scan_hw, fwd: torch.Tensor, out: torch.Tensor = None) -> torch.Tensor:
+    """[h,w,2] uint8: the radii (rx, ry) synth_render uses at every covered pixel of fwd for a scan of scan_hw = (hs, ws), 0 at
+    the uncovered ones.  A radius of 8 is the cap: the scan is minified further there than the filter follows."""
+    name = "synth_footprint"
+    if not isinstance(scan_hw, (tuple, list)) or len(scan_hw) != 2 or not all(_is_int(v) for v in scan_hw):
+        raise ValueError(f"{name}: scan_hw must be two integers (hs, ws), got {scan_hw!r}")
+    hs, ws = _synth_sides(scan_hw[0], scan_hw[1], name, "the scan")
+    h, w = _synth_fwd(fwd, name)
+    out = _inv_out(out, (h, w, 2), torch.uint8, fwd.device, name)
+    lib.call("dvd_synth_footprint", ptr(fwd), h, w, hs, ws, ptr(out), stream_ptr())
+    return out
+
+
+def synth_document(scan_u8: torch.Tensor, flow: torch.Tensor, h: int, w: int, step: int = 8, scale: float = 0.987,
+                   background=(255, 255, 255), shading=None):
+    """A photograph of h x w whose map is known: flow [2,G,G] is the backward map (what unwarp_u8 samples), map_invert turns it
+    round and synth_render draws the scan through the result.  Returns (photo [h,w,3] uint8, fwd [h,w,2] f32, stats): the
+    stats are map_invert's, and the shading's a_ref is hs ws / stats['covered'] unless the caller gives one."""
+    name = "synth_document"
+    hs, ws = _synth_scan(scan_u8, name)
+    _synth_device(flow, torch.float32, "[2,G,G] float32", name, "flow")
+    prm = synth_shading(shading, name)
+    if not torch.is_tensor(background):
+        _inv_color(background, name, "background")
+    fwd, stats = map_invert(flow, h, w, step=step, scale=scale)
+    if shading is not None and prm["a_ref"] is None:
+        prm["a_ref"] = hs * ws / stats["covered"] if stats["covered"] else 1.0
+    return synth_render(scan_u8, fwd, background=background, shading=None if shading is None else prm), fwd, stats

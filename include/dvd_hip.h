@@ -892,6 +892,33 @@ int dvd_transfer_points(const float* fwd, int h, int w, const float* pts, long n
  * four surrounding page pixels' positions; 0xffffffff where a component is not finite. */
 int dvd_map_points(const float* flow, int g, int h, int w, float scale, const float* pts, long n, float* out, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Synthetic documents (tests/synth_model.py is the definition).  A flat scan [hs,ws,3] u8 is drawn on a
+ * photograph of h x w through fwd [h,w,2] f32, exactly what dvd_map_invert writes: the page position (u, v) in page pixels of
+ * every covered photograph pixel, the bit pattern 0xffffffff elsewhere.  Per covered pixel: the Q8 scan position
+ * floor(u (ws - 1) / (w - 1) 256 + 1/2); integer radii rx, ry = 1..8 from the first differences over the covered 4-neighbours;
+ * a separable integer tent of that half-width (rx = ry = 1 is Q8 bilinear sampling), rounded exactly; optional shading in Q16;
+ * and a blend with the background by the covered share of the 3 x 3 window.  An uncovered pixel takes the background.
+ * Sides 1..16384 (else DVD_E_SYNTH_SHAPE), finite shading parameters and, with shading on, a_ref > 0 (DVD_E_SYNTH_PARAM): all
+ * refused before any launch.  No atomics, no scratch memory; equal calls give equal bytes.
+ * ---------------------------------------------------------------------------------------- */
+#define DVD_E_SYNTH_SHAPE (-57)
+#define DVD_E_SYNTH_PARAM (-58)
+/* Shading: each channel c becomes min(255, (c Lq + 32768) >> 16), Lq = clamp(rint(65536 L), 0, 131072),
+ * L = l0 + lgx (px / (w - 1) - 1/2) + lgy (py / (h - 1) - 1/2) + k (A / a_ref - 1), A = the scan area under the photograph pixel.
+ * All of l0, lgx, lgy, k zero: no shading, and a_ref is not read. */
+typedef struct {
+  float l0, lgx, lgy, k;
+  float a_ref; /* the mean scan area per covered photograph pixel: hs ws / covered */
+} dvd_synth_params;
+/* out [h,w,3] u8 <- scan [hs,ws,3] u8 through fwd (8-byte aligned).  bg [h,w,3] u8, or NULL for the colour bg_color
+ * (0x00BBGGRR) everywhere.  Where w is a multiple of 4 the picture is stored as whole dwords and out must be 4-byte aligned.
+ * out must be another buffer than scan and bg.  One launch. */
+int dvd_synth_render_rgb8(const uint8_t* scan, int hs, int ws, const float* fwd, int h, int w, const uint8_t* bg, uint32_t bg_color,
+                          const dvd_synth_params* params, uint8_t* out, void* stream);
+/* out [h,w,2] u8 <- the radii (rx, ry) the render uses at every covered pixel, 0 at the others.  One launch. */
+int dvd_synth_footprint(const float* fwd, int h, int w, int hs, int ws, uint8_t* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
