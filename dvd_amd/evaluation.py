@@ -16,7 +16,28 @@ import numpy as np
 import torch as th
 
 from . import ops, run_options, synth
-from .run_options import GT_METRICS, RunOptions, parse_gt_metrics  # noqa: F401 - parse_gt_metrics is imported from here
+from .run_options import FLOW_OUTPUTS, GT_METRICS, INVERSE_OUTPUTS, parse_gt_metrics  # noqa: F401 - these are imported from here
+from .run_options import SCORE, SCORES, RoundOptions, RunOptions
+
+MAP_SCORE_COLUMNS, MAP_SCORE_LOGGED = SCORE["map_score"].columns, SCORE["map_score"].logged           # map_score.txt; the log line
+MAP_INVERSE_COLUMNS, MAP_INVERSE_LOGGED = SCORE["map_inverse"].columns, SCORE["map_inverse"].logged
+map_score_means = SCORE["map_score"].means      # {key: mean over the documents that have a finite value for it} of settings.map_score
+
+
+def run_dir(settings):
+    """Where a round writes: its pictures, its predicted maps and its score sheets."""
+    return f"vis_hp/{settings.env.eval_dataset_name}/{settings.name}"
+
+
+def page_name(path):
+    """The file name a document's page is written under: its path, as a .png when it has no extension."""
+    return path if os.path.splitext(path)[1] else path + ".png"
+
+
+def page_stem(path):
+    """The <stem> of warped_<stem>.png and of every other per-document file."""
+    from utils_flow.visualization_utils import _stem
+    return _stem([page_name(path)])
 
 
 def run_sample_lr_dewarping(settings, logger, diffusion, model, radius, source, feature_size, raw_corr, init_flow, c20,
@@ -293,15 +314,6 @@ def adopt_reference_items(batch, device):
                 raise ValueError(f"{d['path']}: no 'source_image' and a non-integer 'source_image_ori' to make it from")
 
 
-def keyed_noise_of(settings):
-    """`settings.keyed_noise` (run_sampling.py --keyed_noise): absent means False; anything but a bool is a ValueError that names
-    the attribute."""
-    flag = getattr(settings, "keyed_noise", False)
-    if not isinstance(flag, (bool, np.bool_)):
-        raise ValueError(f"settings.keyed_noise must be True or False, got {flag!r}")
-    return bool(flag)
-
-
 def sample_batch(settings, logger, diffusion, model, batch, grid, device, *, keyed_noise=None, keep_hypotheses=False):
     """The conditioned documents of one batch through `run_sample_lr_dewarping` (evaluation.py:247-265): the flow [B,2,G,G].
     keyed_noise (None: settings.keyed_noise): the sampler's noise is keyed per document by (settings.seed, path), the
@@ -311,7 +323,7 @@ def sample_batch(settings, logger, diffusion, model, batch, grid, device, *, key
     src, msk, seg, line = (_stack(batch, k, device) for k in ("y512", "mask_cat", "mask_y512", "line_msk"))
     init_flow = _stack(batch, "init_flow", device) if settings.env.use_init_flow else th.zeros(nb, 2, grid, grid, device=device)  # :176-181
     extra = {}
-    if keyed_noise_of(settings) if keyed_noise is None else keyed_noise:
+    if run_options.check(settings, "keyed_noise") if keyed_noise is None else keyed_noise:
         extra["noise_keys"] = [ops.corruption_key(getattr(settings, "seed", 0), d["path"]) for d in batch]
     if keep_hypotheses:
         extra["keep_hypotheses"] = True
@@ -369,31 +381,14 @@ def unwarp_tail(batch, flow, mode, device):
     return outs
 
 
-FLOW_OUTPUTS = ("png", "flo", "npy")     # what settings.flow_outputs may name
-
-
-def flow_outputs_of(settings):
-    """`settings.flow_outputs` (run_sampling.py --flow_outputs): a comma-separated list of FLOW_OUTPUTS names without repeats ->
-    the names, in the order of FLOW_OUTPUTS.  Absent or "" means none; anything else is a ValueError that names the attribute."""
-    value = getattr(settings, "flow_outputs", "")
-    if isinstance(value, str) and value == "":
-        return ()
-    names = [n.strip() for n in value.split(",")] if isinstance(value, str) else None
-    if not names or any(n not in FLOW_OUTPUTS for n in names) or len(set(names)) != len(names):
-        raise ValueError(f"settings.flow_outputs must be a comma-separated list of {FLOW_OUTPUTS} without repeats, got {value!r}")
-    return tuple(n for n in FLOW_OUTPUTS if n in names)
-
-
 def write_flow_outputs(settings, logger, d, flow, h, w, outputs, huffman="fixed"):
     """The predicted map of one document (`flow` [2,G,G], what the unwarp tail consumed) under pred_flow/ (DESIGN.md 4.12):
     'png' flow_<stem>.png, the colour-wheel picture of its displacement at the page's size h x w with norm 'max', and one log
     line with the largest radius; 'flo' flow_<stem>.flo, that displacement; 'npy' flow_<stem>.npy, the coarse map itself -
     what ops.unwarp_u8 needs to redo the page."""
-    from utils_flow.visualization_utils import _stem
-    out_dir = f"vis_hp/{settings.env.eval_dataset_name}/{settings.name}/pred_flow"
+    out_dir = f"{run_dir(settings)}/pred_flow"
     os.makedirs(out_dir, exist_ok=True)
-    name = d["path"] if os.path.splitext(d["path"])[1] else d["path"] + ".png"
-    base = f"{out_dir}/flow_{_stem([name])}"
+    base = f"{out_dir}/flow_{page_stem(d['path'])}"
     flow = flow.detach().float().contiguous()
     if "png" in outputs:
         _, largest = ops.flow_picture_to_file(flow, h, w, base + ".png", norm="max", huffman=huffman, return_radius=True)
@@ -402,21 +397,6 @@ def write_flow_outputs(settings, logger, d, flow, h, w, outputs, huffman="fixed"
         ops.flow_write_flo(flow, h, w, base + ".flo")
     if "npy" in outputs:
         np.save(base + ".npy", flow.cpu().numpy())
-
-
-MAP_SCORE_LOGGED = ("epe", "pck1", "pck5", "fl", "ause_epe")                 # the per-document log line, in this order
-MAP_SCORE_COLUMNS = ("epe", "epe_std", "pck1", "pck3", "pck5", "fl", "n_valid", "ause_epe", "ause_pck1", "ause_pck5")   # map_score.txt
-
-
-def gt_map_dir_of(settings):
-    """`settings.gt_map_dir` (run_sampling.py --gt_map_dir): the directory of ground-truth maps, absent or "" -> None (nothing
-    is scored).  Anything but a string, or a directory that does not exist, is a ValueError that names the attribute."""
-    value = getattr(settings, "gt_map_dir", "")
-    if isinstance(value, str) and value == "":
-        return None
-    if not isinstance(value, str) or not os.path.isdir(value):
-        raise ValueError(f"settings.gt_map_dir must be an existing directory (or \"\" for none), got {value!r}")
-    return value
 
 
 def gt_map_candidates(path):
@@ -461,51 +441,8 @@ def score_against_gt_maps(settings, logger, batch, flow, hyps, outs, gt_map_dir)
         if mine is None:
             logger.info(f"{path} map_score: one hypothesis, no spread: sparsification skipped")
         score = ops.map_score(flow[j].detach().float().contiguous(), gt, mine, size=size)
-        logger.info(f"{path} map_score " + " ".join(f"{k} {score[k]:.6f}" if k in score else f"{k} -" for k in MAP_SCORE_LOGGED))
+        logger.info(f"{path} map_score " + " ".join(f"{k} {SCORE['map_score'].cell(score, k)}" for k in MAP_SCORE_LOGGED))
         settings.map_score.append((path, score))
-
-
-def map_score_means(scores, keys=MAP_SCORE_COLUMNS):
-    """{key: mean over the documents that have a finite value for it} of settings.map_score."""
-    means = {}
-    for k in keys:
-        values = [float(s[k]) for _, s in scores if k in s and np.isfinite(s[k])]
-        if values:
-            means[k] = sum(values) / len(values)
-    return means
-
-
-def summarize_map_score(settings, logger, documents):
-    """The end of a round under settings.gt_map_dir: map_score.txt beside the round's other score files, and the means."""
-    scores = settings.map_score
-    with open(f"vis_hp/{settings.env.eval_dataset_name}/{settings.name}/map_score.txt", "w") as f:
-        f.write("path " + " ".join(MAP_SCORE_COLUMNS) + "\n")
-        for path, s in scores:
-            f.write(f"{path} " + " ".join((f"{s[k]}" if k == "n_valid" else f"{s[k]:.6f}") if k in s else "-" for k in MAP_SCORE_COLUMNS) + "\n")
-    if scores:
-        for k, mean in map_score_means(scores, MAP_SCORE_LOGGED).items():
-            logger.info(f"mean {k} {mean:.6f} over {sum(1 for _, s in scores if k in s and np.isfinite(s[k]))} of {documents} documents")
-    else:
-        logger.info(f"mean map_score: no document of {documents} has a ground-truth map in {settings.gt_map_dir}")
-
-
-INVERSE_OUTPUTS = ("mesh", "flo", "mask")     # what settings.inverse_outputs may name
-MAP_INVERSE_LOGGED = ("covered", "fold_px", "flipped", "skipped", "cycle_mean", "cycle_max")     # the per-document log line
-MAP_INVERSE_COLUMNS = ("covered", "fold_px", "flipped", "degenerate", "skipped", "tris", "cycle_mean", "cycle_max", "fold", "cycle")
-_INVERSE_INTEGERS = ("covered", "fold_px", "flipped", "degenerate", "skipped", "tris")
-
-
-def inverse_outputs_of(settings):
-    """`settings.inverse_outputs` (run_sampling.py --inverse_outputs): a comma-separated list of INVERSE_OUTPUTS names without
-    repeats -> the names, in the order of INVERSE_OUTPUTS.  Absent or "" means none: nothing is inverted.  Anything else is a
-    ValueError that names the attribute."""
-    value = getattr(settings, "inverse_outputs", "")
-    if isinstance(value, str) and value == "":
-        return ()
-    names = [n.strip() for n in value.split(",")] if isinstance(value, str) else None
-    if not names or any(n not in INVERSE_OUTPUTS for n in names) or len(set(names)) != len(names):
-        raise ValueError(f"settings.inverse_outputs must be a comma-separated list of {INVERSE_OUTPUTS} without repeats, got {value!r}")
-    return tuple(n for n in INVERSE_OUTPUTS if n in names)
 
 
 def _photograph_u8(d, device):
@@ -520,13 +457,10 @@ def write_inverse_outputs(settings, logger, batch, flow, outs, outputs, device, 
     photograph's size (ops.map_invert, ops.map_cycle_error), with one log line and an entry (path, dict) of
     `settings.map_inverse`; under pred_flow/ 'mesh' writes mesh_<stem>.png, the page mesh on the photograph, 'flo'
     inv_<stem>.flo, the forward displacement (1e10 where the page does not reach), 'mask' mask_<stem>.png, 255 where it does."""
-    from utils_flow.visualization_utils import _stem
-    out_dir = f"vis_hp/{settings.env.eval_dataset_name}/{settings.name}/pred_flow"
+    out_dir = f"{run_dir(settings)}/pred_flow"
     os.makedirs(out_dir, exist_ok=True)
     for j, (d, out) in enumerate(zip(batch, outs)):
-        path = d["path"]
-        name = path if os.path.splitext(path)[1] else path + ".png"
-        stem = _stem([name])
+        path, stem = d["path"], page_stem(d["path"])
         h, w = int(out.shape[0]), int(out.shape[1])
         mine = flow[j].detach().float().contiguous()
         fwd, stats = ops.map_invert(mine, h, w)
@@ -535,8 +469,7 @@ def write_inverse_outputs(settings, logger, batch, flow, outs, outputs, device, 
                  "degenerate": stats["degenerate_tris"], "skipped": stats["skipped_tris"], "tris": stats["tris"],
                  "cycle_mean": cycle["cycle_mean"], "cycle_max": cycle["cycle_max"],
                  "fold": stats["fold_px"] / stats["covered"] if stats["covered"] else float("nan"), "cycle": cycle["cycle_mean"]}
-        logger.info(f"{path} map_inverse " + " ".join(f"{k} {score[k]}" if k in _INVERSE_INTEGERS else f"{k} {score[k]:.6f}"
-                                                      for k in MAP_INVERSE_LOGGED))
+        logger.info(f"{path} map_inverse " + " ".join(f"{k} {SCORE['map_inverse'].cell(score, k)}" for k in MAP_INVERSE_LOGGED))
         settings.map_inverse.append((path, score))
         if "mesh" in outputs:
             ops.mesh_overlay_to_file(_photograph_u8(d, device), fwd, f"{out_dir}/mesh_{stem}.png", huffman=huffman)
@@ -544,22 +477,6 @@ def write_inverse_outputs(settings, logger, batch, flow, outs, outputs, device, 
             ops.inverse_write_flo(fwd, f"{out_dir}/inv_{stem}.flo")
         if "mask" in outputs:
             ops.png_encode_to_file(ops.coverage_mask(fwd), f"{out_dir}/mask_{stem}.png", huffman)
-
-
-def map_inverse_means(scores, keys=MAP_INVERSE_COLUMNS):
-    """{key: mean over the documents that have a finite value for it} of settings.map_inverse."""
-    return map_score_means(scores, keys)
-
-
-def summarize_map_inverse(settings, logger, documents):
-    """The end of a round under settings.inverse_outputs: map_inverse.txt beside the round's other score files, and the means."""
-    scores = settings.map_inverse
-    with open(f"vis_hp/{settings.env.eval_dataset_name}/{settings.name}/map_inverse.txt", "w") as f:
-        f.write("path " + " ".join(MAP_INVERSE_COLUMNS) + "\n")
-        for path, s in scores:
-            f.write(f"{path} " + " ".join(f"{s[k]}" if k in _INVERSE_INTEGERS else f"{s[k]:.6f}" for k in MAP_INVERSE_COLUMNS) + "\n")
-    for k, mean in map_inverse_means(scores, ("fold", "cycle_mean", "cycle_max")).items():
-        logger.info(f"mean map_inverse {k} {mean:.6f} over {sum(1 for _, s in scores if np.isfinite(s[k]))} of {documents} documents")
 
 
 def emit(settings, logger, batch, outs, results, opts, device, *, flow=None, flow_outputs=()):
@@ -571,105 +488,93 @@ def emit(settings, logger, batch, outs, results, opts, device, *, flow=None, flo
             write_flow_outputs(settings, logger, d, flow[j], int(out.shape[0]), int(out.shape[1]), flow_outputs, opts.png_huffman)
         if settings.env.visualize:
             from utils_flow.visualization_utils import visualize_dewarping
-            name = d["path"] if os.path.splitext(d["path"])[1] else d["path"] + ".png"
-            visualize_dewarping(settings, None, d, len(results) - 1, None, [name], warped_u8=out)
+            visualize_dewarping(settings, None, d, len(results) - 1, None, [page_name(d["path"])], warped_u8=out)
         if opts.gt_dir:
             _score_against_gt(settings, logger, d["path"], out, device, opts)
 
 
-def summarize(settings, logger, opts, times, results):
-    """The end of a run: the timing, and per metric of env.gt_dir its <name>.txt and the mean."""
+def enabled_scores(opts, round_opts):
+    """The rows of SCORES that this round keeps: the metrics env.gt_dir scores, and the kinds whose round switch is on."""
+    metrics = opts.gt_metrics if opts.gt_dir else ()
+    return [kind for kind in SCORES if (kind.name in metrics if kind.switch is None else getattr(round_opts, kind.switch))]
+
+
+def write_score_sheet(settings, logger, kind, documents):
+    """The end of a round for one score kind: `settings.<kind.name>` as <kind.name>.txt in the run's directory - one line per
+    scored document, under a header when the values are dicts - and its means over the scored of `documents` documents."""
+    scores = getattr(settings, kind.name)
+    with open(f"{run_dir(settings)}/{kind.name}.txt", "w") as f:
+        if kind.columns:
+            f.write("path " + " ".join(kind.columns) + "\n")
+        for path, value in scores:
+            f.write(f"{path} " + " ".join(kind.cell(value, k) for k in kind.columns or (kind.name,)) + "\n")
+    if not scores and kind.none:
+        logger.info(f"mean {kind.name}: no document of {documents} has {kind.none.format(settings=settings)}")
+    for k, mean in kind.means(scores, kind.mean_keys).items():
+        logger.info(f"{kind.mean_words}{k} {mean:.6f} over {len(kind.values(scores, k))} of {documents} documents")
+
+
+def summarize(settings, logger, kinds, times, documents, clean):
+    """The end of a round: the timing, then the sheet and the means of every score kind the round kept."""
     if times:
         print(len(times))
         print("Elapsed time:{:.2f} avg_second ".format(sum(times) / len(times)))
-    for name in opts.gt_metrics if opts.gt_dir else ():
-        scores = getattr(settings, name)
-        with open(f"vis_hp/{settings.env.eval_dataset_name}/{settings.name}/{name}.txt", "w") as f:
-            for path, value in scores:
-                f.write(f"{path} {value:.6f}\n")
-        if scores:
-            mean = sum(v for _, v in scores) / len(scores)
-            logger.info(f"mean {name} {mean:.6f} over {len(scores)} of {len(results)} documents")
-        else:
-            logger.info(f"mean {name}: no document of {len(results)} has a ground truth in {opts.gt_dir}")
-
-
-def summarize_map_deviation(settings, logger, documents):
-    """The end of a scored round under settings.keyed_noise: map_dev.txt beside the round's other score files, and the mean."""
-    scores = settings.map_dev
-    with open(f"vis_hp/{settings.env.eval_dataset_name}/{settings.name}/map_dev.txt", "w") as f:
-        for path, value in scores:
-            f.write(f"{path} {value:.6f}\n")
-    if scores:
-        mean = sum(v for _, v in scores) / len(scores)
-        logger.info(f"mean map_dev {mean:.6f} over {len(scores)} of {documents} documents")
-    else:
-        logger.info(f"mean map_dev: no document of {documents} has a reference map from a clean round")
+    for kind in kinds:
+        if kind.clean_rounds or not clean or getattr(settings, kind.name):
+            write_score_sheet(settings, logger, kind, documents)
 
 
 def run_evaluation_docunet(settings, logger, val_loader, diffusion, model, pretrained_dewarp_model,
                            pretrained_line_seg_model=None, pretrained_seg_model=None):
     """Document loop with the reference's positional signature (evaluation.py:142-327; call site val_TDiff.py:103-104).
     `val_loader` yields the reference's dicts or this package's documents (`documents_of`); env.batch_docs of them go through
-    each pass (the reference: 1): adopt, ingest + pre-stage nets (:162-216), the sampler (:247-265), the unwarp tail, then the
-    picture and the scores.  The engine-side switches (dvd_amd/run_options.py) are read and checked once, before the loader is
-    touched and before anything is written; so are settings.severity / corruption_number, settings.keyed_noise
-    (4.11: the sampler's noise keyed per document, reference maps kept and later rounds scored with map_dev) and
-    settings.flow_outputs (4.12: every document's predicted map written under pred_flow/) and settings.gt_map_dir (4.13: every
-    document that has a ground-truth map there is scored: EPE, PCK, Fl, AUSE) and settings.inverse_outputs (4.14: every document's
-    map inverted on the device: mesh picture, forward field, coverage mask, fold count, cycle error).  The pre-stage models
-    may all be None when every document carries ready
-    conditioning tensors.  Returns [(path, uint8 [H,W,3] device tensor)] (the reference returns None)."""
+    each pass (the reference: 1): adopt, ingest + pre-stage nets (:162-216, with the corruption stage between them), the sampler
+    (:247-265), the map deviation, the unwarp tail, the map score, the map inverse, then per document the map files, the picture
+    and the env.gt_dir metrics.  Every switch - env.* (RunOptions), settings.severity / corruption_number, then the round's own
+    (RoundOptions) - is read and checked once, before the loader is touched and before anything is written; one that is absent
+    or off calls nothing, writes nothing and logs nothing.  The round's scores (run_options.SCORES) start empty and end as
+    score sheets beside the pictures.  The pre-stage models may all be None when every document carries ready conditioning
+    tensors.  Returns [(path, uint8 [H,W,3] device tensor)] (the reference returns None)."""
     opts = RunOptions.from_env(settings.env)
     corruption = corruption_of(settings)
-    keyed = {"keyed_noise": True} if keyed_noise_of(settings) else {}    # absent or False: sample_batch is called as it always was
-    outputs = flow_outputs_of(settings)         # absent or "": emit is called as it always was
-    gt_map_dir = gt_map_dir_of(settings)        # absent or "": sample_batch returns what it always did, nothing more is launched
-    hypotheses = {"keep_hypotheses": True} if gt_map_dir else {}
-    inverse = inverse_outputs_of(settings)      # absent or "": no map is inverted, no file, the same log
-    stage = {}                                  # nothing corrupted: prepare_conditioning is called exactly as it always was
+    round_opts = RoundOptions.from_settings(settings)
+    # what is absent or off adds no keyword: the stages are called exactly as they were before the switch existed
+    stage, sampling = {}, {}
     if corruption is not None:
         logger.info(f"corruption {corruption[0]} ({ops.CORRUPTIONS[corruption[0]]}) severity {corruption[1]}")
         stage["corrupt"] = (*corruption, getattr(settings, "seed", 0))
+    if round_opts.keyed_noise:
+        sampling["keyed_noise"] = True
+    if round_opts.gt_map_dir:
+        sampling["keep_hypotheses"] = True      # the map score's spread needs the per-sample maps
     device = next(model.parameters()).device
     nets = (pretrained_dewarp_model, pretrained_seg_model, pretrained_line_seg_model)
     prestage_models = None if all(m is None for m in nets) else nets
-    os.makedirs(f"vis_hp/{settings.env.eval_dataset_name}/{settings.name}", exist_ok=True)
-    for name in opts.gt_metrics if opts.gt_dir else ():
-        setattr(settings, name, [])
-    if keyed:
-        settings.map_dev = []                   # a round's scores are its own; the reference maps outlive the round
-        if not isinstance(getattr(settings, "map_ref", None), dict):
-            settings.map_ref = {}
-    if gt_map_dir:
-        settings.map_score = []
-    if inverse:
-        settings.map_inverse = []
+    os.makedirs(run_dir(settings), exist_ok=True)
+    kinds = enabled_scores(opts, round_opts)
+    for kind in kinds:
+        setattr(settings, kind.name, [])        # a round's scores are its own; the reference maps outlive the round
+    if round_opts.keyed_noise and not isinstance(getattr(settings, "map_ref", None), dict):
+        settings.map_ref = {}
     times, results = [], []
     for batch in batches_of(val_loader, opts.batch_docs):
         adopt_reference_items(batch, device)
         prepare_conditioning(batch, device, opts.grid_size, prestage_models, bool(settings.env.use_init_flow),
                              decode_png=opts.png_decoder == "hip", **stage)
         t0 = time.time()
-        flow = sample_batch(settings, logger, diffusion, model, batch, opts.grid_size, device, **keyed, **hypotheses)
-        if gt_map_dir:
+        flow = sample_batch(settings, logger, diffusion, model, batch, opts.grid_size, device, **sampling)
+        if round_opts.gt_map_dir:
             flow, hyps = flow
         th.cuda.synchronize()
         times.append((time.time() - t0) / len(batch))
-        if keyed:
+        if round_opts.keyed_noise:
             score_map_deviation(settings, logger, batch, flow, clean=corruption is None)
         outs = unwarp_tail(batch, flow, opts.unwarp_mode, device)
-        if gt_map_dir:
-            score_against_gt_maps(settings, logger, batch, flow, hyps, outs, gt_map_dir)
-        if inverse:
-            write_inverse_outputs(settings, logger, batch, flow, outs, inverse, device, opts.png_huffman)
-        maps = {"flow": flow, "flow_outputs": outputs} if outputs else {}
+        if round_opts.gt_map_dir:
+            score_against_gt_maps(settings, logger, batch, flow, hyps, outs, round_opts.gt_map_dir)
+        if round_opts.inverse_outputs:
+            write_inverse_outputs(settings, logger, batch, flow, outs, round_opts.inverse_outputs, device, opts.png_huffman)
+        maps = {"flow": flow, "flow_outputs": round_opts.flow_outputs} if round_opts.flow_outputs else {}
         emit(settings, logger, batch, outs, results, opts, device, **maps)
-    summarize(settings, logger, opts, times, results)
-    if keyed and (corruption is not None or settings.map_dev):
-        summarize_map_deviation(settings, logger, len(results))
-    if gt_map_dir:
-        summarize_map_score(settings, logger, len(results))
-    if inverse:
-        summarize_map_inverse(settings, logger, len(results))
+    summarize(settings, logger, kinds, times, len(results), clean=corruption is None)
     return results

@@ -1006,7 +1006,7 @@ def ad_u8(pred_hwc_u8: torch.Tensor, gt_hwc_u8: torch.Tensor, area: int = MSSSIM
     return float(aligned_distortion(y, x, **params)[0][0])
 
 
-GT_METRIC_NAMES = run_options.GT_METRICS + ("ad",)
+GT_METRIC_NAMES = tuple(kind.name for kind in run_options.SCORES if kind.switch is None)     # ms_ssim, ld, ad
 
 
 def gt_metrics_u8(pred_hwc_u8: torch.Tensor, gt_hwc_u8: torch.Tensor, metrics, preset: str = "docunet",

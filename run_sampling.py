@@ -67,29 +67,21 @@ def write_corruption_table(path, rows, metrics):
     return text
 
 
-MAP_DEV = "map_dev"        # the table's column under --keyed_noise, after the env.gt_dir metrics
-MAP_SCORE = "map_score"    # settings.map_score under --gt_map_dir: [(path, dict)]
-MAP_SCORE_COLUMNS = ("epe", "pck5", "ause_epe")   # ... and the table's columns from it, after every other one
-MAP_INVERSE = "map_inverse"                       # settings.map_inverse under --inverse_outputs: [(path, dict)]
-MAP_INVERSE_COLUMNS = ("fold", "cycle")           # ... and the table's last columns: fold_px / covered and cycle_mean
-
-
 def run_sampling(train_module, train_name, seed, name, cudnn_benchmark=True, corruption=False, severity=None,
                  corruption_number=None, *, keyed_noise=False, flow_outputs="", gt_map_dir="", inverse_outputs=""):
     from dvd_amd import ops
+    from dvd_amd.evaluation import run_dir
+    from dvd_amd.run_options import ROUND_TABLE, SCORES
     print(f"Sampling:  {train_module}  {train_name}\nDate: {date.today().strftime('%d/%m/%Y')}")
     settings = ws_settings.Settings()
     settings.module_name, settings.script_name = train_module, train_name
     settings.project_path = f"train_settings/{train_module}/{train_name}"
     settings.seed, settings.name = seed, name
-    if keyed_noise:                                           # absent without the flag: the run is what it always was
-        settings.keyed_noise = True
-    if flow_outputs:                                          # likewise: "" leaves the attribute absent
-        settings.flow_outputs = flow_outputs
-    if gt_map_dir:                                            # likewise
-        settings.gt_map_dir = gt_map_dir
-    if inverse_outputs:                                       # likewise
-        settings.inverse_outputs = inverse_outputs
+    flags = {"keyed_noise": keyed_noise, "flow_outputs": flow_outputs, "gt_map_dir": gt_map_dir, "inverse_outputs": inverse_outputs}
+    for switch in ROUND_TABLE:                                # absent without the flag: the run is what it always was
+        if flags[switch.name]:
+            setattr(settings, switch.name, flags[switch.name])
+    scores = [score for score in SCORES if score.switch is None or flags[score.switch]]   # the env.gt_dir metrics, and what the flags add
     save_dir = os.path.join(settings.env.workspace_dir, settings.project_path)
     os.makedirs(save_dir, exist_ok=True)
     shutil.copyfile(settings.project_path + ".py", os.path.join(save_dir, settings.script_name + ".py"))
@@ -113,24 +105,19 @@ def run_sampling(train_module, train_name, seed, name, cudnn_benchmark=True, cor
             print(f"corruption {number} ({kind}): no device kernel, round skipped")
             continue
         settings.severity, settings.corruption_number, settings.name = sev, number, round_name(name, sev, number)
-        for metric in ops.GT_METRIC_NAMES + (MAP_DEV, MAP_SCORE, MAP_INVERSE):   # a round's scores are its own
-            if hasattr(settings, metric):
-                delattr(settings, metric)
+        for score in SCORES:                                  # a round's scores are its own
+            if hasattr(settings, score.name):
+                delattr(settings, score.name)
         run(settings)
-        means = {m: sum(v for _, v in getattr(settings, m)) / len(getattr(settings, m))
-                 for m in ops.GT_METRIC_NAMES + ((MAP_DEV,) if keyed_noise else ()) if getattr(settings, m, None)}
-        if gt_map_dir:
-            from dvd_amd.evaluation import map_score_means
-            means.update(map_score_means(getattr(settings, MAP_SCORE, None) or [], MAP_SCORE_COLUMNS))
-        if inverse_outputs:
-            from dvd_amd.evaluation import map_inverse_means
-            means.update(map_inverse_means(getattr(settings, MAP_INVERSE, None) or [], MAP_INVERSE_COLUMNS))
+        means = {}
+        for score in scores:
+            means.update(score.means(getattr(settings, score.name, None) or [], score.table_columns))
         rows.append((number, kind, sev, means))
     settings.name = name
     if rows:
-        metrics = [m for m in ops.GT_METRIC_NAMES if any(m in r[3] for r in rows)] + ([MAP_DEV] if keyed_noise else []) + \
-            (list(MAP_SCORE_COLUMNS) if gt_map_dir else []) + (list(MAP_INVERSE_COLUMNS) if inverse_outputs else [])
-        write_corruption_table(os.path.join("vis_hp", str(settings.env.eval_dataset_name), name, "corruption_table.txt"), rows, metrics)
+        # the ground-truth metrics that some row has, then every column of the kinds the flags enable, valued or not
+        metrics = [c for score in scores for c in score.table_columns if score.switch or any(c in means for *_, means in rows)]
+        write_corruption_table(os.path.join(run_dir(settings), "corruption_table.txt"), rows, metrics)
 
 
 def main():

@@ -297,13 +297,18 @@ def _exploding_loader():
     yield                                                                          # pragma: no cover
 
 
+def _flow_outputs_of(settings):
+    from dvd_amd import evaluation
+    return evaluation.RoundOptions.from_settings(settings).flow_outputs
+
+
 def test_flow_outputs_parsing():
     from dvd_amd import evaluation
     assert evaluation.FLOW_OUTPUTS == ("png", "flo", "npy")
-    assert evaluation.flow_outputs_of(_settings()) == () and evaluation.flow_outputs_of(_settings(flow_outputs="")) == ()
-    assert evaluation.flow_outputs_of(_settings(flow_outputs="png")) == ("png",)
-    assert evaluation.flow_outputs_of(_settings(flow_outputs="npy, png")) == ("png", "npy")
-    assert evaluation.flow_outputs_of(_settings(flow_outputs="flo,npy,png")) == ("png", "flo", "npy")
+    assert _flow_outputs_of(_settings()) == () and _flow_outputs_of(_settings(flow_outputs="")) == ()
+    assert _flow_outputs_of(_settings(flow_outputs="png")) == ("png",)
+    assert _flow_outputs_of(_settings(flow_outputs="npy, png")) == ("png", "npy")
+    assert _flow_outputs_of(_settings(flow_outputs="flo,npy,png")) == ("png", "flo", "npy")
 
 
 def test_a_bad_flow_outputs_is_refused_before_the_loader_is_read(tmp_path, monkeypatch):
@@ -342,7 +347,7 @@ def _emit(monkeypatch, tmp_path, **attrs):
     batch = [{"path": "a.png"}, {"path": "dir/b_1 copy.jpg"}, {"path": "synthetic_00002"}]
     outs = [torch.zeros(6, 4, 3, dtype=torch.uint8)] * 3
     flow = torch.arange(3 * 2 * 8 * 8, dtype=torch.float32).reshape(3, 2, 8, 8)
-    extra = {"flow": flow, "flow_outputs": evaluation.flow_outputs_of(s)} if evaluation.flow_outputs_of(s) else {}
+    extra = {"flow": flow, "flow_outputs": _flow_outputs_of(s)} if _flow_outputs_of(s) else {}
     evaluation.emit(s, types.SimpleNamespace(info=lines.append), batch, outs, results, RunOptions.from_env(s.env), "cpu", **extra)
     assert [p for p, _ in results] == [d["path"] for d in batch]
     return spy, lines, flow

@@ -367,10 +367,12 @@ def _exploding_loader():
 def test_inverse_outputs_parsing():
     from dvd_amd import evaluation
     assert evaluation.INVERSE_OUTPUTS == ("mesh", "flo", "mask")
-    assert evaluation.inverse_outputs_of(_settings()) == () and evaluation.inverse_outputs_of(_settings(inverse_outputs="")) == ()
-    assert evaluation.inverse_outputs_of(_settings(inverse_outputs="mask")) == ("mask",)
-    assert evaluation.inverse_outputs_of(_settings(inverse_outputs="mask, mesh")) == ("mesh", "mask")
-    assert evaluation.inverse_outputs_of(_settings(inverse_outputs="flo,mask,mesh")) == ("mesh", "flo", "mask")
+    def read(settings):
+        return evaluation.RoundOptions.from_settings(settings).inverse_outputs
+    assert read(_settings()) == () and read(_settings(inverse_outputs="")) == ()
+    assert read(_settings(inverse_outputs="mask")) == ("mask",)
+    assert read(_settings(inverse_outputs="mask, mesh")) == ("mesh", "mask")
+    assert read(_settings(inverse_outputs="flo,mask,mesh")) == ("mesh", "flo", "mask")
 
 
 def test_a_bad_inverse_outputs_is_refused_before_the_loader_is_read(tmp_path, monkeypatch):

@@ -282,8 +282,9 @@ def test_a_bad_gt_map_dir_is_refused_before_the_loader_is_read(tmp_path, monkeyp
         with pytest.raises(ValueError, match="settings.gt_map_dir"):
             evaluation.run_evaluation_docunet(_settings(gt_map_dir=value), LOG, _exploding_loader(), None, torch.nn.Linear(1, 1), None)
     assert list(tmp_path.iterdir()) == []
-    assert evaluation.gt_map_dir_of(_settings()) is None and evaluation.gt_map_dir_of(_settings(gt_map_dir="")) is None
-    assert evaluation.gt_map_dir_of(_settings(gt_map_dir=str(tmp_path))) == str(tmp_path)
+    read = evaluation.RoundOptions.from_settings
+    assert read(_settings()).gt_map_dir is None and read(_settings(gt_map_dir="")).gt_map_dir is None
+    assert read(_settings(gt_map_dir=str(tmp_path))).gt_map_dir == str(tmp_path)
 
 
 def test_no_new_env_switch():
@@ -407,7 +408,7 @@ def test_documents_are_scored_logged_and_summarised(tmp_path, monkeypatch):
     s.map_score.pop()
     os.makedirs("vis_hp/synthetic/pytest_mapscore")
     lines.clear()
-    evaluation.summarize_map_score(s, log, 3)
+    evaluation.write_score_sheet(s, log, evaluation.SCORE["map_score"], 3)
     text = (tmp_path / "vis_hp/synthetic/pytest_mapscore/map_score.txt").read_text().splitlines()
     assert text[0] == "path " + " ".join(evaluation.MAP_SCORE_COLUMNS) and text[1].startswith("a 0.000000 0.000000 1.000000") and len(text) == 3
     assert lines[0] == f"mean epe {b['epe'] / 2:.6f} over 2 of 3 documents" and [ln.split()[1] for ln in lines] == list(evaluation.MAP_SCORE_LOGGED)

@@ -337,7 +337,8 @@ def test_a_flag_that_is_no_bool_is_refused_before_the_loader_is_read(tmp_path, m
         with pytest.raises(ValueError, match="settings.keyed_noise"):
             evaluation.run_evaluation_docunet(_settings(keyed_noise=flag), LOG, _exploding_loader(), None, torch.nn.Linear(1, 1), None)
     assert list(tmp_path.iterdir()) == []
-    assert evaluation.keyed_noise_of(_settings()) is False and evaluation.keyed_noise_of(_settings(keyed_noise=True)) is True
+    read = evaluation.RoundOptions.from_settings
+    assert read(_settings()).keyed_noise is False and read(_settings(keyed_noise=True)).keyed_noise is True
 
 
 def test_the_loop_refuses_a_key_list_of_the_wrong_length_or_shape():

@@ -1,5 +1,6 @@
 """The engine-side switches (dvd_amd/run_options.py) without a GPU: the defaults, one parse, and - for every switch and every bad
-value - a refusal before the loader is read and before anything is written."""
+value - a refusal before the loader is read and before anything is written.  The same for the round's switches, the attributes
+the launcher puts on `settings` itself."""
 import dataclasses
 import os
 import subprocess
@@ -11,7 +12,7 @@ import torch
 
 import admin.settings as ws
 from dvd_amd import logger
-from dvd_amd.run_options import TABLE, PageOptions, RunOptions
+from dvd_amd.run_options import ROUND_TABLE, TABLE, PageOptions, RoundOptions, RunOptions
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -127,6 +128,94 @@ def test_of_two_bad_values_the_earlier_one_is_reported(tmp_path, monkeypatch):
             with pytest.raises(ValueError, match=f"env.{first}"):
                 PageOptions.from_env(_settings(**{first: BAD[first][1][0], second: BAD[second][1][0]}).env)
     assert list(tmp_path.iterdir()) == []
+
+
+# ---- the round's switches: what the launcher puts on `settings` itself (ROUND_TABLE) ---------------------------------------------
+ROUND_DEFAULTS = {"keyed_noise": False, "flow_outputs": "", "gt_map_dir": "", "inverse_outputs": ""}     # written out, as above
+ROUND_PARSED = {"keyed_noise": False, "flow_outputs": (), "gt_map_dir": None, "inverse_outputs": ()}
+# switch -> (the message, the bad values); in the order the values are checked
+ROUND_BAD = {
+    "keyed_noise": ("settings.keyed_noise must be True or False, got ", (1, 0, "yes", None, 1.0)),
+    "flow_outputs": ("settings.flow_outputs must be a comma-separated list of ('png', 'flo', 'npy') without repeats, got ",
+                     ("jpg", "png,png", "png,", ",", " ", "PNG", None, True, 3, ("png",), ["png"])),
+    "gt_map_dir": ("settings.gt_map_dir must be an existing directory (or \"\" for none), got ",
+                   (1, None, True, ["maps"], "missing", b"maps")),
+    "inverse_outputs": ("settings.inverse_outputs must be a comma-separated list of ('mesh', 'flo', 'mask') without repeats, got ",
+                        ("png", "mesh,mesh", "mesh,", ",", " ", "MESH", None, True, 3, ("mesh",), ["mesh"])),
+}
+ROUND_CASES = [pytest.param(key, value, id=f"{key}-{value!r}") for key, (_, values) in ROUND_BAD.items() for value in values]
+
+
+def _round_settings(env=None, **attrs):
+    s = _settings(**(env or {}))
+    for key, value in attrs.items():
+        setattr(s, key, value)
+    return s
+
+
+@pytest.mark.parametrize("key,value", ROUND_CASES)
+def test_bad_round_value_is_refused(tmp_path, monkeypatch, key, value):
+    """By run_evaluation_docunet, before the loader is read and before anything is written; the whole message."""
+    monkeypatch.chdir(tmp_path)
+    s = _round_settings(**{key: value})
+    assert _refused(s, "settings.") == ROUND_BAD[key][0] + repr(value)
+    with pytest.raises(ValueError) as e:
+        RoundOptions.from_settings(s)
+    assert str(e.value) == ROUND_BAD[key][0] + repr(value)
+    assert list(tmp_path.iterdir()) == []
+
+
+def test_every_checked_round_switch_has_bad_values():
+    assert [s.name for s in ROUND_TABLE if s.accepts is not None] == list(ROUND_BAD) == list(ROUND_DEFAULTS)
+    assert {f.name for f in dataclasses.fields(RoundOptions)} == set(ROUND_DEFAULTS)
+    assert not {s.name for s in ROUND_TABLE} & {s.name for s in TABLE}
+
+
+def test_round_defaults_are_the_literal_ones(tmp_path):
+    assert {s.name: s.default for s in ROUND_TABLE} == ROUND_DEFAULTS and all(s.doc and s.owner == "settings" for s in ROUND_TABLE)
+    assert all(s.owner == "env" for s in TABLE)
+    assert not any(hasattr(ws.Settings(), name) for name in ROUND_DEFAULTS)              # the launcher leaves them absent
+    assert dataclasses.asdict(RoundOptions.from_settings(ws.Settings())) == ROUND_PARSED
+    assert RoundOptions.from_settings(_round_settings(**ROUND_DEFAULTS)) == RoundOptions.from_settings(ws.Settings())
+    given = RoundOptions.from_settings(_round_settings(keyed_noise=np.True_, flow_outputs="npy, png", gt_map_dir=str(tmp_path),
+                                                       inverse_outputs="mask,mesh"))
+    assert dataclasses.astuple(given) == (True, ("png", "npy"), str(tmp_path), ("mesh", "mask")) and type(given.keyed_noise) is bool
+    with pytest.raises(dataclasses.FrozenInstanceError):
+        given.keyed_noise = False
+
+
+@pytest.mark.parametrize("name", list(ROUND_DEFAULTS))
+def test_an_absent_round_attribute_means_its_default(name):
+    s = _round_settings(keyed_noise=True, flow_outputs="png", gt_map_dir=ROOT, inverse_outputs="mesh")
+    delattr(s, name)
+    assert getattr(RoundOptions.from_settings(s), name) == ROUND_PARSED[name]
+
+
+def test_of_two_bad_round_values_the_earlier_one_is_reported(tmp_path, monkeypatch):
+    """The env.* switches first, then the corruption, then the round's switches in ROUND_TABLE order."""
+    monkeypatch.chdir(tmp_path)
+    order = list(ROUND_BAD)
+    for i, first in enumerate(order):
+        for second in order[i + 1:]:
+            s = _round_settings(**{first: ROUND_BAD[first][1][0], second: ROUND_BAD[second][1][0]})
+            assert f"settings.{second}" not in _refused(s, f"settings.{first}")
+    for key in order:
+        s = _round_settings({"unwarp_mode": "nearest"}, **{key: ROUND_BAD[key][1][0]})
+        assert "settings." not in _refused(s, "env.unwarp_mode must be 'bilinear' or 'bicubic'")
+        s = _round_settings(severity=9, **{key: ROUND_BAD[key][1][0]})
+        assert f"settings.{key}" not in _refused(s, "settings.severity")
+    assert list(tmp_path.iterdir()) == []
+
+
+def test_one_name_list_checker():
+    """env.gt_metrics refuses ""; the two lists of `settings` read it as none."""
+    from dvd_amd import run_options
+    check = run_options.name_list("x.names", ("a", "b", "c"))
+    assert check("c, a") == ("a", "c") and run_options.name_list("x.names", ("a", "b"), empty_is_none=True)("") == ()
+    for bad in ("", "a,a", "a,", "d", None, ("a",)):
+        with pytest.raises(ValueError) as e:
+            check(bad)
+        assert str(e.value) == f"x.names must be a comma-separated list of ('a', 'b', 'c') without repeats, got {bad!r}"
 
 
 def test_metric_preset_is_checked_only_with_gt_dir():
