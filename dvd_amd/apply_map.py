@@ -5,6 +5,13 @@
 The image is decoded by PIL, unwarped on the device by ops.unwarp_u8 - the kernel that made the run's page - and written as
 a PNG by PIL.
 
+    python -m dvd_amd.apply_map MAP.npy IMAGE OUT.png --size SPEC [--max-radius R]
+
+renders the page at a size of its own instead - SPEC is 'HxW', 'long:N' or 'xFACTOR' (ops.page_size) - through
+ops.unwarp_u8_sized, which filters the photograph by the map's footprint (bilinear only, rounded not truncated),
+and prints the three counts: pixels where the filter's radius was capped, whose centre is outside the photograph, and whose map
+value is not finite.
+
     python -m dvd_amd.apply_map MAP.npy IMAGE OUT.txt --points PTS.txt --to page|photo [--step 8]
 
 carries the N x 2 coordinates (x y per line, in pixels) of PTS.txt through the map instead: --to page takes positions on the
@@ -38,6 +45,35 @@ def apply_map(map_path, image_path, out_path, mode="bilinear"):
     page = ops.unwarp_u8(torch.from_numpy(flow).cuda(), src, mode=mode)
     Image.fromarray(page.cpu().numpy()).save(out_path)
     return page
+
+
+class SizeRequestError(ValueError):
+    """A --size or --max-radius the page cannot be rendered with: a usage error, unlike a broken map or image file."""
+
+
+def apply_map_sized(map_path, image_path, out_path, size, max_radius=16):
+    """The page at the size `size` asks for (ops.page_size); returns (page, counts) and prints the counts in one line.  A bad
+    request is refused before a file is opened."""
+    from . import ops
+    if isinstance(max_radius, bool) or not isinstance(max_radius, int) or not 1 <= max_radius <= ops.SIZED_MAX_RADIUS:
+        raise SizeRequestError(f"--max-radius must be an integer 1..{ops.SIZED_MAX_RADIUS}, got {max_radius!r}")
+    try:
+        ops.parse_page_size(size)
+    except ValueError as e:
+        raise SizeRequestError(f"--size: {e}") from None
+    flow = load_map(map_path)
+    import torch
+    from PIL import Image
+    src = torch.from_numpy(np.array(Image.open(image_path).convert("RGB"))).cuda()
+    try:
+        hp, wp = ops.page_size(int(src.shape[0]), int(src.shape[1]), size)
+    except ValueError as e:
+        raise SizeRequestError(f"--size: {image_path} is {int(src.shape[0])} x {int(src.shape[1])}: {e}") from None
+    page, counts = ops.unwarp_u8_sized(torch.from_numpy(flow[0]).cuda(), src, (hp, wp), max_radius=max_radius, return_stats=True)
+    Image.fromarray(page.cpu().numpy()).save(out_path)
+    print(f"{out_path}: {hp} x {wp} from {int(src.shape[0])} x {int(src.shape[1])}; capped {counts['capped']}, outside {counts['outside']}, "
+          f"invalid {counts['invalid']}")
+    return page, counts
 
 
 POINT_TARGETS = ("page", "photo")
@@ -95,7 +131,23 @@ def main(argv=None):
                    "a text file and IMAGE gives the size only")
     p.add_argument("--to", default="page", choices=POINT_TARGETS, help="with --points: photograph -> page (default) or page -> photo")
     p.add_argument("--step", type=int, default=8, help="with --points --to page: the mesh step of the inverse")
+    p.add_argument("--size", default=None, metavar="SPEC", help="render the page at this size: 'HxW', 'long:N' or 'xFACTOR' "
+                   "(footprint-filtered, bilinear only)")
+    p.add_argument("--max-radius", type=int, default=None, help="with --size: the filter's largest half-width in photograph pixels, "
+                   "1..16 (default 16)")
     a = p.parse_args(argv)
+    if a.size is not None:
+        if a.points is not None:
+            p.error("--size renders a page: it cannot be combined with --points")
+        if a.mode != "bilinear":
+            p.error(f"--size filters bilinearly: it cannot be combined with --mode {a.mode}")
+        try:
+            apply_map_sized(a.map, a.image, a.out, a.size, 16 if a.max_radius is None else a.max_radius)
+        except SizeRequestError as e:
+            p.error(str(e))
+        return
+    if a.max_radius is not None:
+        p.error("--max-radius needs --size")
     if a.points is not None:
         apply_points(a.map, a.image, a.out, a.points, a.to, a.step)
         return

@@ -140,6 +140,15 @@ class SynthParams(C.Structure):
     _fields_ = [(name, C.c_float) for name in ("l0", "lgx", "lgy", "k", "a_ref")]
 
 
+E_SIZED_SHAPE, E_SIZED_PARAM = -59, -60    # DVD_E_SIZED_*: what the page at a chosen size refuses
+SIZED_STATS = 3                            # DVD_SIZED_STATS: the counts of a sized unwarp (capped, outside, invalid)
+
+
+class SizedImage(C.Structure):
+    """dvd_sized_image: one document of a sized ragged batch (device pointers; the photograph's and the page's size)."""
+    _fields_ = [("src", C.c_void_p), ("out", C.c_void_p), ("hs", C.c_int), ("ws", C.c_int), ("hp", C.c_int), ("wp", C.c_int)]
+
+
 RAGGED_CAP = 64  # DVD_RAGGED_CAP: documents per launch of the ragged entry points (larger batches are cut by the library)
 
 NON_STATUS = {"dvd_last_error", "dvd_version", "dvd_engine_workspace_bytes", "dvd_engine_tensor_count",
@@ -253,6 +262,9 @@ SIGNATURES = {
     "dvd_map_points": [c_void, C.c_int, C.c_int, C.c_int, C.c_float, c_void, C.c_long, c_void, c_void],
     "dvd_synth_render_rgb8": [c_void, C.c_int, C.c_int, c_void, C.c_int, C.c_int, c_void, C.c_uint32, C.POINTER(SynthParams), c_void, c_void],
     "dvd_synth_footprint": [c_void, C.c_int, C.c_int, C.c_int, C.c_int, c_void, c_void],
+    "dvd_unwarp_u8_sized": [c_void, C.c_int, c_void, C.c_int, C.c_int, c_void, C.c_int, C.c_int, C.c_float, C.c_int, c_void, c_void],
+    "dvd_unwarp_u8_sized_ragged": [c_void, C.c_int, C.POINTER(SizedImage), C.c_int, C.c_float, C.c_int, c_void, c_void],
+    "dvd_sized_footprint": [c_void, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, c_void, c_void],
     "dvd_png_bound": [C.c_int, C.c_int],
     "dvd_png_scratch_bytes": [C.c_int, C.c_int],
     "dvd_png_encode_rgb8": [c_void, C.c_int, C.c_int, c_void, C.c_long, c_void, c_void, c_void],

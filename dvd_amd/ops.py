@@ -1935,3 +1935,160 @@ def synth_document(scan_u8: torch.Tensor, flow: torch.Tensor, h: int, w: int, st
     if shading is not None and prm["a_ref"] is None:
         prm["a_ref"] = hs * ws / stats["covered"] if stats["covered"] else 1.0
     return synth_render(scan_u8, fwd, background=background, shading=None if shading is None else prm), fwd, stats
+
+
+# ---- pages at a chosen size: the unwarp tail at any page size, filtered by its footprint (dvd_amd/csrc/sized.hip; definition:
+# DESIGN.md 4.16, tests/sized_model.py)
+SIZED_MAX_SIDE, SIZED_MAX_RADIUS = 16384, 16
+SIZED_STATS = ("capped", "outside", "invalid")
+
+
+def _size_error(spec, why):
+    return ValueError(f"page_size: {spec!r}: {why} (an (hp, wp) tuple, 'HxW', 'long:N' or 'xFACTOR'; sides 1..{SIZED_MAX_SIDE})")
+
+
+def parse_page_size(spec):
+    """A size request, checked without a photograph: ('size', hp, wp), ('long', N) or ('scale', factor).  Anything that is no
+    request is a ValueError that names the value; whether the sides it gives for a photograph are 1..16384 is page_size's to say."""
+    if isinstance(spec, (tuple, list)):
+        if len(spec) != 2 or not all(_is_int(v) for v in spec):
+            raise _size_error(spec, "a tuple must hold two integers")
+        return "size", int(spec[0]), int(spec[1])
+    if isinstance(spec, str):
+        import re
+        text = spec.strip()
+        if m := re.fullmatch(r"(\d{1,6})[xX](\d{1,6})", text):
+            return "size", int(m.group(1)), int(m.group(2))
+        if m := re.fullmatch(r"long:(\d{1,6})", text):
+            if int(m.group(1)) < 1:
+                raise _size_error(spec, "the long side must be at least 1")
+            return "long", int(m.group(1))
+        if m := re.fullmatch(r"[xX](\d{1,6}(?:\.\d{0,9})?|\.\d{1,9})", text):
+            if not float(m.group(1)) > 0:
+                raise _size_error(spec, "the factor must be positive")
+            return "scale", float(m.group(1))
+    raise _size_error(spec, "not a size request")
+
+
+def page_size(h: int, w: int, spec):
+    """The page size (hp, wp) a request asks for of a photograph of h x w.  spec: an (hp, wp) tuple of integers, or a string:
+    'HxW' - that size; 'long:N' - the long side becomes N and the other side round(N short / long), at least 1; 'x0.5' - both
+    sides times the factor, rounded, at least 1 (a half rounds up in both forms).  Every side must end in 1..16384; anything
+    else is a ValueError that names the value.  Host only."""
+    if not _is_int(h) or not _is_int(w) or h < 1 or w < 1:
+        raise ValueError(f"page_size: the photograph's size must be two positive integers, got {h!r} x {w!r}")
+    kind, *args = parse_page_size(spec)
+    if kind == "size":
+        hp, wp = args
+    elif kind == "long":
+        n = args[0]                # integer arithmetic: round(n short / long), a half rounding up
+        hp, wp = (n, max(1, (2 * n * w + h) // (2 * h))) if h >= w else (max(1, (2 * n * h + w) // (2 * w)), n)
+    else:
+        hp, wp = max(1, int(np.floor(h * args[0] + 0.5))), max(1, int(np.floor(w * args[0] + 0.5)))
+    if not 1 <= hp <= SIZED_MAX_SIDE or not 1 <= wp <= SIZED_MAX_SIDE:
+        raise _size_error(spec, f"it asks for {hp} x {wp}")
+    return hp, wp
+
+
+def _sized_size(size, name):
+    if not isinstance(size, (tuple, list)) or len(size) != 2 or not all(_is_int(v) for v in size) or \
+            not all(1 <= v <= SIZED_MAX_SIDE for v in size):
+        raise ValueError(f"{name}: size must be two integers (hp, wp) in 1..{SIZED_MAX_SIDE} (ops.page_size parses a request), got {size!r}")
+    return int(size[0]), int(size[1])
+
+
+def _sized_radius(max_radius, name):
+    if not _is_int(max_radius) or not 1 <= max_radius <= SIZED_MAX_RADIUS:
+        raise ValueError(f"{name}: max_radius must be an integer 1..{SIZED_MAX_RADIUS}, got {max_radius!r}")
+    return int(max_radius)
+
+
+def _sized_src(src_hwc, name, what="src_hwc"):
+    if not torch.is_tensor(src_hwc) or not src_hwc.is_cuda:
+        raise ValueError(f"{name}: {what} must be a [H,W,3] uint8 tensor on the device, got "
+                         f"{src_hwc.device if torch.is_tensor(src_hwc) else type(src_hwc)}")
+    if src_hwc.dtype != torch.uint8 or not src_hwc.is_contiguous():
+        raise ValueError(f"{name}: {what} must be contiguous uint8, got {src_hwc.dtype} contiguous={src_hwc.is_contiguous()}")
+    if src_hwc.dim() != 3 or src_hwc.shape[2] != 3:
+        raise ValueError(f"{name}: {what} must be [H,W,3], got {tuple(src_hwc.shape)}")
+    return _synth_sides(int(src_hwc.shape[0]), int(src_hwc.shape[1]), name, what)
+
+
+def _sized_counts(stats):
+    """[n,3] int64 on the device -> n dicts of exact integers (one copy to the host)."""
+    return [dict(zip(SIZED_STATS, (int(v) for v in row))) for row in stats.cpu().tolist()]
+
+
+def unwarp_u8_sized(flow: torch.Tensor, src_hwc: torch.Tensor, size, scale: float = 0.987, max_radius: int = 16, out: torch.Tensor = None,
+                    return_stats: bool = False):
+    """The page [hp,wp,3] uint8 of the photograph src_hwc [H,W,3] uint8 under the coarse map flow [2,G,G] (or [1,2,G,G]) at ANY
+    page size = (hp, wp), each 1..16384 (ops.page_size parses 'long:1600', 'x0.5', 'HxW').  A page pixel's position on the
+    photograph is the native tail's own grid at the page's size (size = (H, W): unwarp_u8's, bit for bit) as a signed Q8
+    number; the photograph is filtered there with an integer tent whose radii 1..max_radius follow the first differences of
+    those positions, so a minified page does not alias; radius 1 x 1 is Q8 bilinear sampling.  A tap outside the photograph
+    contributes zero (padding_mode='zeros'); a pixel whose grid value is not finite is black.  The byte is ROUNDED to nearest
+    once - unwarp_u8 truncates - so at the photograph's own size the two differ by up to 2 levels.  return_stats=True: also
+    {capped, outside, invalid}, the page pixels whose radius would have exceeded max_radius, whose centre lies outside the
+    photograph, and whose grid value is not finite: exact integers.  One launch; equal calls give equal bytes."""
+    name = "unwarp_u8_sized"
+    hp, wp = _sized_size(size, name)
+    max_radius = _sized_radius(max_radius, name)
+    cscale = _inv_scale(scale, name)
+    flow, g = _inv_flow(flow, name)
+    hs, ws = _sized_src(src_hwc, name)
+    dev = flow.device
+    if src_hwc.device != dev:
+        raise ValueError(f"{name}: src_hwc is on {src_hwc.device}, flow on {dev}")
+    out = _inv_out(out, (hp, wp, 3), torch.uint8, dev, name)
+    if out.data_ptr() < src_hwc.data_ptr() + src_hwc.numel() and src_hwc.data_ptr() < out.data_ptr() + out.numel():
+        raise ValueError(f"{name}: out must share no byte with src_hwc")
+    stats = torch.empty((1, lib.SIZED_STATS), dtype=torch.int64, device=dev) if return_stats else None
+    lib.call("dvd_unwarp_u8_sized", ptr(flow), g, ptr(src_hwc), hs, ws, ptr(out), hp, wp, cscale, max_radius, ptr(stats), stream_ptr())
+    return (out, _sized_counts(stats)[0]) if return_stats else out
+
+
+def unwarp_u8_sized_ragged(flow: torch.Tensor, srcs, sizes, scale: float = 0.987, max_radius: int = 16, return_stats: bool = False):
+    """flow [n,2,G,G]; srcs: n [H_d,W_d,3] uint8 tensors of ANY sizes; sizes: n page sizes (hp_d, wp_d) -> n uint8 pages, each the
+    bytes of unwarp_u8_sized(flow[d], srcs[d], sizes[d]): the batch's documents in ONE launch (per lib.RAGGED_CAP documents).
+    The pages are views of one allocation.  return_stats=True: also the list of the documents' counts."""
+    name = "unwarp_u8_sized_ragged"
+    max_radius = _sized_radius(max_radius, name)
+    cscale = _inv_scale(scale, name)
+    srcs, sizes = list(srcs), list(sizes)
+    _map_device(flow, "[n,2,G,G]", name, "flow")
+    if flow.dim() != 4 or flow.shape[1] != 2 or flow.shape[2] != flow.shape[3] or not NOISE_MIN_GRID <= flow.shape[2] <= NOISE_MAX_GRID:
+        raise ValueError(f"{name}: flow must be [n,2,G,G] with G {NOISE_MIN_GRID}..{NOISE_MAX_GRID}, got {tuple(flow.shape)}")
+    if flow.shape[0] != len(srcs) or len(sizes) != len(srcs):
+        raise ValueError(f"{name}: {flow.shape[0]} maps, {len(srcs)} photographs and {len(sizes)} sizes: one of each per document")
+    dims = []
+    for d, (s, size) in enumerate(zip(srcs, sizes)):
+        hs, ws = _sized_src(s, name, f"srcs[{d}]")
+        if s.device != flow.device:
+            raise ValueError(f"{name}: srcs[{d}] is on {s.device}, flow on {flow.device}")
+        dims.append((hs, ws, *_sized_size(size, f"{name}: sizes[{d}]")))
+    if not srcs:
+        return ([], []) if return_stats else []
+    outs = [o.view(hp, wp, 3) for o, (_, _, hp, wp) in zip(_carve([3 * hp * wp for _, _, hp, wp in dims], flow.device), dims)]
+    tab = (lib.SizedImage * len(srcs))()
+    for d, (s, o, (hs, ws, hp, wp)) in enumerate(zip(srcs, outs, dims)):
+        tab[d].src, tab[d].out, tab[d].hs, tab[d].ws, tab[d].hp, tab[d].wp = s.data_ptr(), o.data_ptr(), hs, ws, hp, wp
+    stats = torch.empty((len(srcs), lib.SIZED_STATS), dtype=torch.int64, device=flow.device) if return_stats else None
+    lib.call("dvd_unwarp_u8_sized_ragged", ptr(flow), int(flow.shape[2]), tab, len(srcs), cscale, max_radius, ptr(stats), stream_ptr())
+    return (outs, _sized_counts(stats)) if return_stats else outs
+
+
+def sized_footprint(flow: torch.Tensor, src_hw, size, scale: float = 0.987, max_radius: int = 16, out: torch.Tensor = None) -> torch.Tensor:
+    """[hp,wp] int16: rx | ry << 8, the radii unwarp_u8_sized uses at every page pixel for a photograph of src_hw = (H, W); 0
+    where the grid value is not finite.  A radius equal to max_radius may be the cap (unwarp_u8_sized's `capped` counts where
+    it is).  The same position and footprint code, no gather: no photograph is needed."""
+    name = "sized_footprint"
+    if not isinstance(src_hw, (tuple, list)) or len(src_hw) != 2 or not all(_is_int(v) for v in src_hw):
+        raise ValueError(f"{name}: src_hw must be two integers (H, W), got {src_hw!r}")
+    hs, ws = _synth_sides(src_hw[0], src_hw[1], name, "the photograph")
+    hp, wp = _sized_size(size, name)
+    max_radius = _sized_radius(max_radius, name)
+    cscale = _inv_scale(scale, name)
+    flow, g = _inv_flow(flow, name)
+    out = _inv_out(out, (hp, wp), torch.int16, flow.device, name)
+    lib.call("dvd_sized_footprint", ptr(flow), g, hs, ws, hp, wp, cscale, max_radius, ptr(out), stream_ptr())
+    return out

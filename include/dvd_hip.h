@@ -919,6 +919,46 @@ int dvd_synth_render_rgb8(const uint8_t* scan, int hs, int ws, const float* fwd,
 /* out [h,w,2] u8 <- the radii (rx, ry) the render uses at every covered pixel, 0 at the others.  One launch. */
 int dvd_synth_footprint(const float* fwd, int h, int w, int hs, int ws, uint8_t* out, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Pages at a chosen size (tests/sized_model.py is the definition).  The photograph src [hs,ws,3] u8 is unwarped
+ * through flow [2,g,g] to a page of hp x wp, any size 1..16384.  Per page pixel (i, j): the grid value of dvd_unwarp_grid at
+ * the page's size (at hp = hs, wp = ws the native tail's own, bit for bit); the signed Q8 position floor(256 x + 1/2) of
+ * x = (gx + 1) ((ws - 1) / 2) on the photograph, moved to 17 pixels outside it where it is further out; integer radii
+ * rx, ry = 1..max_radius from the doubled first differences of those positions over the page's 4-neighbours; and the separable
+ * integer tent of dvd_synth_render_rgb8 with that half-width over the PHOTOGRAPH (rx = ry = 1 is Q8 bilinear sampling).  A tap
+ * outside the photograph contributes zero and its weight still counts (padding_mode='zeros'), so the divisor is the constant
+ * 65536 rx^2 ry^2 and the byte is ROUNDED once - the native u8 tail truncates.  A pixel whose grid value is not finite is
+ * black and its neighbours' differences go without it.
+ * stats (device, DVD_SIZED_STATS 8-byte words per document, or NULL): the page pixels whose uncapped radius exceeded max_radius,
+ * whose centre lies outside the photograph, and whose grid value is not finite - exact integers, added with integer atomics.
+ * Sides 1..16384 and g 2..8192 (else DVD_E_SIZED_SHAPE), a finite scale and max_radius 1..16 (DVD_E_SIZED_PARAM), no null
+ * pointer and a page that shares no byte with its photograph (DVD_E_ARG): all refused before any HIP call.  No scratch
+ * memory; equal calls give equal bytes.
+ * ---------------------------------------------------------------------------------------- */
+#define DVD_E_SIZED_SHAPE (-59)
+#define DVD_E_SIZED_PARAM (-60)
+#define DVD_SIZED_STATS 3
+/* out [hp,wp,3] u8, any byte alignment.  One launch (and one memset of stats). */
+int dvd_unwarp_u8_sized(const float* flow, int g, const uint8_t* src, int hs, int ws, uint8_t* out, int hp, int wp, float scale,
+                        int max_radius, unsigned long long* stats, void* stream);
+/* One document of dvd_unwarp_u8_sized_ragged: device pointers to its photograph and its page, and their sizes. */
+typedef struct {
+  const uint8_t* src; /* [hs,ws,3] uint8 */
+  uint8_t* out;       /* [hp,wp,3] uint8 */
+  int hs, ws, hp, wp;
+} dvd_sized_image;
+/* flow [n,2,g,g], stats [n,DVD_SIZED_STATS] or NULL: docs[d].out and the counts of document d equal those of
+ * dvd_unwarp_u8_sized(flow + d*2*g*g, g, docs[d]..., scale, max_radius, stats + d*DVD_SIZED_STATS) byte for byte.  docs is a
+ * HOST array read during the call only; at most DVD_RAGGED_CAP documents and 2^23 tiles of 64 x 16 page pixels go into one
+ * launch (a larger batch is cut into several).  Documents may share a photograph; a page may share no byte with any photograph
+ * or any other page of its launch (DVD_E_ARG, before any HIP call). */
+int dvd_unwarp_u8_sized_ragged(const float* flow, int g, const dvd_sized_image* docs, int n, float scale, int max_radius,
+                               unsigned long long* stats, void* stream);
+/* out [hp,wp] u16 <- rx | ry << 8, the radii dvd_unwarp_u8_sized uses at every page pixel for a photograph of hs x ws, 0 where
+ * the grid value is not finite.  A radius equal to max_radius may be the cap.  One launch; no photograph is read. */
+int dvd_sized_footprint(const float* flow, int g, int hs, int ws, int hp, int wp, float scale, int max_radius, uint16_t* out,
+                        void* stream);
+
 #ifdef __cplusplus
 }
 #endif
