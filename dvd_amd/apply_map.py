@@ -16,7 +16,13 @@ value is not finite.
 
 carries the N x 2 coordinates (x y per line, in pixels) of PTS.txt through the map instead: --to page takes positions on the
 photograph IMAGE to the dewarped page (ops.map_invert, ops.transfer_points; "nan nan" where the page does not reach), --to photo
-takes positions on the page to the photograph (ops.map_points).  IMAGE is opened for its size only."""
+takes positions on the page to the photograph (ops.map_points).  IMAGE is opened for its size only.
+
+    python -m dvd_amd.apply_map MAP.npy IMAGE OUT.png [--size SPEC] --clean flatten|binarize|flatten,binarize
+
+cleans the page after the unwarp, at either size: `flatten` divides the illumination out by a paper estimate,
+`binarize` writes Sauvola's black-and-white plane (of the flattened page where both are given), at ops.page_clean's defaults;
+one more line prints the three counts: channel samples that saturated, samples whose paper estimate was raised, ink pixels."""
 import argparse
 
 import numpy as np
@@ -34,7 +40,19 @@ def load_map(path):
     return np.ascontiguousarray(flow[None], dtype=np.float32)
 
 
-def apply_map(map_path, image_path, out_path, mode="bilinear"):
+def clean_page(page, clean, out_path):
+    """The page [H,W,3] uint8 after the stages of clean = (flatten, binarize), again [H,W,3] (a plane is repeated into RGB), and
+    the counts, and the line that reports them."""
+    from . import ops
+    flatten, binarize = clean
+    out, counts = ops.page_clean(page, flatten=flatten, binarize=binarize, return_stats=True)
+    if binarize:
+        out = out[:, :, None].expand(*out.shape, 3).contiguous()
+    stages = ",".join(s for s, on in zip(ops.CLEAN_STAGES, clean) if on)
+    return out, counts, f"{out_path}: {stages}; " + ", ".join(f"{s} {counts[s]}" for s in ops.CLEAN_STATS)
+
+
+def apply_map(map_path, image_path, out_path, mode="bilinear", clean=None):
     if mode not in WARP_MODES:
         raise ValueError(f"--mode must be one of {WARP_MODES}, got {mode!r}")
     flow = load_map(map_path)
@@ -43,7 +61,11 @@ def apply_map(map_path, image_path, out_path, mode="bilinear"):
     from . import ops
     src = torch.from_numpy(np.array(Image.open(image_path).convert("RGB"))).cuda()
     page = ops.unwarp_u8(torch.from_numpy(flow).cuda(), src, mode=mode)
+    if clean is not None:
+        page, _, line = clean_page(page, clean, out_path)
     Image.fromarray(page.cpu().numpy()).save(out_path)
+    if clean is not None:
+        print(line)
     return page
 
 
@@ -51,7 +73,7 @@ class SizeRequestError(ValueError):
     """A --size or --max-radius the page cannot be rendered with: a usage error, unlike a broken map or image file."""
 
 
-def apply_map_sized(map_path, image_path, out_path, size, max_radius=16):
+def apply_map_sized(map_path, image_path, out_path, size, max_radius=16, clean=None):
     """The page at the size `size` asks for (ops.page_size); returns (page, counts) and prints the counts in one line.  A bad
     request is refused before a file is opened."""
     from . import ops
@@ -70,9 +92,14 @@ def apply_map_sized(map_path, image_path, out_path, size, max_radius=16):
     except ValueError as e:
         raise SizeRequestError(f"--size: {image_path} is {int(src.shape[0])} x {int(src.shape[1])}: {e}") from None
     page, counts = ops.unwarp_u8_sized(torch.from_numpy(flow[0]).cuda(), src, (hp, wp), max_radius=max_radius, return_stats=True)
+    if clean is not None:
+        page, cleaned, line = clean_page(page, clean, out_path)
     Image.fromarray(page.cpu().numpy()).save(out_path)
     print(f"{out_path}: {hp} x {wp} from {int(src.shape[0])} x {int(src.shape[1])}; capped {counts['capped']}, outside {counts['outside']}, "
           f"invalid {counts['invalid']}")
+    if clean is not None:
+        print(line)
+        counts = {**counts, **cleaned}
     return page, counts
 
 
@@ -135,14 +162,25 @@ def main(argv=None):
                    "(footprint-filtered, bilinear only)")
     p.add_argument("--max-radius", type=int, default=None, help="with --size: the filter's largest half-width in photograph pixels, "
                    "1..16 (default 16)")
+    p.add_argument("--clean", default=None, metavar="STAGES", help="clean the page after the unwarp: 'flatten', 'binarize' or "
+                   "'flatten,binarize'")
     a = p.parse_args(argv)
+    clean = None
+    if a.clean is not None:
+        from . import ops
+        if a.points is not None:
+            p.error("--clean cleans a page: it cannot be combined with --points")
+        try:
+            clean = ops.parse_clean(a.clean)
+        except ValueError as e:
+            p.error(f"--clean: {e}")
     if a.size is not None:
         if a.points is not None:
             p.error("--size renders a page: it cannot be combined with --points")
         if a.mode != "bilinear":
             p.error(f"--size filters bilinearly: it cannot be combined with --mode {a.mode}")
         try:
-            apply_map_sized(a.map, a.image, a.out, a.size, 16 if a.max_radius is None else a.max_radius)
+            apply_map_sized(a.map, a.image, a.out, a.size, 16 if a.max_radius is None else a.max_radius, clean)
         except SizeRequestError as e:
             p.error(str(e))
         return
@@ -151,7 +189,7 @@ def main(argv=None):
     if a.points is not None:
         apply_points(a.map, a.image, a.out, a.points, a.to, a.step)
         return
-    apply_map(a.map, a.image, a.out, a.mode)
+    apply_map(a.map, a.image, a.out, a.mode, clean)
 
 
 if __name__ == "__main__":

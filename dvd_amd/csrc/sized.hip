@@ -15,6 +15,7 @@
 //   sized_footprint_kernel      the same staging; the radii as two bytes per pixel, no gather
 // No scratch memory.
 #include "common.h"
+#include "hwc_bytes.h"
 #include "sized_core.h"
 
 namespace dvd {
@@ -59,25 +60,6 @@ __device__ __forceinline__ void stage_tile(const float* __restrict__ flow, const
     s.tile[i] = p;
   }
   __syncthreads();
-}
-
-// Twelve bytes d0 | d1 | d2 (little endian) to dst, which may begin anywhere: whole dwords where dst is on one, else
-// head = 4 - (dst & 3) single bytes, the two dwords between, and the 4 - head bytes left.  Only shifts: no indexed registers.
-__device__ __forceinline__ void store12(uint8_t* __restrict__ dst, uint32_t d0, uint32_t d1, uint32_t d2) {
-  const unsigned m = (unsigned)((uintptr_t)dst & 3);
-  if (m == 0) {
-    uint32_t* p = reinterpret_cast<uint32_t*>(dst);
-    p[0] = d0;
-    p[1] = d1;
-    p[2] = d2;
-    return;
-  }
-  const unsigned head = 4 - m, sh = 8 * head;             // 1..3 bytes, 8..24 bits
-  for (unsigned k = 0; k < head; ++k) dst[k] = (uint8_t)(d0 >> (8 * k));
-  uint32_t* p = reinterpret_cast<uint32_t*>(dst + head);
-  p[0] = d0 >> sh | d1 << (32 - sh);
-  p[1] = d1 >> sh | d2 << (32 - sh);
-  for (unsigned k = 0; k < m; ++k) dst[head + 8 + k] = (uint8_t)(d2 >> (sh + 8 * k));
 }
 
 // One tile of one document.  Every thread of the workgroup comes here and reaches every barrier.

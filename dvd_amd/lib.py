@@ -149,6 +149,9 @@ class SizedImage(C.Structure):
     _fields_ = [("src", C.c_void_p), ("out", C.c_void_p), ("hs", C.c_int), ("ws", C.c_int), ("hp", C.c_int), ("wp", C.c_int)]
 
 
+E_CLEAN_SHAPE, E_CLEAN_PARAM = -61, -62    # DVD_E_CLEAN_*: what the scan-like page refuses
+CLEAN_STATS = 3                            # DVD_CLEAN_STATS: the counts of a cleaned page (saturated, floored, ink)
+
 RAGGED_CAP = 64  # DVD_RAGGED_CAP: documents per launch of the ragged entry points (larger batches are cut by the library)
 
 NON_STATUS = {"dvd_last_error", "dvd_version", "dvd_engine_workspace_bytes", "dvd_engine_tensor_count",
@@ -157,7 +160,8 @@ NON_STATUS = {"dvd_last_error", "dvd_version", "dvd_engine_workspace_bytes", "dv
               "dvd_msssim_workspace_bytes", "dvd_png_bound", "dvd_png_scratch_bytes", "dvd_png_scratch_bytes_huff", "dvd_jpeg_bound",
               "dvd_jpeg_scratch_bytes", "dvd_sflow_level_workspace_bytes", "dvd_sflow_workspace_bytes",
               "dvd_adist_workspace_bytes", "dvd_corrupt_supported", "dvd_corrupt_table", "dvd_map_deviation_workspace_bytes",
-              "dvd_flow_workspace_bytes", "dvd_mapscore_workspace_bytes", "dvd_map_invert_workspace_bytes"}
+              "dvd_flow_workspace_bytes", "dvd_mapscore_workspace_bytes", "dvd_map_invert_workspace_bytes",
+              "dvd_page_clean_workspace_bytes"}
 
 # name -> argtypes; kept in one table so tests can check every symbol of include/dvd_hip.h
 SIGNATURES = {
@@ -265,6 +269,12 @@ SIGNATURES = {
     "dvd_unwarp_u8_sized": [c_void, C.c_int, c_void, C.c_int, C.c_int, c_void, C.c_int, C.c_int, C.c_float, C.c_int, c_void, c_void],
     "dvd_unwarp_u8_sized_ragged": [c_void, C.c_int, C.POINTER(SizedImage), C.c_int, C.c_float, C.c_int, c_void, c_void],
     "dvd_sized_footprint": [c_void, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, c_void, c_void],
+    "dvd_page_clean_workspace_bytes": [C.c_int, C.c_int, C.c_int],
+    "dvd_page_background": [c_void, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_void, c_void, c_void],
+    "dvd_page_flatten_rgb8": [c_void, C.c_int, C.c_int, c_void, C.c_int, C.c_int, c_void, c_void, c_void, c_void],
+    "dvd_page_binarize_u8": [c_void, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_void, c_void, c_void],
+    "dvd_page_clean_rgb8": [c_void, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                            c_void, c_void, c_void, c_void, c_void],
     "dvd_png_bound": [C.c_int, C.c_int],
     "dvd_png_scratch_bytes": [C.c_int, C.c_int],
     "dvd_png_encode_rgb8": [c_void, C.c_int, C.c_int, c_void, C.c_long, c_void, c_void, c_void],
@@ -301,7 +311,7 @@ RESTYPES = {"dvd_gemm_kernel_name": C.c_char_p, "dvd_ingest_ragged_scratch_bytes
             "dvd_sflow_level_workspace_bytes": C.c_long, "dvd_sflow_workspace_bytes": C.c_long,
             "dvd_adist_workspace_bytes": C.c_long, "dvd_map_deviation_workspace_bytes": C.c_long,
             "dvd_flow_workspace_bytes": C.c_long, "dvd_mapscore_workspace_bytes": C.c_long,
-            "dvd_map_invert_workspace_bytes": C.c_long, "dvd_png_bound": C.c_long, "dvd_png_scratch_bytes": C.c_long, "dvd_png_scratch_bytes_huff": C.c_long,
+            "dvd_map_invert_workspace_bytes": C.c_long, "dvd_page_clean_workspace_bytes": C.c_long, "dvd_png_bound": C.c_long, "dvd_png_scratch_bytes": C.c_long, "dvd_png_scratch_bytes_huff": C.c_long,
             "dvd_jpeg_bound": C.c_long, "dvd_jpeg_scratch_bytes": C.c_long}
 
 # entry points that exist only in the lab build (benchmarks/lab/dvd_hip_lab.h; loaded through use_library)

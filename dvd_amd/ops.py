@@ -2092,3 +2092,152 @@ def sized_footprint(flow: torch.Tensor, src_hw, size, scale: float = 0.987, max_
     out = _inv_out(out, (hp, wp), torch.int16, flow.device, name)
     lib.call("dvd_sized_footprint", ptr(flow), g, hs, ws, hp, wp, cscale, max_radius, ptr(out), stream_ptr())
     return out
+
+
+# ---- scan-like pages: the paper estimate, the flattened page and Sauvola's plane (dvd_amd/csrc/clean.hip; definition:
+# DESIGN.md 4.17, tests/clean_model.py)
+CLEAN_CELLS = (4, 8, 16, 32, 64)
+CLEAN_MAX_SIDE, CLEAN_MAX_CLOSE, CLEAN_MAX_SMOOTH, CLEAN_MAX_RADIUS, CLEAN_MAX_KQ = 16384, 8, 8, 63, 256
+CLEAN_STATS = ("saturated", "floored", "ink")
+CLEAN_STAGES = ("flatten", "binarize")
+
+
+def parse_clean(spec):
+    """A --clean request 'flatten', 'binarize' or 'flatten,binarize' as (flatten, binarize); anything else is a ValueError that
+    names the value.  Host only."""
+    parts = [p.strip() for p in spec.split(",")] if isinstance(spec, str) else None
+    if not parts or any(p not in CLEAN_STAGES for p in parts) or len(set(parts)) != len(parts):
+        raise ValueError(f"clean: {spec!r}: expected 'flatten', 'binarize' or 'flatten,binarize'")
+    return "flatten" in parts, "binarize" in parts
+
+
+def _clean_int(v, lo, hi, name, what):
+    if not _is_int(v) or not lo <= v <= hi:
+        raise ValueError(f"{name}: {what} must be an integer {lo}..{hi}, got {v!r}")
+    return int(v)
+
+
+def _clean_background_params(cell, close, smooth, name):
+    if not _is_int(cell) or cell not in CLEAN_CELLS:
+        raise ValueError(f"{name}: cell must be one of {CLEAN_CELLS}, got {cell!r}")
+    return int(cell), _clean_int(close, 0, CLEAN_MAX_CLOSE, name, "close"), _clean_int(smooth, 0, CLEAN_MAX_SMOOTH, name, "smooth")
+
+
+def clean_kq(k, name="page_binarize"):
+    """Sauvola's k as kq = round(256 k), a half rounding up: 0..256.  Host only."""
+    if isinstance(k, bool) or not isinstance(k, (int, float)) or not np.isfinite(k) or not 0 <= np.floor(256 * float(k) + 0.5) <= CLEAN_MAX_KQ:
+        raise ValueError(f"{name}: k must be a number in 0..1, got {k!r}")
+    return int(np.floor(256 * float(k) + 0.5))
+
+
+def _clean_page(img, name, what="img", planes=(3,)):
+    """A page [H,W,3] uint8 (planes holds 1: also a gray plane [H,W]) on the device: (h, w, channels)."""
+    shapes = "[H,W,3]" + (" or [H,W]" if 1 in planes else "")
+    if not torch.is_tensor(img) or not img.is_cuda:
+        raise ValueError(f"{name}: {what} must be a {shapes} uint8 tensor on the device, got "
+                         f"{img.device if torch.is_tensor(img) else type(img)}")
+    if img.dtype != torch.uint8 or not img.is_contiguous():
+        raise ValueError(f"{name}: {what} must be contiguous uint8, got {img.dtype} contiguous={img.is_contiguous()}")
+    if not ((img.dim() == 3 and img.shape[2] == 3) or (img.dim() == 2 and 1 in planes)):
+        raise ValueError(f"{name}: {what} must be {shapes}, got {tuple(img.shape)}")
+    h, w = int(img.shape[0]), int(img.shape[1])
+    if not 1 <= h <= CLEAN_MAX_SIDE or not 1 <= w <= CLEAN_MAX_SIDE:
+        raise ValueError(f"{name}: the sides of {what} must be 1..{CLEAN_MAX_SIDE}, got {h} x {w}")
+    return h, w, 3 if img.dim() == 3 else 1
+
+
+def _clean_disjoint(out, img, name, what="out"):
+    if out.data_ptr() < img.data_ptr() + img.numel() and img.data_ptr() < out.data_ptr() + out.numel():
+        raise ValueError(f"{name}: {what} must share no byte with the input")
+
+
+def _clean_workspace(h, w, cell, dev):
+    return torch.empty(_size_query("dvd_page_clean_workspace_bytes", h, w, cell), dtype=torch.uint8, device=dev)
+
+
+def _clean_counts(stats, names):
+    return dict(zip(names, (int(v) for v in stats.cpu().tolist())))
+
+
+def page_background(img: torch.Tensor, cell: int = 16, close: int = 2, smooth: int = 2, neutral: bool = True) -> torch.Tensor:
+    """The paper estimate [3,hc,wc] uint8 of the page img [H,W,3] uint8, hc = ceil(H / cell), wc = ceil(W / cell): per channel
+    the maximum of every cell of cell x cell pixels (cell in 4, 8, 16, 32, 64), closed with a (2 close + 1)^2 window (ink
+    narrower than that many cells is bridged; close 0..8) and smoothed with a tent of half-width `smooth` cells (0..8), every
+    window clipped to the plane, rounded once.  neutral=False: one gray plane (R + 2G + B + 2) >> 2 of that estimate stands for
+    all three channels, so a later flatten keeps the colour cast.  Two launches; integer arithmetic, equal calls give equal bytes."""
+    name = "page_background"
+    cell, close, smooth = _clean_background_params(cell, close, smooth, name)
+    h, w, _ = _clean_page(img, name)
+    bg = torch.empty((3, -(-h // cell), -(-w // cell)), dtype=torch.uint8, device=img.device)
+    ws = _clean_workspace(h, w, cell, img.device)
+    lib.call("dvd_page_background", ptr(img), h, w, cell, close, smooth, 1 if neutral else 0, ptr(bg), ptr(ws), stream_ptr())
+    return bg
+
+
+def page_flatten(img: torch.Tensor, cell: int = 16, close: int = 2, smooth: int = 2, neutral: bool = True, white: int = 255,
+                 background: torch.Tensor = None, out: torch.Tensor = None, return_stats: bool = False):
+    """The page img [H,W,3] uint8 with its illumination divided out: every sample becomes min(255, v white / bg) with bg the
+    paper estimate of page_background(img, cell, close, smooth, neutral) sampled bilinearly between the cell centres and raised
+    to at least one level - a constant page comes out as exactly `white` (1..255).  background: a [3,hc,wc] uint8 estimate to
+    use instead (close, smooth and neutral are not read then).  return_stats=True: also {saturated, floored}, the channel
+    samples whose quotient exceeded 255 and whose background was raised: exact integers.  img is not written."""
+    name = "page_flatten"
+    cell, close, smooth = _clean_background_params(cell, close, smooth, name)
+    white = _clean_int(white, 1, 255, name, "white")
+    h, w, _ = _clean_page(img, name)
+    dev = img.device
+    shape = (3, -(-h // cell), -(-w // cell))
+    if background is None:
+        background = page_background(img, cell, close, smooth, neutral)
+    elif not torch.is_tensor(background) or background.device != dev or background.dtype != torch.uint8 or \
+            not background.is_contiguous() or tuple(background.shape) != shape:
+        raise ValueError(f"{name}: background must be a contiguous uint8 tensor {shape} on {dev} (cell = {cell})")
+    out = _inv_out(out, (h, w, 3), torch.uint8, dev, name)
+    _clean_disjoint(out, img, name)
+    _clean_disjoint(out, background, name)
+    stats = torch.empty(2, dtype=torch.int64, device=dev) if return_stats else None
+    lib.call("dvd_page_flatten_rgb8", ptr(img), h, w, ptr(background), cell, white, ptr(out), None, ptr(stats), stream_ptr())
+    return (out, _clean_counts(stats, CLEAN_STATS[:2])) if return_stats else out
+
+
+def page_binarize(img_or_gray: torch.Tensor, radius: int = 15, k: float = 0.2, out: torch.Tensor = None, return_stats: bool = False):
+    """The black-and-white plane [H,W] uint8 (0 ink, 255 paper) of a page [H,W,3] uint8 - its gray (R + 2G + B + 2) >> 2 - or of
+    a gray plane [H,W] uint8, by Sauvola's rule in integers: ink where g <= m (1 + k (sd / 128 - 1)) with the mean m and the
+    standard deviation sd of the (2 radius + 1)^2 window clipped to the page (radius 1..63); k is quantised to
+    kq = round(256 k), 0..256, and the square root is an exact floor.  return_stats=True: also {ink}, the ink pixels."""
+    name = "page_binarize"
+    radius = _clean_int(radius, 1, CLEAN_MAX_RADIUS, name, "radius")
+    kq = clean_kq(k, name)
+    h, w, channels = _clean_page(img_or_gray, name, "img_or_gray", planes=(1, 3))
+    dev = img_or_gray.device
+    out = _inv_out(out, (h, w), torch.uint8, dev, name)
+    _clean_disjoint(out, img_or_gray, name)
+    stats = torch.empty(1, dtype=torch.int64, device=dev) if return_stats else None
+    lib.call("dvd_page_binarize_u8", ptr(img_or_gray), channels, h, w, radius, kq, ptr(out), ptr(stats), stream_ptr())
+    return (out, _clean_counts(stats, CLEAN_STATS[2:])) if return_stats else out
+
+
+def page_clean(img: torch.Tensor, flatten: bool = True, binarize: bool = False, cell: int = 16, close: int = 2, smooth: int = 2,
+               neutral: bool = True, white: int = 255, radius: int = 15, k: float = 0.2, return_stats: bool = False):
+    """The chain on one page img [H,W,3] uint8 in one workspace: page_flatten (flatten=True), then page_binarize of its result
+    (binarize=True) - or of img where flatten=False.  Returns the plane [H,W] uint8 with binarize, else the flattened page
+    [H,W,3] uint8: the bytes of the single calls.  The flattened page's gray plane is written by the flatten kernel, so the
+    binarise stage reads no RGB page again.  return_stats=True: also {saturated, floored, ink}; a stage that does not run
+    counts 0."""
+    name = "page_clean"
+    if not flatten and not binarize:
+        raise ValueError(f"{name}: flatten and binarize are both off: nothing to do")
+    cell, close, smooth = _clean_background_params(cell, close, smooth, name)
+    white = _clean_int(white, 1, 255, name, "white")
+    radius = _clean_int(radius, 1, CLEAN_MAX_RADIUS, name, "radius")
+    kq = clean_kq(k, name)
+    h, w, _ = _clean_page(img, name)
+    dev = img.device
+    page = torch.empty((h, w, 3), dtype=torch.uint8, device=dev) if flatten else None
+    plane = torch.empty((h, w), dtype=torch.uint8, device=dev) if binarize else None
+    ws = _clean_workspace(h, w, cell, dev)
+    stats = torch.empty(lib.CLEAN_STATS, dtype=torch.int64, device=dev) if return_stats else None
+    lib.call("dvd_page_clean_rgb8", ptr(img), h, w, cell, close, smooth, 1 if neutral else 0, white, 1 if flatten else 0,
+             1 if binarize else 0, radius, kq, ptr(page), ptr(plane), ptr(stats), ptr(ws), stream_ptr())
+    result = plane if binarize else page
+    return (result, _clean_counts(stats, CLEAN_STATS)) if return_stats else result

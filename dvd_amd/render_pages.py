@@ -7,7 +7,12 @@ the stem's leading integer (evaluation.gt_candidates' rule).  SPEC is what ops.p
 Documents of different sizes go --batch at a time through ops.unwarp_u8_sized_ragged - one launch filters every photograph by
 its own footprint - and the pages are written by the device encoders, so only compressed bytes come back to the
 host.  OUT/manifest.json records, per document, the photograph's size, the page's size and the three counts.  A map without a
-photograph is logged and skipped."""
+photograph is logged and skipped.
+
+    ... --clean flatten|binarize|flatten,binarize
+
+cleans every page after the unwarp (ops.page_clean at its defaults, DESIGN.md 4.17: the illumination divided out, Sauvola's
+black-and-white plane, or both); the manifest then also names the stages and, per document, the counts saturated, floored and ink."""
 import argparse
 import json
 import os
@@ -79,10 +84,19 @@ class DeviceBackend:
     def shape(self, photo):
         return int(photo.shape[0]), int(photo.shape[1])
 
+    def clean(self, page, flatten, binarize):
+        """(the cleaned page, again [H,W,3] - a plane is repeated into RGB; its counts)"""
+        out, counts = self.ops.page_clean(page, flatten=flatten, binarize=binarize, return_stats=True)
+        if binarize:
+            out = out[:, :, None].expand(*out.shape, 3).contiguous()
+        return out, counts
 
-def render_pages(map_dir, image_dir, out_dir, size, fmt="png", quality=90, batch=8, max_radius=16, log=print, backend=None):
-    """Render every map of map_dir; returns the manifest (also written to out_dir/manifest.json)."""
+
+def render_pages(map_dir, image_dir, out_dir, size, fmt="png", quality=90, batch=8, max_radius=16, log=print, backend=None, clean=None):
+    """Render every map of map_dir; returns the manifest (also written to out_dir/manifest.json).  clean: None, or a --clean
+    request (ops.parse_clean), applied to every page after the unwarp."""
     from . import ops
+    stages = None if clean is None else ops.parse_clean(clean)
     if fmt not in FORMATS:
         raise ValueError(f"--format must be one of {tuple(FORMATS)}, got {fmt!r}")
     if isinstance(quality, bool) or not isinstance(quality, int) or not 1 <= quality <= 100:
@@ -124,16 +138,24 @@ def render_pages(map_dir, image_dir, out_dir, size, fmt="png", quality=90, batch
             pages, counts = backend.render([e[4][0] for e in part], photos, [e[3] for e in part], max_radius)
             for (stem, map_path, image, page_hw, _, photo), page, cnt in zip(part, pages, counts):
                 name = stem + FORMATS[fmt]
+                cleaned = None
+                if stages is not None:
+                    page, cleaned = backend.clean(page, *stages)
                 backend.write(page, os.path.join(out_dir, name), fmt, quality)
                 docs.append(dict(zip(MANIFEST_KEYS, (stem, os.path.basename(map_path), os.path.basename(image), name,
                                                      list(backend.shape(photo)), list(page_hw), cnt["capped"], cnt["outside"], cnt["invalid"]))))
                 log(f"{name}: {page_hw[0]} x {page_hw[1]} from {backend.shape(photo)[0]} x {backend.shape(photo)[1]}; capped {cnt['capped']}, "
                     f"outside {cnt['outside']}, invalid {cnt['invalid']}")
+                if cleaned is not None:
+                    docs[-1].update((s, cleaned[s]) for s in ops.CLEAN_STATS)
+                    log(f"{name}: {clean}; " + ", ".join(f"{s} {cleaned[s]}" for s in ops.CLEAN_STATS))
     for k in range(0, len(todo), batch):
         flush([(*e, load_map(e[1]), backend.load(e[2])) for e in todo[k:k + batch]])
     docs.sort(key=lambda d: d["stem"])
     manifest = {"size": list(size) if isinstance(size, (tuple, list)) else size, "format": fmt, "quality": quality if fmt == "jpeg" else None,
                 "max_radius": max_radius, "documents": docs}
+    if stages is not None:
+        manifest["clean"] = ",".join(s for s, on in zip(ops.CLEAN_STAGES, stages) if on)
     with open(os.path.join(out_dir, "manifest.json"), "w") as f:
         json.dump(manifest, f, indent=1)
     return manifest
@@ -149,9 +171,11 @@ def main(argv=None):
     p.add_argument("--quality", type=int, default=90, help="JPEG quality 1..100")
     p.add_argument("--batch", type=int, default=8, help="documents per launch")
     p.add_argument("--max-radius", type=int, default=16, help="the filter's largest half-width in photograph pixels, 1..16")
+    p.add_argument("--clean", default=None, metavar="STAGES", help="clean every page after the unwarp: 'flatten', 'binarize' or "
+                   "'flatten,binarize'")
     a = p.parse_args(argv)
     try:
-        render_pages(a.map_dir, a.image_dir, a.out, a.size, a.format, a.quality, a.batch, a.max_radius)
+        render_pages(a.map_dir, a.image_dir, a.out, a.size, a.format, a.quality, a.batch, a.max_radius, clean=a.clean)
     except ValueError as e:
         p.error(str(e))
 

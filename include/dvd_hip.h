@@ -959,6 +959,51 @@ int dvd_unwarp_u8_sized_ragged(const float* flow, int g, const dvd_sized_image* 
 int dvd_sized_footprint(const float* flow, int g, int hs, int ws, int hp, int wp, float scale, int max_radius, uint16_t* out,
                         void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Scan-like pages (tests/clean_model.py is the definition).  All integer arithmetic; equal calls give equal
+ * bytes.  A page is img [h,w,3] u8, sides 1..16384 (else DVD_E_CLEAN_SHAPE).
+ *   background  cell s in {4,8,16,32,64}: the coarse plane has hc = ceil(h/s) x wc = ceil(w/s) cells.  Per channel: the maximum
+ *               of every cell (cut at the page's edge); a closing with a (2 close + 1)^2 window, close 0..8 (maximum, then
+ *               minimum, windows clipped to the plane); a separable tent 1, 2, .., smooth + 1, .., 2, 1, smooth 0..8, over the
+ *               clipped window, bg = (2 num + den) / (2 den) rounded once.  neutral == 0: the plane (R + 2 G + B + 2) >> 2 of
+ *               that result stands for all three channels (the colour cast stays).
+ *   flatten     bg is sampled bilinearly between cell centres (i + 1/2) s - 1/2 in units of 1/(2s), clamped at the plane's edge:
+ *               bgQ = 4 s^2 x the sample, raised to at least 4 s^2; q = (v white 4 s^2 + bgQ / 2) / bgQ, out = min(255, q),
+ *               white 1..255.  Counts: samples with q > 255 (saturated) and samples whose bgQ was raised (floored).
+ *   binarise    Sauvola's rule on g = (R + 2 G + B + 2) >> 2 over the (2 radius + 1)^2 window clipped to the page, radius 1..63,
+ *               kq = round(256 k) in 0..256, R = 128: with N, S1 = sum g, S2 = sum g^2 and sN = floor(sqrt(N S2 - S1^2)) the
+ *               pixel is ink (0) iff g N (256 R N) <= S1 (256 R N) + kq S1 (sN - R N), else 255.  Count: the ink pixels.
+ * A parameter outside its range is DVD_E_CLEAN_PARAM; a null pointer, a misaligned count pointer or an output that shares bytes
+ * with an input is DVD_E_ARG: all refused before any HIP call.  The counts are exact integers (DVD_CLEAN_STATS 8-byte words in
+ * the order saturated, floored, ink), added with integer atomics; an entry point zeroes the words it counts into.  No scratch
+ * memory.
+ * ---------------------------------------------------------------------------------------- */
+#define DVD_E_CLEAN_SHAPE (-61)
+#define DVD_E_CLEAN_PARAM (-62)
+#define DVD_CLEAN_STATS 3
+/* bytes of `ws` for a page of h x w at cell size `cell`, 256-byte aligned pieces in this order: the cell maxima [3,hc,wc], the
+ * background [3,hc,wc] and the gray plane [h,w]; DVD_E_CLEAN_SHAPE / DVD_E_CLEAN_PARAM for a bad size or cell.  Host only. */
+long dvd_page_clean_workspace_bytes(int h, int w, int cell);
+/* bg [3,hc,wc] u8 <- img.  ws: dvd_page_clean_workspace_bytes(h, w, cell) bytes (the cell maxima are kept there).  Two
+ * launches. */
+int dvd_page_background(const uint8_t* img, int h, int w, int cell, int close, int smooth, int neutral, uint8_t* bg, void* ws,
+                        void* stream);
+/* out [h,w,3] u8 (any byte alignment) <- img flattened by bg [3,hc,wc] u8.  gray [h,w] u8 or NULL: the plane g of OUT.
+ * stats: 2 words (saturated, floored) or NULL.  One launch (and one memset of stats). */
+int dvd_page_flatten_rgb8(const uint8_t* img, int h, int w, const uint8_t* bg, int cell, int white, uint8_t* out, uint8_t* gray,
+                          unsigned long long* stats, void* stream);
+/* out [h,w] u8 (0 ink, 255 paper) <- img [h,w,channels] u8, channels 3 (RGB) or 1 (a gray plane, taken as g).  ink: 1 word or
+ * NULL.  One launch (and one memset of ink). */
+int dvd_page_binarize_u8(const uint8_t* img, int channels, int h, int w, int radius, int kq, uint8_t* out, unsigned long long* ink,
+                         void* stream);
+/* The chain in one workspace: the background and the flattened page (flatten != 0: page [h,w,3] u8), then the Sauvola plane of
+ * that page - or of img where flatten == 0 - (binarize != 0: plane [h,w] u8).  At least one of the two; the output that is not
+ * asked for may be NULL.  stats: DVD_CLEAN_STATS words or NULL; a count of a stage that does not run is 0.  The flattened
+ * page's gray plane goes through ws, so binarising reads no RGB page again. */
+int dvd_page_clean_rgb8(const uint8_t* img, int h, int w, int cell, int close, int smooth, int neutral, int white, int flatten,
+                        int binarize, int radius, int kq, uint8_t* page, uint8_t* plane, unsigned long long* stats, void* ws,
+                        void* stream);
+
 #ifdef __cplusplus
 }
 #endif
